@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- the north-star measurement: batched PNG decode (inflate + unfilter) of 4K RGBA8 images.
 
-    python bench.py --gpus N --steps K --warmup W [--mode decode|encode] [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--mode decode|encode] [--scaling strong|weak] [--full] [--dump-outputs DIR]
     (N > 1: one rank per GPU over RCCL; started by torch.distributed.run, or by this script itself when
      it is run plainly with --gpus N)
+
+A plain run does only what the headline needs: it makes the inputs, warms up, times K steps, writes the outputs of the
+last step (--dump-outputs) and prints the line.  `--full` adds everything else: the batch's rasters compared with their
+sources, the same batch on the other encoder's streams, the CPU baseline and the extra legs (copy ceiling, the other
+BASELINE configs, encode, scanline formats ...).
 
 decode (default).  A "step" is one pass of the decode hot path (spng_decode_batch: inflate -> unfilter,
 results left in HBM) over the whole batch.  Workload = BASELINE.json configs[1]: 1024 synthetic
 4096x4096 RGBA8 PNG streams, mixed filters chosen by the reference's own heuristic, DEFLATE level 6.
 The headline line is measured on swift-png-made level-6 streams (the batch's scanlines deflated by the
 device deflater, bit-exact with LZ77.Deflator: a dynamic block every <= 2047 tokens; `--streams`); the
-same scanlines deflated by host zlib (16 K-token blocks) are measured in the same run and reported under
-"zlib_streams".  At N > 1 the default is configs[2]: the SAME 1024
+same scanlines deflated by host zlib (16 K-token blocks) are measured in the same run with --full and reported
+under "zlib_streams".  At N > 1 the default is configs[2]: the SAME 1024
 images sharded 1024/N per GPU ("strong"), every rank decoding its shard in groups whose rasters travel
 to rank 0 over RCCL (grouped point-to-point, xGMI) while the next group decodes; `--scaling weak`
 gives every GPU its own 1024 images instead.  Compressed inputs are resident in HBM before the timed
@@ -20,7 +25,12 @@ region; nothing is copied to the host inside it.
 encode (`--mode encode`).  BASELINE configs[3]: random 4096x4096 RGBA8 rasters -> filter-select ->
 DEFLATE level 9 (spng_encode_batch); a step encodes the whole batch.
 
-The CPU oracle is used only for the `cpu_baseline` leg (rank 0, N = 1, bounded sample).
+The CPU oracle is used only for the `cpu_baseline` leg (rank 0, N = 1, bounded sample, --full).
+
+--dump-outputs DIR (decode mode): after the timed steps, rank 0 writes what the last step handed its caller, as float64 / float32
+.npy files: results.npy (status, written, consumed of every slot), raster_sums.npy (the byte sum of every slot's raster) and
+raster_sample.npy (the raster bytes at DUMP_SAMPLE positions drawn once from a fixed seed over the whole output).  The inputs
+are a function of the arguments alone, so two builds run with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -43,24 +53,38 @@ DEPTH, CHANNELS = 8, 4
 MPIX = W * H / 1e6
 HBM_PEAK_GBPS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 STAGES = ("pinf_find", "pinf_decode", "pinf_resolve", "inflate", "unfilter")
+DUMP_SAMPLE, DUMP_SEED = 1 << 22, 20240607   # --dump-outputs: raster bytes sampled (16 MiB as float32), and where
 PMC_FILE = "r06_pmc_traffic.json"      # rocprofv3 --pmc passes of this very workload (bench.py --traffic / tools/final_run.sh), committed
 
 
-def build_inputs(session, unique: int, threads: int, encoder: str):
+def filter_rows(session, img) -> bytes:
+    """session.filter(img.tobytes(), W, H, DEPTH, CHANNELS, False): the same spng_filter call (the host-buffer form of
+    filter-select), its rows handed back through one numpy buffer instead of a Python list of 64 Mi ints (1 s per image)"""
+    import numpy as np
+    import swift_png_amd as spng
+    src = np.ascontiguousarray(img, dtype=np.uint8)
+    dst = np.empty(spng.inflated_size(W, H, DEPTH, CHANNELS, False), dtype=np.uint8)
+    res = spng.Result()
+    spng._check(session.lib, session.lib.spng_filter(session.ctx, ctypes.c_void_p(src.ctypes.data), W, H, DEPTH, CHANNELS, 0,
+                                                     ctypes.c_void_p(dst.ctypes.data), ctypes.byref(res)))
+    return dst.tobytes()
+
+
+def build_inputs(session, unique: int, threads: int, encoder: str, verify: bool = True):
     """-> (rasters, filtered rows, streams).  Product path only: synthetic rasters -> GPU filter-select
     (spng_filter, the reference heuristic) -> level-6 DEFLATE, by zlib on the host cores or by the
-    device deflater (swift-png's own bitstream)."""
+    device deflater (swift-png's own bitstream).  verify: every stream inflated again by zlib."""
     from swift_png_amd import synth
     with ThreadPoolExecutor(threads) as pool:
         images = list(pool.map(lambda s: synth.image(s, W, H, CHANNELS, DEPTH), range(unique)))
-        rows = [session.filter(img.tobytes(), W, H, DEPTH, CHANNELS, False) for img in images]
+        rows = [filter_rows(session, img) for img in images]
         if encoder == "swiftpng":
             outs, res = session.deflate_batch([session.to_device(r) for r in rows], 6)
             assert all(r.status == 0 for r in res)
             streams = [bytes(o[:r.written].cpu().numpy()) for o, r in zip(outs, res)]
         else:
             streams = list(pool.map(lambda r: zlib.compress(r, 6), rows))
-        ok = list(pool.map(lambda rz: zlib.decompress(rz[1]) == rz[0], zip(rows, streams)))
+        ok = list(pool.map(lambda rz: zlib.decompress(rz[1]) == rz[0], zip(rows, streams))) if verify else [True]
     assert all(ok)
     return images, rows, streams
 
@@ -223,12 +247,31 @@ class DecodeJob:
         return list((self.spng.Result * self.n).from_buffer_copy(raw))
 
 
-def run_decode(args, torch, dist, spng, s, rank, world, kind, unique, with_gather):
-    """Builds the inputs of `kind` ("zlib" / "swiftpng"), times args.steps steps, checks every slot.
+def dump_outputs(torch, job, path):
+    """--dump-outputs: what the last timed step handed its caller (the module's docstring says which files)"""
+    import numpy as np
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    res = job.results()
+    np.save(path / "results.npy", np.array([(r.status, r.written, r.consumed) for r in res], dtype=np.float64))
+    S = job.S
+    sums = torch.stack([job.d_out[j * S:(j + 1) * S].sum(dtype=torch.int64) for j in range(job.n)])
+    np.save(path / "raster_sums.npy", sums.cpu().numpy().astype(np.float64))
+    total = job.n * S
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, min(DUMP_SAMPLE, total), dtype=np.int64))
+    cut = np.searchsorted(idx, np.arange(job.n + 1) * S)            # (gathered slot by slot: offsets within one raster)
+    sample = torch.cat([job.d_out[j * S:(j + 1) * S][torch.from_numpy(idx[cut[j]:cut[j + 1]] - j * S).to(job.d_out.device)]
+                        for j in range(job.n)])
+    np.save(path / "raster_sample.npy", sample.cpu().numpy().astype(np.float32))
+
+
+def run_decode(args, torch, dist, spng, s, rank, world, kind, unique, with_gather, check=True, dump=None):
+    """Builds the inputs of `kind` ("zlib" / "swiftpng"), times args.steps steps, checks every slot (check: the rasters
+    against their sources too), writes the last step's outputs to `dump` (rank 0).
     -> dict of measurements (rank 0 gets the max-over-ranks time)."""
     from swift_png_amd.distributed import exchange_plan, shard
     cores = os.cpu_count() or 1
-    images, rows, streams = build_inputs(s, unique, min(cores, 32), kind)
+    images, rows, streams = build_inputs(s, unique, min(cores, 32), kind, verify=check)
     d_streams = [s.to_device(z) for z in streams]
     # (the deflater's slabs and torch's cached blocks of the input generation go back to the device before the decode sizes its
     # own scratch: measured without this, the first 128-image call after build_inputs took 292 ms instead of 97)
@@ -312,6 +355,8 @@ def run_decode(args, torch, dist, spng, s, rank, world, kind, unique, with_gathe
     dt = time.perf_counter() - t0
     prof = {k: s.profile_get(getattr(spng, "K_" + k.upper())) for k in STAGES}
     s.profile(False)
+    if dump and rank == 0:
+        dump_outputs(torch, job, dump)
     # N > 1: the same steps without the exchange, so that the line shows what the gather costs on top of the decode
     dt_decode_only = None
     if do_gather:
@@ -324,15 +369,15 @@ def run_decode(args, torch, dist, spng, s, rank, world, kind, unique, with_gathe
         dt_decode_only = time.perf_counter() - t0
         gather_on[0] = True
 
-    # parity of the whole batch: every slot equals its source raster, every status is DONE
+    # every status is DONE; with `check`, parity of the whole batch: every slot equals its source raster
     res = job.results()
     U = job.U
     assert all(r.status == 0 and r.written == U for r in res), [r.status for r in res if r.status][:8]
     fast = sum(r.reserved == 1 for r in res)
-    ref = [s.to_device(img.reshape(-1)) for img in images]
-    for j in range(n):
+    ref = [s.to_device(img.reshape(-1)) for img in images] if check else None
+    for j in range(n if check else 0):
         assert torch.equal(job.d_out[j * S:(j + 1) * S], ref[job.src[j]]), f"slot {first + j} differs"
-    if gathered is not None and do_gather:
+    if check and gathered is not None and do_gather:
         for g in range(0, args.images, max(1, args.images // 16)):
             assert torch.equal(gathered[g * S:(g + 1) * S], ref[g % unique]), f"gathered image {g} differs"
 
@@ -801,7 +846,15 @@ def main():
     ap.add_argument("--encode-steps", type=int, default=3, help="decode mode: timed steps of the two encode legs (after one warm-up)")
     ap.add_argument("--encode-images", type=int, default=1024,
                     help="decode mode: images of the configs[3] leg (BASELINE: 1024)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else this benchmark measures and checks: the rasters against their sources, "
+                         "the other encoder's streams, the CPU baseline and the extra legs (the --no-* options and --legs narrow it); "
+                         "without it only the headline line is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="decode mode: write the outputs of the last timed step to DIR/*.npy (see the module's docstring)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "decode":
+        ap.error("--dump-outputs: decode mode only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(args))
@@ -831,6 +884,7 @@ def main():
 
     if args.mode == "encode":
         from bench_encode import run_encode
+        args.no_cpu_baseline = args.no_cpu_baseline or not args.full
         out = run_encode(args, torch, dist, spng, s, rank, world)
         if rank == 0:
             print(json.dumps(out))
@@ -838,9 +892,9 @@ def main():
             dist.destroy_process_group()
         return
 
-    m = run_decode(args, torch, dist, spng, s, rank, world, args.streams, args.unique, True)
+    m = run_decode(args, torch, dist, spng, s, rank, world, args.streams, args.unique, True, check=args.full, dump=args.dump_outputs)
     other = None
-    if world == 1 and not args.no_swiftpng:
+    if args.full and world == 1 and not args.no_swiftpng:
         alt = "swiftpng" if args.streams == "zlib" else "zlib"
         try:
             other = (alt, run_decode(args, torch, dist, spng, s, rank, world, alt, args.swiftpng_unique, False))
@@ -908,9 +962,9 @@ def main():
                 "ms_per_step": round(mo["dt"] / args.steps * 1e3, 3), "unique_images": args.swiftpng_unique,
                 "compressed_ratio": mo["ratio"], "parallel_inflate_streams": mo["fast"],
                 "inflate_gbps": round(mo["n"] * mo["U"] / (io * 1e-3) / 1e9, 2), "kernels": ko}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(m["streams"], m["images"], m["rows"], cores)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the other BASELINE configs and the path's neighbours, each on a bounded workload (never lose the headline to one)
             only = set(args.legs.split(",")) if args.legs else None
 

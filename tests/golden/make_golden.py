@@ -70,7 +70,33 @@ def main():
             shutil.copyfile(REFERENCE / "Tests" / "Outputs" / f.name, enc / (f.stem + ".swiftpng9.png"))
     (HERE / "encode.json").write_text(json.dumps(digests, indent=1, sort_keys=True) + "\n")
     print(len(digests), "encoder goldens digested,", len(keep), "copied")
+    reference_digests()
+
+
+def reference_digests():
+    """reference.json: sha256 of the reference's own files the fixtures above were taken from -- the decode inputs and
+    their RGBA16 goldens (premultiplied for the iOS set, as above), the encoder's baselines and the IDAT data of its
+    committed outputs -- so that the tests pin the committed copies without a reference checkout."""
+    base = REFERENCE / "Sources" / "PNGIntegrationTests"
+    out = {"pngsuite": {}, "encode": {}}
+    for sub in ("Common", "iOS"):
+        for f in sorted((base / "Inputs" / sub).glob("*.png")):
+            gold = np.frombuffer((base / "RGBA" / (f.name + ".rgba")).read_bytes(), dtype="<u2").reshape(-1, 4)
+            if sub == "iOS":
+                gold = premultiply8(gold)
+            out["pngsuite"][f"{sub.lower()}/{f.name}"] = {
+                "input_sha256": hashlib.sha256(f.read_bytes()).hexdigest(),
+                "rgba16_sha256": hashlib.sha256(np.ascontiguousarray(gold).astype("<u2").tobytes()).hexdigest()}
+    for f in sorted((REFERENCE / "Tests" / "Baselines").glob("*.png")):
+        gold = parse_png((REFERENCE / "Tests" / "Outputs" / f.name).read_bytes())
+        out["encode"][f.stem] = {"baseline_sha256": hashlib.sha256(f.read_bytes()).hexdigest(),
+                                 "output_idat_sha256": hashlib.sha256(gold.idat).hexdigest()}
+    (HERE / "reference.json").write_text(json.dumps(out, indent=1, sort_keys=True) + "\n")
+    print(len(out["pngsuite"]), "decode inputs and", len(out["encode"]), "encoder baselines of the reference digested")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--digests"]:
+        reference_digests()
+    else:
+        main()

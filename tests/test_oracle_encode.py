@@ -74,16 +74,18 @@ def test_stored_tail_departure_of_the_row_pushed_reference():
     assert ph.orc_inflate(pushed, 0, cap=len(rows) + 16)[0] != 0          # (the pinned inflate oracle rejects it as well)
 
 
-@pytest.mark.skipif(not ph.have_reference(), reason="reference checkout not mounted")
 @pytest.mark.parametrize("name", sorted(ENC))
 def test_level9_stream_is_bit_exact_reference(name):
-    base = ph.REFERENCE / "Tests"
-    src = ph.parse_png((base / "Baselines" / (name + ".png")).read_bytes())
-    gold = ph.parse_png((base / "Outputs" / (name + ".png")).read_bytes())
-    assert hashlib.sha256(gold.idat).hexdigest() == ENC[name]["idat_sha256"]
+    """The reference's baseline (the committed copy, byte-identical by its digest) encodes to the IDAT data of the reference's
+    committed output (its digest, taken from the reference's own file by make_golden.py: golden/reference.json)."""
+    ref = json.loads((ph.GOLDEN / "reference.json").read_text())["encode"][name]
+    data = (ph.GOLDEN / "encode" / (name + ".baseline.png")).read_bytes()
+    assert hashlib.sha256(data).hexdigest() == ref["baseline_sha256"]
+    assert ref["output_idat_sha256"] == ENC[name]["idat_sha256"]
+    src = ph.parse_png(data)
     st, storage, _ = ph.orc_decode(src)
     assert st == 0
-    assert _encode9(src, storage) == gold.idat
+    assert hashlib.sha256(_encode9(src, storage)).hexdigest() == ref["output_idat_sha256"]
 
 
 def test_matching_kat():

@@ -141,17 +141,14 @@ enum { SPNG_CFG_INFLATE_MODE = 0,   /* SPNG_INFLATE_AUTO: parallel pipeline, ser
                                               (an experiment: slower than one pass on MI355X, so never by default) */
        SPNG_CFG_RESOLVE_PARTS = 5,         /* parallel inflate, batches of <= 384 streams: workgroups that resolve ONE stream side by
                                               side (0: as many as fill the chip, at most 128 and not below ~1 MiB of output each; 1: one, as in large batches; n: n, at most 128) */
-       SPNG_CFG_DEFLATE_MODE = 6,          /* levels >= 8: SPNG_DEFLATE_AUTO = search and parse in kernels of their own, rounds of 2^21 vertices
-                                              (streams its candidate pool cannot serve: the one-kernel search afterwards);
-                                              SPNG_DEFLATE_ONE_KERNEL = one wave per stream does everything (round 2's kernel) */
-       SPNG_CFG_DEFLATE_BYTES = 7,         /* levels >= 8: size limit of the context's scratch slab (per-stream vertex arrays, candidate
-                                              pool, link rings) in bytes; 0 = half of the free device memory.  Streams that do not
-                                              fit side by side go in groups */
+                                           /* 6: reserved (spng_configure refuses it) */
+       SPNG_CFG_DEFLATE_BYTES = 7,         /* deflate, every level: size limit of the context's scratch slab (the search's records and
+                                              candidate pools, the parse's vertex arrays) in bytes; 0 = half of the free device
+                                              memory.  Streams that do not fit side by side go in groups */
        SPNG_CFG_MULTI_GROUPS = 8,          /* spng_decode_batch_multi: calls a context's shard is cut into when its rasters leave for another
                                               device (a group's copies run beside the next group's decode); 0 = 2, at most 2 */
        SPNG_CFG_COUNT = 9 };
 enum { SPNG_INFLATE_AUTO = 0, SPNG_INFLATE_SERIAL = 1 };
-enum { SPNG_DEFLATE_AUTO = 0, SPNG_DEFLATE_ONE_KERNEL = 1 };
 enum { SPNG_OVERLAP_AUTO = 0, SPNG_OVERLAP_ALWAYS = 1, SPNG_OVERLAP_NEVER = 2 };
 int32_t spng_configure(spng_ctx *ctx, int key, int64_t value);
 

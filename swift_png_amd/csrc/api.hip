@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -78,10 +79,8 @@ struct spng_ctx {
     int slab_next = 0;
     void *h_ws = nullptr;                 // the slab of the call in progress
     Slab *cur = nullptr;
-    void *d_ring = nullptr; size_t ring_cap = 0;     // deflate link rings (greedy / lazy kernel)
-    void *d_ring2 = nullptr; size_t ring2_cap = 0;   // (one-kernel full search)
     // parallel inflate (pinflate2.hip): chunk-record slab, token buffer, knobs (spng_configure)
-    void *d_graph = nullptr; size_t graph_cap = 0;   // deflate levels >= 8: match graphs
+    void *d_graph = nullptr; size_t graph_cap = 0;   // deflate: the search's records and pools, the parse's vertex arrays
     void *d_log = nullptr;  size_t log_cap = 0;
     void *d_tok = nullptr;  size_t tok_cap = 0;      // bytes
     void *d_sym = nullptr;  size_t sym_cap = 0;      // several workgroups per stream: 16-bit symbols, windows (bytes)
@@ -266,8 +265,6 @@ void spng_destroy(spng_ctx *c)
     for (auto e : c->pool) (void)hipEventDestroy(e);
     if (c->d_ws) (void)hipFree(c->d_ws);
     for (auto &sl : c->slabs) { if (sl.h) (void)hipHostFree(sl.h); if (sl.ev) (void)hipEventDestroy(sl.ev); }
-    if (c->d_ring) (void)hipFree(c->d_ring);
-    if (c->d_ring2) (void)hipFree(c->d_ring2);
     if (c->d_graph) (void)hipFree(c->d_graph);
     if (c->d_log) (void)hipFree(c->d_log);
     if (c->d_tok) (void)hipFree(c->d_tok);
@@ -296,7 +293,7 @@ int32_t spng_sync(spng_ctx *c)
 
 int32_t spng_configure(spng_ctx *c, int key, int64_t value)
 {
-    if (!c || key < 0 || key >= SPNG_CFG_COUNT || value < 0) return SPNG_E_ARGUMENT;
+    if (!c || key < 0 || key >= SPNG_CFG_COUNT || key == 6 /* reserved */ || value < 0) return SPNG_E_ARGUMENT;
     std::lock_guard<std::mutex> g(c->mu);
     c->cfg[key] = value;
     return SPNG_DONE;
@@ -1612,199 +1609,127 @@ int32_t spng_pack_as(spng_ctx *c, const void *pixels, uint32_t w, uint32_t h, in
 
 uint64_t spng_deflate_bound(uint64_t n) { return n + n / 4 + 4096; }   // (covers the 18 bytes of a gzip wrapper too)
 
-// The one-kernel full search (deflate_full_kernel) for the streams in `sorted[first, last)`: per-stream graph scratch (129 bytes per
-// vertex, up to 2^21 vertices) from the context's slab, in groups that fit it.  The path of streams the two-kernel search could
-// not finish (its pool ran dry under them), and of SPNG_CFG_DEFLATE_MODE = SPNG_DEFLATE_ONE_KERNEL.
-static int32_t deflate_full_legacy(spng_ctx *c, std::vector<DeflateJob> &sorted, size_t first, size_t last, spng_result *dr, Arena &a, size_t jslot)
+// The context's deflate slab (c->d_graph) for a plan of stream groups: plan(budget, single) cuts the groups for a budget and
+// returns the bytes they need (single: every group is one stream).  The budget is SPNG_CFG_DEFLATE_BYTES, or half of the free
+// memory, and at least `floor`.  When hipMalloc cannot give that much, the budget is halved and the groups cut again, down to
+// one stream per group.  (A launch of this call may still read the slab: it is waited for before the slab moves.)
+static int32_t deflate_slab(spng_ctx *c, uint64_t floor, const std::function<uint64_t(uint64_t, bool &)> &plan)
 {
-    if (first >= last) return SPNG_DONE;
-    {
-        // link rings of these streams (the slab may still be read by the greedy / lazy kernel of this call: wait before it moves)
-        const size_t ring_bytes = (last - first) * 65536 * 4;
-        if (ring_bytes > c->ring2_cap) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (c->d_ring2) HIP_TRY(hipFree(c->d_ring2));
-            c->d_ring2 = nullptr; c->ring2_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_ring2, ring_bytes));
-            c->ring2_cap = ring_bytes;
-        }
-    }
-    uint64_t need = 0, largest = 0;
-    for (size_t i = first; i < last; ++i) {
-        DeflateJob &f = sorted[i];
-        f.graph_vertices = (uint32_t)deflate_graph_vertices(f.src_len);
-        const uint64_t bytes = deflate_graph_bytes(f.graph_vertices);
-        need += bytes; largest = bytes > largest ? bytes : largest;
-    }
-    {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        uint64_t budget = c->cfg[SPNG_CFG_DEFLATE_BYTES] ? (uint64_t)c->cfg[SPNG_CFG_DEFLATE_BYTES] : (uint64_t)(free_b + c->graph_cap) / 2;
-        if (budget < largest) budget = largest;
-        uint64_t want = need < budget ? need : budget;
-        while (want > c->graph_cap) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (c->d_graph) HIP_TRY(hipFree(c->d_graph));
-            c->d_graph = nullptr; c->graph_cap = 0;
-            if (hipMalloc(&c->d_graph, want) == hipSuccess) { c->graph_cap = want; break; }
-            (void)hipGetLastError();
-            // no room for that many streams side by side: smaller groups
-            if (want <= largest) return fail_hip(hipErrorOutOfMemory, "deflate: no room for the match graph of one stream");
-            want = want / 2 > largest ? want / 2 : largest;
-        }
-    }
-    // Which full-search streams get helper waves: the ones whose input repeats itself (deflate_density_kernel).  The sparse
-    // ones go first, so every launch group is of one kind.
-    const size_t nfull = last - first;
-    std::vector<uint32_t> dense(nfull, 0);
-    {
-        memcpy(a.host<DeflateJob>(jslot), sorted.data(), sorted.size() * sizeof(DeflateJob));
-        if (int32_t st = c->upload(jslot, jslot + sorted.size() * sizeof(DeflateJob))) return st;
-        const size_t dslot = a.take(nfull * 4);
-        HIP_TRY(launch_deflate_density(a.dev<DeflateJob>(jslot) + first, (uint32_t)nfull, a.dev<uint32_t>(dslot), c->stream));
-        HIP_TRY(hipMemcpyAsync(dense.data(), a.dev<uint32_t>(dslot), nfull * 4, hipMemcpyDeviceToHost, c->stream));
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    uint64_t budget = c->cfg[SPNG_CFG_DEFLATE_BYTES] ? (uint64_t)c->cfg[SPNG_CFG_DEFLATE_BYTES] : (uint64_t)(free_b + c->graph_cap) / 2;
+    if (budget < floor) budget = floor;
+    for (;;) {
+        bool single = false;
+        const uint64_t slab = plan(budget, single);
+        if (slab <= c->graph_cap) return SPNG_DONE;
         HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<DeflateJob> part;
-        part.reserve(nfull);
-        for (int kind = 0; kind < 2; ++kind)
-            for (size_t i = 0; i < nfull; ++i) if ((int)dense[i] == kind) part.push_back(sorted[first + i]);
-        size_t ndense = 0;
-        for (uint32_t d : dense) ndense += d;
-        std::copy(part.begin(), part.end(), sorted.begin() + first);
-        for (size_t i = 0; i < nfull; ++i) dense[i] = i >= nfull - ndense;
+        if (c->d_graph) HIP_TRY(hipFree(c->d_graph));
+        c->d_graph = nullptr; c->graph_cap = 0;
+        if (hipMalloc(&c->d_graph, slab) == hipSuccess) { c->graph_cap = slab; return SPNG_DONE; }
+        (void)hipGetLastError();
+        if (single) return fail_text("deflate: no device memory for the search scratch of a single stream");
+        budget /= 2;
     }
-    // groups of full-search streams of one kind that fit the slab together
-    struct Group { size_t first, last; bool helpers; };
-    std::vector<Group> groups;
-    for (size_t i = first; i < last;) {
-        uint64_t used = 0;
-        size_t k = i;
-        const bool kind = dense[i - first] != 0;
-        while (k < last && (dense[k - first] != 0) == kind) {
-            const uint64_t bytes = deflate_graph_bytes(sorted[k].graph_vertices);
-            if (used + bytes > c->graph_cap && k > i) break;
-            sorted[k].graph = (uint32_t *)((char *)c->d_graph + used);
-            sorted[k].ring = (uint32_t *)c->d_ring2 + (k - first) * 65536;
-            used += bytes; ++k;
-        }
-        groups.push_back({i, k, kind});
-        i = k;
-    }
-    memcpy(a.host<DeflateJob>(jslot), sorted.data(), sorted.size() * sizeof(DeflateJob));
-    if (int32_t st = c->upload(jslot, jslot + sorted.size() * sizeof(DeflateJob))) return st;
-    for (auto &gr : groups)
-        HIP_TRY(launch_deflate_full(a.dev<DeflateJob>(jslot) + gr.first, (uint32_t)(gr.last - gr.first), gr.helpers, dr, c->stream));
-    return SPNG_DONE;
 }
 
-// The two-kernel full search (deflate.hip, "round 4") for sorted[first, last): per stream 11 bytes of scratch per vertex of a
-// round (<= 2^21 vertices), a pool of candidate words shared by all streams, rings for the search workgroups -- all from the
-// context's slab, which is capped at SPNG_CFG_DEFLATE_BYTES (default: half of the free memory); streams whose scratch does not fit
-// side by side go in groups.  Streams the pool could not serve come back unfinished and take the one-kernel search.
-static int32_t deflate_full_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted, size_t first, size_t last, spng_result *dr, Arena &a, size_t jslot)
+// One pass of the two-kernel full search (deflate.hip, "round 4") over jobs[0, n): per stream 11 bytes of scratch per vertex of
+// a round (<= 2^21 vertices), rings for the search workgroups and, per group of streams, two pools of candidate words (one per
+// round parity) -- all from the context's slab; streams whose scratch does not fit side by side go in groups.  The pools take
+// what the budget leaves (at least 64 MiB) or, `worst`, their group's worst case: a position leaves at most min(attempts, 30)
+// words and a pool starts empty at every search launch, so that no stream of the group can run dry.  The stream table and the
+// states are the arena's slots sslot / tslot.
+static int32_t deflate_full_pass(spng_ctx *c, const DeflateJob *jobs, size_t n, bool worst, spng_result *dr, Arena &a, size_t sslot, size_t tslot)
 {
-    if (first >= last) return SPNG_DONE;
-    const size_t nfull = last - first;
-    auto scratch_of = [](uint64_t n) -> uint64_t {
-        const uint64_t V = deflate2_vertices(n), B = V / 64 + 2;
+    auto scratch_of = [](uint64_t len) -> uint64_t {
+        const uint64_t V = deflate2_vertices(len), B = V / 64 + 2;
         // (the candidate records twice: round r + 1 is searched while round r is parsed)
         return 2 * (((2 * V + 255) & ~255ull) + ((8 * B + 255) & ~255ull) + ((4 * B + 255) & ~255ull)) + ((8 * B + 255) & ~255ull) +
                2 * ((4 * (V + 2) + 255) & ~255ull) + ((V + 2 + 255) & ~255ull) + ((B + 255) & ~255ull);
     };
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = c->cfg[SPNG_CFG_DEFLATE_BYTES] ? (uint64_t)c->cfg[SPNG_CFG_DEFLATE_BYTES] : (uint64_t)(free_b + c->graph_cap + c->ring_cap) / 2;
-    uint64_t largest = 0, all = 0, worst_pool = 0;
-    for (size_t i = first; i < last; ++i) {
-        const uint64_t sc = scratch_of(sorted[i].src_len);
-        largest = sc > largest ? sc : largest; all += sc;
-        // (a position leaves at most min(attempts, 30) words: 14 at level 8, 20 at level 9, 30 from level 10 on)
-        const uint64_t per = sorted[i].level <= 8 ? 14 : sorted[i].level == 9 ? 20 : 30;
-        worst_pool += (sorted[i].src_len < (1u << 21) ? sorted[i].src_len : (1u << 21)) * per * 4;
+    auto pool_of = [](const DeflateJob &j) -> uint64_t {      // (14 words per position at level 8, 20 at level 9, 30 from level 10 on)
+        const uint64_t per = j.level <= 8 ? 14 : j.level == 9 ? 20 : 30;
+        return (j.src_len < (1u << 21) ? j.src_len : (1u << 21)) * per * 4;
+    };
+    auto cps_of = [](uint64_t cnt) -> uint32_t {              // (a search workgroup is a CU: one round of them where the streams are few,
+        const uint64_t cps = (256 + cnt - 1) / cnt;           //  chunks of 2^20 positions -- 3 % of warm-up -- where they are many)
+        return cps < 2 ? 2u : cps > 64 ? 64u : (uint32_t)cps;
+    };
+    uint64_t largest = 0, worst_pool = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t sc = scratch_of(jobs[i].src_len);
+        largest = sc > largest ? sc : largest;
+        worst_pool += pool_of(jobs[i]);
     }
     const uint64_t min_pool = 64ull << 20;
-    if (budget < largest + min_pool + (64ull << 20)) budget = largest + min_pool + (64ull << 20);
-    // groups of streams whose scratch takes at most 2 / 3 of the budget; the rest is rings and pool
-    std::vector<std::pair<size_t, size_t>> groups;
-    for (size_t i = first; i < last;) {
-        uint64_t used = 0; size_t k = i;
-        while (k < last && (k == i || used + scratch_of(sorted[k].src_len) <= budget * 2 / 3)) used += scratch_of(sorted[k++].src_len);
-        groups.push_back({i, k});
-        i = k;
-    }
-    uint64_t slab = 0;
-    struct Lay { uint64_t scratch, rings, pool; uint32_t cps, chunk; };
+    struct Lay { size_t first, last; uint64_t scratch, rings, pool; uint32_t cps, chunk; };
     std::vector<Lay> lay;
-    for (auto &gr : groups) {
-        const uint32_t cnt = (uint32_t)(gr.second - gr.first);
-        Lay l;
-        l.scratch = 0;
-        for (size_t i = gr.first; i < gr.second; ++i) l.scratch += scratch_of(sorted[i].src_len);
-        uint32_t cps = (256 + cnt - 1) / cnt;                 // (a search workgroup is a CU: one round of them where the streams are few,
-        cps = cps < 2 ? 2 : cps > 64 ? 64 : cps;              //  chunks of 2^20 positions -- 3 % of warm-up -- where they are many)
-        l.cps = cps; l.chunk = (((1u << 21) / cps + 63) / 64) * 64;
-        l.rings = deflate2_temp_bytes(cnt * cps);             // (the searchers' word scratch; round 4: a 256 KiB link ring per workgroup)
-        uint64_t room = budget > l.scratch + l.rings ? budget - l.scratch - l.rings : 0;
-        l.pool = worst_pool < room / 2 ? worst_pool : room / 2;       // (one pool per round parity)
-        if (l.pool < min_pool) l.pool = min_pool;
-        l.pool &= ~255ull;
-        const uint64_t tot = l.scratch + l.rings + 2 * (l.pool + 256) + 4096;
-        slab = tot > slab ? tot : slab;
-        lay.push_back(l);
-    }
-    if (slab > c->graph_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_graph) HIP_TRY(hipFree(c->d_graph));
-        c->d_graph = nullptr; c->graph_cap = 0;
-        if (hipMalloc(&c->d_graph, slab) != hipSuccess) {
-            (void)hipGetLastError();
-            // (the one-kernel search knows neither `more` nor a state kept between pushes: a pushed stream it finished from byte 0
-            //  would leave its D2State stale and a non-final push with a trailer -- ADVICE r4.  Such a call fails instead; the
-            //  caller's states and destinations are untouched and the push can be repeated once memory is there)
-            for (size_t i = first; i < last; ++i)
-                if (sorted[i].state || sorted[i].more) {
-                    return fail_text("spng_deflate_resume_batch: no device memory for the search scratch of pushed streams");
-                }
-            return deflate_full_legacy(c, sorted, first, last, dr, a, jslot);   // (it sizes its groups by what it can get)
+    auto plan = [&](uint64_t budget, bool &single) -> uint64_t {
+        lay.clear(); single = true;
+        uint64_t slab = 0;
+        for (size_t i = 0; i < n;) {
+            // the group: streams whose scratch takes at most 2 / 3 of the budget (the rest is rings and pool) -- or, worst, whose
+            // scratch, rings and worst-case pools fit it
+            Lay l{i, i, 0, 0, 0, 0, 0};
+            uint64_t wp = 0;
+            while (l.last < n) {
+                const uint64_t sc = l.scratch + scratch_of(jobs[l.last].src_len), p = wp + pool_of(jobs[l.last]);
+                const uint64_t need = worst ? sc + deflate2_temp_bytes((uint32_t)(l.last + 1 - i) * cps_of(l.last + 1 - i)) + 2 * (p + 512) + 4096 : sc;
+                if (l.last > i && need > (worst ? budget : budget * 2 / 3)) break;
+                l.scratch = sc; wp = p; ++l.last;
+            }
+            const uint32_t cnt = (uint32_t)(l.last - i);
+            l.cps = cps_of(cnt);
+            l.chunk = (((1u << 21) / l.cps + 63) / 64) * 64;
+            l.rings = deflate2_temp_bytes(cnt * l.cps);           // (the searchers' word scratch; round 4: a 256 KiB link ring per workgroup)
+            if (worst) l.pool = (wp + 255) & ~255ull;
+            else {
+                const uint64_t room = budget > l.scratch + l.rings ? budget - l.scratch - l.rings : 0;
+                l.pool = worst_pool < room / 2 ? worst_pool : room / 2;
+                if (l.pool < min_pool) l.pool = min_pool;
+                l.pool &= ~255ull;
+            }
+            const uint64_t tot = l.scratch + l.rings + 2 * (l.pool + 256) + 4096;
+            slab = tot > slab ? tot : slab;
+            single = single && cnt == 1;
+            lay.push_back(l);
+            i = l.last;
         }
-        c->graph_cap = slab;
-    }
-    // the stream table and the device-side states: in the arena, uploaded once
-    const size_t sslot = a.take(nfull * sizeof(D2Stream)), tslot = a.take(nfull * sizeof(D2State)), fslot = a.take((nfull + 1) * 4);
+        return slab;
+    };
+    if (int32_t st = deflate_slab(c, worst ? 0 : largest + min_pool + (64ull << 20), plan)) return st;
     D2Stream *hs = a.host<D2Stream>(sslot);
     D2State *ht = a.host<D2State>(tslot);
-    memset(ht, 0, nfull * sizeof(D2State));                    // (a zeroed state = a stream's beginning: dfl2_begin_kernel)
-    std::vector<uint32_t> rounds_of(nfull, 1);
-    for (size_t g = 0; g < groups.size(); ++g) {
+    memset(ht, 0, n * sizeof(D2State));                        // (a zeroed state = a stream's beginning: dfl2_begin_kernel)
+    std::vector<uint32_t> rounds_of(n, 1);
+    for (const Lay &l : lay) {
         char *base = (char *)c->d_graph;
         uint64_t at = 0;
         auto take = [&](uint64_t bytes) { char *p = base + at; at += (bytes + 255) & ~255ull; return p; };
-        for (size_t i = groups[g].first; i < groups[g].second; ++i) {
-            const DeflateJob &j = sorted[i];
-            D2Stream &s = hs[i - first];
+        for (size_t i = l.first; i < l.last; ++i) {
+            const DeflateJob &j = jobs[i];
+            D2Stream &s = hs[i];
             const uint64_t V = deflate2_vertices(j.src_len), B = V / 64 + 2;
             s.src = j.src; s.dst = j.dst; s.src_len = j.src_len; s.dst_cap = j.dst_cap; s.format = j.format; s.level = j.level;
             s.image = j.image; s.exponent = j.exponent; s.more = j.more; s.pad = 0;
             // (spng_deflate_resume_batch: the caller's state, kept from push to push; else the call's own)
-            s.state = j.state ? (D2State *)j.state : a.dev<D2State>(tslot) + (i - first);
+            s.state = j.state ? (D2State *)j.state : a.dev<D2State>(tslot) + i;
             s.vinfo = (uint16_t *)take(2 * V); s.bbase = (uint64_t *)take(8 * B); s.bwords = (uint32_t *)take(4 * B); s.emask = (uint64_t *)take(8 * B);
             s.vinfo2 = (uint16_t *)take(2 * V); s.bbase2 = (uint64_t *)take(8 * B); s.bwords2 = (uint32_t *)take(4 * B);
             s.up = (uint32_t *)take(4 * (V + 2)); s.step = (uint32_t *)take(4 * (V + 2)); s.pathb = (uint8_t *)take(V + 2); s.litb = (uint8_t *)take(B);
             uint64_t pos = j.state ? j.plan_pos : 0;
             uint32_t lim = j.state && j.plan_limit ? j.plan_limit : 2048;
-            rounds_of[i - first] = deflate2_plan(j.src_len, j.more != 0, pos, lim);
+            rounds_of[i] = deflate2_plan(j.src_len, j.more != 0, pos, lim);
         }
     }
-    if (int32_t st = c->upload(sslot, tslot + nfull * sizeof(D2State))) return st;
-    uint32_t *d_failed = a.dev<uint32_t>(fslot);
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const uint32_t cnt = (uint32_t)(groups[g].second - groups[g].first);
-        const Lay &l = lay[g];
+    if (int32_t st = c->upload(sslot, tslot + n * sizeof(D2State))) return st;
+    for (const Lay &l : lay) {
+        const uint32_t cnt = (uint32_t)(l.last - l.first);
         char *rings = (char *)c->d_graph + ((l.scratch + 255) & ~255ull);
         char *pools[2] = {rings + l.rings, rings + l.rings + l.pool + 256};       // (each followed by its bump counter)
         uint32_t rounds = 0;
-        for (size_t i = groups[g].first; i < groups[g].second; ++i) rounds = rounds_of[i - first] > rounds ? rounds_of[i - first] : rounds;
-        const D2Stream *ds = a.dev<D2Stream>(sslot) + (groups[g].first - first);
+        for (size_t i = l.first; i < l.last; ++i) rounds = rounds_of[i] > rounds ? rounds_of[i] : rounds;
+        const D2Stream *ds = a.dev<D2Stream>(sslot) + l.first;
         HIP_TRY(launch_deflate2_begin(ds, cnt, c->stream));
         // The search of round r + 1 beside the parse of round r, on a stream of its own (candidates are a function of the input
         // alone; the parse is one wave per stream and leaves most of the chip idle): two sets of records and pools, by round parity.
@@ -1827,36 +1752,47 @@ static int32_t deflate_full_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted,
             HIP_TRY(hipEventRecord(c->ev_dfl[2 + par], c->stream));
         }
     }
-    // who is not finished?  (the pool ran dry under them: a batch of very compressible streams on little memory)
-    HIP_TRY(launch_deflate2_failed(a.dev<D2Stream>(sslot), (uint32_t)nfull, d_failed, c->stream));
-    std::vector<uint32_t> failed(nfull + 1, 0);
-    HIP_TRY(hipMemcpyAsync(failed.data(), d_failed, (nfull + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPNG_DONE;
+}
+
+// The full search for sorted[first, last).  Streams the pool could not serve (a batch of very compressible streams on little
+// memory) come back unfinished and go through the rounds once more, with pools of their worst case.
+static int32_t deflate_full_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted, size_t first, size_t last, spng_result *dr, Arena &a)
+{
+    if (first >= last) return SPNG_DONE;
+    const size_t nfull = last - first;
+    // the stream table, the device-side states, who is not finished: in the arena, once (the second pass takes the same slots)
+    const size_t sslot = a.take(nfull * sizeof(D2Stream)), tslot = a.take(nfull * sizeof(D2State)), fslot = a.take((nfull + 1) * 4);
+    std::vector<uint32_t> failed;
+    auto unfinished = [&](size_t n) -> int32_t {
+        HIP_TRY(launch_deflate2_failed(a.dev<D2Stream>(sslot), (uint32_t)n, a.dev<uint32_t>(fslot), c->stream));
+        failed.assign(n + 1, 0);
+        HIP_TRY(hipMemcpyAsync(failed.data(), a.dev<uint32_t>(fslot), (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SPNG_DONE;
+    };
+    if (int32_t st = deflate_full_pass(c, sorted.data() + first, nfull, false, dr, a, sslot, tslot)) return st;
+    if (int32_t st = unfinished(nfull)) return st;
     for (size_t i = 0; i < nfull; ++i) if (failed[1 + i] == 1 && sorted[first + i].more) { failed[1 + i] = 0; failed[0] -= 1; }   // (a push that is not the last is never "finished")
     for (size_t i = 0; i < nfull; ++i)
         if (failed[1 + i] && sorted[first + i].state) {
             snprintf(g_err, sizeof g_err, "spng_deflate_resume_batch: the candidate pool ran dry under stream %u (raise SPNG_CFG_DEFLATE_BYTES)", sorted[first + i].image);
             return SPNG_E_DEVICE;
         }
-    if (failed[0]) {
-        std::vector<DeflateJob> again;
-        for (size_t i = 0; i < nfull; ++i) if (failed[1 + i]) again.push_back(sorted[first + i]);
-        std::vector<DeflateJob> rest;
-        for (size_t i = 0; i < nfull; ++i) if (!failed[1 + i]) rest.push_back(sorted[first + i]);
-        std::copy(again.begin(), again.end(), sorted.begin() + first);
-        std::copy(rest.begin(), rest.end(), sorted.begin() + first + again.size());
-        return deflate_full_legacy(c, sorted, first, first + again.size(), dr, a, jslot);
-    }
+    if (!failed[0]) return SPNG_DONE;
+    std::vector<DeflateJob> again;
+    for (size_t i = 0; i < nfull; ++i) if (failed[1 + i]) again.push_back(sorted[first + i]);
+    if (int32_t st = deflate_full_pass(c, again.data(), again.size(), true, dr, a, sslot, tslot)) return st;
+    if (int32_t st = unfinished(again.size())) return st;
+    if (failed[0]) return fail_text("deflate: a stream is unfinished after a pass with pools of its worst case");
     return SPNG_DONE;
 }
 
 // Levels 0-7 in rounds (deflate.hip, "round 5"): the chip-wide search leaves one word per position, a parse wave per stream walks
 // them.  Per stream two sets of 4 bytes per position of a round (<= 2^21 positions; the search of round r + 1 beside the parse of
-// round r) from the context's slab, streams that do not fit side by side in groups.  No room at all: the one-kernel form for
-// streams that keep no state, an error for pushed ones.
-static int32_t deflate_fast_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted, size_t first, size_t last, spng_result *dr, Arena &a, size_t jslot, bool &fell_back)
+// round r) from the context's slab, streams that do not fit side by side in groups.
+static int32_t deflate_fast_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted, size_t first, size_t last, spng_result *dr, Arena &a)
 {
-    fell_back = false;
     if (first >= last) return SPNG_DONE;
     const size_t nfast = last - first;
     const uint64_t RV = deflate3_round_positions();
@@ -1885,40 +1821,29 @@ static int32_t deflate_fast_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted,
         }
         return b;
     };
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = c->cfg[SPNG_CFG_DEFLATE_BYTES] ? (uint64_t)c->cfg[SPNG_CFG_DEFLATE_BYTES] : (uint64_t)(free_b + c->graph_cap + c->ring_cap) / 2;
     struct Group { size_t first, last; bool blocks; };
     std::vector<Group> groups;
-    uint64_t slab = 0;
-    for (size_t i = first; i < last;) {
-        const bool blocks = i < mid;
-        const size_t stop = blocks ? mid : last;
-        uint64_t used = 0;
-        size_t k = i;
-        while (k < stop) {
-            const uint64_t sc = scratch_of(sorted[k], blocks);
-            if (used + sc > budget && k > i) break;
-            used += sc; ++k;
+    auto plan = [&](uint64_t budget, bool &single) -> uint64_t {
+        groups.clear(); single = true;
+        uint64_t slab = 0;
+        for (size_t i = first; i < last;) {
+            const bool blocks = i < mid;
+            const size_t stop = blocks ? mid : last;
+            uint64_t used = 0;
+            size_t k = i;
+            while (k < stop) {
+                const uint64_t sc = scratch_of(sorted[k], blocks);
+                if (used + sc > budget && k > i) break;
+                used += sc; ++k;
+            }
+            slab = used > slab ? used : slab;
+            single = single && k == i + 1;
+            groups.push_back({i, k, blocks});
+            i = k;
         }
-        slab = used > slab ? used : slab;
-        groups.push_back({i, k, blocks});
-        i = k;
-    }
-    slab += 4096;
-    if (slab > c->graph_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_graph) HIP_TRY(hipFree(c->d_graph));
-        c->d_graph = nullptr; c->graph_cap = 0;
-        if (hipMalloc(&c->d_graph, slab) != hipSuccess) {
-            (void)hipGetLastError();
-            for (size_t i = first; i < last; ++i)
-                if (sorted[i].state || sorted[i].more) return fail_text("spng_deflate_resume_batch: no device memory for the search records of pushed streams");
-            fell_back = true;                                  // (the caller runs the one-kernel form)
-            return SPNG_DONE;
-        }
-        c->graph_cap = slab;
-    }
+        return slab + 4096;
+    };
+    if (int32_t st = deflate_slab(c, 0, plan)) return st;
     const size_t sslot = a.take(nfast * sizeof(D3Stream)), tslot = a.take(nfast * sizeof(D1State));
     D3Stream *hs = a.host<D3Stream>(sslot);
     // (a zeroed state = a stream's beginning: dfl3_begin_kernel)
@@ -1984,7 +1909,7 @@ static int32_t deflate_fast_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted,
     return SPNG_DONE;
 }
 
-// shared by spng_deflate_batch / spng_encode_batch.  Per-stream link rings of the greedy / lazy kernel live in a context-owned slab.
+// shared by spng_deflate_batch / spng_encode_batch
 static int32_t deflate_launch(spng_ctx *c, std::vector<DeflateJob> &jobs, spng_result *dr, Arena &a, size_t jslot,
                               size_t gzparts = (size_t)-1)
 {
@@ -1994,31 +1919,15 @@ static int32_t deflate_launch(spng_ctx *c, std::vector<DeflateJob> &jobs, spng_r
     for (auto &j : jobs) if (j.level < 8) sorted.push_back(j);
     const size_t nfast = sorted.size();
     for (auto &j : jobs) if (j.level >= 8) sorted.push_back(j);
-    bool legacy = c->cfg[SPNG_CFG_DEFLATE_MODE] == SPNG_DEFLATE_ONE_KERNEL;
-    for (auto &j : jobs) if (j.state) legacy = false;          // (streams that arrive in pieces: only the two-kernel search keeps a state)
-    // levels 0-7: the search chip-wide and a parse wave per stream, round by round -- unless the one-kernel form is asked for
-    bool fast_one_kernel = legacy && nfast;
-    if (nfast && !fast_one_kernel) {
+    if (nfast) {
         Timed t(c, SPNG_K_DEFLATE);
-        if (int32_t st = deflate_fast_rounds(c, sorted, 0, nfast, dr, a, jslot, fast_one_kernel)) return st;
+        if (int32_t st = deflate_fast_rounds(c, sorted, 0, nfast, dr, a)) return st;
     }
-    const size_t nring = fast_one_kernel ? nfast : 0;
-    const size_t ring_bytes = nring * 65536 * 4;
-    if (ring_bytes > c->ring_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_ring) HIP_TRY(hipFree(c->d_ring));
-        c->d_ring = nullptr; c->ring_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_ring, ring_bytes));
-        c->ring_cap = ring_bytes;
-    }
-    for (size_t i = 0; i < nring; ++i) sorted[i].ring = (uint32_t *)c->d_ring + i * 65536;
     memcpy(a.host<DeflateJob>(jslot), sorted.data(), sorted.size() * sizeof(DeflateJob));
     if (int32_t st = c->upload(jslot, jslot + sorted.size() * sizeof(DeflateJob))) return st;
     {
         Timed t(c, SPNG_K_DEFLATE);
-        if (fast_one_kernel) HIP_TRY(launch_deflate(a.dev<DeflateJob>(jslot), (uint32_t)nfast, dr, c->stream));
-        if (legacy) { if (int32_t st = deflate_full_legacy(c, sorted, nfast, sorted.size(), dr, a, jslot)) return st; }
-        else if (int32_t st = deflate_full_rounds(c, sorted, nfast, sorted.size(), dr, a, jslot)) return st;
+        if (int32_t st = deflate_full_rounds(c, sorted, nfast, sorted.size(), dr, a)) return st;
     }
     // gzip members: CRC-32 and byte count of the input behind the stream (DeflatorBuffers.swift:96-135)
     if (gzparts != (size_t)-1)
@@ -2042,8 +1951,8 @@ int32_t spng_deflate_batch(spng_ctx *c, const spng_stream_desc *descs, const int
             descs[i].format > SPNG_FORMAT_GZIP) return SPNG_E_ARGUMENT;
         gzip = gzip || descs[i].format == SPNG_FORMAT_GZIP;
         jobs[i] = DeflateJob{(const uint8_t *)descs[i].d_src, (uint8_t *)descs[i].d_dst, descs[i].src_len,
-                             descs[i].dst_cap, nullptr, descs[i].format, levels[i], i,
-                             descs[i].format == SPNG_FORMAT_IOS ? 15u : (uint32_t)e, nullptr, 0, 0};
+                             descs[i].dst_cap, descs[i].format, levels[i], i,
+                             descs[i].format == SPNG_FORMAT_IOS ? 15u : (uint32_t)e, 0};
     }
     if (int32_t st = c->reserve(count * (sizeof(DeflateJob) + sizeof(spng_result) + sizeof(D2Stream) + sizeof(D2State) + sizeof(D3Stream) + sizeof(D1State) + 1024 + (gzip ? 4 * (size_t)gzip_pieces() : 0)) + 8192)) return st;
     Arena a{c};
@@ -2178,9 +2087,9 @@ int32_t spng_trim(spng_ctx *c)
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
     if (c->stream_out) HIP_TRY(hipStreamSynchronize(c->stream_out));
-    void **bufs[] = {&c->d_ring, &c->d_ring2, &c->d_graph, &c->d_log, &c->d_tok, &c->d_sym, &c->d_win, &c->d_multi};
-    size_t *caps[] = {&c->ring_cap, &c->ring2_cap, &c->graph_cap, &c->log_cap, &c->tok_cap, &c->sym_cap, &c->win_cap, &c->multi_cap};
-    for (int i = 0; i < 8; ++i) {
+    void **bufs[] = {&c->d_graph, &c->d_log, &c->d_tok, &c->d_sym, &c->d_win, &c->d_multi};
+    size_t *caps[] = {&c->graph_cap, &c->log_cap, &c->tok_cap, &c->sym_cap, &c->win_cap, &c->multi_cap};
+    for (int i = 0; i < 6; ++i) {
         if (*bufs[i]) HIP_TRY(hipFree(*bufs[i]));
         *bufs[i] = nullptr; *caps[i] = 0;
     }

@@ -191,12 +191,9 @@ struct DeflateJob {
     uint8_t       *dst;
     uint64_t       src_len;
     uint64_t       dst_cap;
-    uint32_t      *ring;          // 65536-entry link ring (scratch, HBM)
     int32_t        format, level;
     uint32_t       image;
     uint32_t       exponent;      // window = 2^exponent (LZ77.Deflator(exponent:); PNG: 15)
-    uint32_t      *graph;         // levels >= 8: match-graph scratch (deflate_graph_bytes)
-    uint32_t       graph_vertices;
     uint32_t       more;          // spng_deflate_resume_batch: more input will follow (src_len is what arrived so far)
     struct D1State *state;        // ... and where the stream keeps itself between pushes (levels 0-7: a D1State, 8 and up: a D2State; null: one-shot)
     uint64_t       plan_pos;      // (host side: where the previous push left the parse; levels >= 8: its block limit, 0-7: how far
@@ -204,10 +201,10 @@ struct DeflateJob {
     uint64_t       plan_aux;
 };
 
-// Greedy / lazy kernel between two pushes (spng_deflate_resume_batch, levels 0-7): the parse position, the terms queued for the
+// A stream of levels 0-7 between two pushes (spng_deflate_resume_batch): the parse position, the terms queued for the
 // block being filled, the bit writer, the Adler sums.  The hash window is not kept: the next push enters the last 32 KiB again.
 struct D1State {
-    uint64_t w, inserted;         // first unparsed position; (one-kernel form) positions below `inserted` are in the Adler sums
+    uint64_t w, inserted;         // first unparsed position; (not read any more: a free word)
     uint64_t acc, total;          // the bit writer: pending bits, bytes produced
     uint32_t nacc, overflow, count, started;
     uint32_t adlerS, adlerI, pad[2];
@@ -290,7 +287,6 @@ hipError_t launch_pinf2_parts(PStream *d_streams, uint32_t nstreams, PSeg *d_seg
 hipError_t launch_pinf2_join(PStream *d_streams, uint32_t nstreams, spng_result *d_results, int32_t *d_done, PPart *d_parts, uint32_t pmax,
                              uint16_t *d_sym, uint8_t *d_win, hipStream_t stream);
 hipError_t launch_pinf2_account(uint32_t *d_ctr, uint32_t *d_totals, uint32_t pages, hipStream_t stream);
-hipError_t launch_deflate(const DeflateJob *d_jobs, uint32_t count, spng_result *d_results, hipStream_t stream);
 // gzip.hip
 static constexpr uint64_t GZ_NONE = ~0ull;
 uint32_t   gzip_pieces();
@@ -301,8 +297,6 @@ hipError_t launch_gzip_inflate_post(const InflateJob *d_jobs, spng_result *d_res
 hipError_t launch_gzip_deflate_post(const DeflateJob *d_jobs, spng_result *d_results, uint32_t *d_parts, uint32_t count,
                                     hipStream_t stream);
 hipError_t launch_resume_post(const InflateJob *d_jobs, spng_result *d_results, uint64_t *d_parts, uint32_t count, hipStream_t stream);
-hipError_t launch_deflate_full(const DeflateJob *d_jobs, uint32_t count, bool helpers, spng_result *d_results, hipStream_t stream);
-hipError_t launch_deflate_density(const DeflateJob *d_jobs, uint32_t count, uint32_t *d_dense, hipStream_t stream);
 uint32_t deflate2_rounds(uint64_t n);
 uint64_t deflate_state_bytes();
 uint32_t deflate2_plan(uint64_t n, bool more, uint64_t &pos, uint32_t &lim);
@@ -325,8 +319,6 @@ uint64_t deflate4_block_bytes();
 hipError_t launch_deflate4_round(const D3Stream *d_streams, uint32_t count, uint32_t max_blocks, spng_result *d_results, uint32_t parity, hipStream_t stream);
 hipError_t launch_deflate2_parse(const D2Stream *d_streams, uint32_t count, const uint32_t *d_pool, spng_result *d_results, uint32_t parity, hipStream_t stream);
 hipError_t launch_deflate2_failed(const D2Stream *d_streams, uint32_t count, uint32_t *d_failed, hipStream_t stream);
-uint64_t deflate_graph_vertices(uint64_t n);
-uint64_t deflate_graph_bytes(uint64_t vertices);
 hipError_t launch_unpack(const UnpackJob *d_jobs, uint32_t count, uint32_t blocks_x, int target, hipStream_t stream);
 hipError_t launch_pack(const PackJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
 size_t lex_chunk_bytes();

@@ -1,6 +1,5 @@
 // deflate.hip -- batched DEFLATE / zlib compression for gfx950, bit-exact with swift-png's
-// LZ77.Deflator at every level: greedy (0-3), lazy (4-7) and the shortest-path search (8 and up);
-// one wavefront per stream (plus three helper waves in the forward pass of the search on compressible input).
+// LZ77.Deflator at every level: greedy (0-3), lazy (4-7) and the shortest-path search (8 and up).
 //
 // Replaces (whole-stream form, i.e. LZ77.Deflator.push(all, last: true)):
 //   level table        Sources/LZ77/Deflator/LZ77.DeflatorSearch.swift:13-35
@@ -16,37 +15,26 @@
 // entered into the window, and the candidates of position p are the earlier positions with the
 // same 4-byte key, most recent first (first one at distance <= 32767, later ones < 32767), tried
 // until `attempts` run out or a run >= `goal` is seen; the first strictly longest run > 5 wins.
-// Only the parse (which positions are asked) is sequential.  So a stream's wave works in layers:
-//   * hash insertion, 64 positions per step: every lane hashes its key; its link is the distance to
-//     the nearest lower lane with the same bucket (radix match over the hash bits, one ballot per bit),
-//     else to the bucket head in LDS; links (+ a 16-bit key tag) go to a 64 K-entry ring in HBM.
-//     Insertion runs ahead of the parse -- later positions never appear in an earlier position's
-//     chain, which only walks backwards;
-//   * match search, 128 positions per step, two per lane (chain_walk2): both chains hop together and the
-//     candidate's first four bytes are fetched speculatively with the link, so the latency of a hop is
-//     paid once per pair;
-//   * the parse itself walks those answers on the scalar unit (readlane per token) with the
-//     reference's greedy / lazy rules, packing terms exactly like LZ77.DeflatorTerm.
-// When 2047 terms are queued (lazy: 2046/2047) the block is written: histogram with LDS atomics,
-// the reference's heap-based length-limited Huffman construction (ranked in parallel, merged on
-// one lane because its tie-breaking is order dependent; depths by pointer jumping), canonical codes
-// by ballot, code-length RLE, and the bits of 64 terms at a time (prefix sum of their lengths, ds_or
-// into a zero-initialised staging ring).  Levels >= 8: see the second half of this file.
+// Only the parse (which positions are asked) is sequential.  So a batch goes through in rounds of
+// up to 2^21 positions per stream, two kinds of kernel per round: a chip-wide search (the window in
+// LDS, a workgroup per chunk of a stream's round) that leaves its answers in global memory, and a
+// parse per stream that walks them with the reference's rules -- greedy / lazy (dfl3_parse_kernel,
+// the dfl4_* kernels) or the shortest path (dfl2_parse_kernel) -- and writes the blocks: histogram
+// with LDS atomics, the reference's heap-based length-limited Huffman construction (ranked in
+// parallel, merged on one lane because its tie-breaking is order dependent; depths by pointer
+// jumping), canonical codes by ballot, code-length RLE, and the bits of 64 terms at a time (prefix
+// sum of their lengths, ds_or into a zero-initialised staging ring).
 #include "common.hpp"
 #include "huffman.hpp"      // UNI / uni64, WSYNC, DPP scans
 
 namespace spng {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed)) U32u { uint32_t v; };
-struct __attribute__((packed)) U128u { u32x4 v; };
-// Input, output and the link ring are global memory, and say so in their types (a generic pointer
+// Input, output and the search's records are global memory, and say so in their types (a generic pointer
 // costs flat instructions, which also tie up the LDS counter).
 typedef uint32_t __attribute__((address_space(1))) gword;
 typedef U32u __attribute__((address_space(1))) gU32u;
 
-static constexpr int HBITS = 13;                 // bucket heads in LDS
-static constexpr uint32_t NONE = 0xffffffffu;
 static constexpr int OUTB = 2048;                // output staging ring (bytes, power of two; at most half of it + the ~600 bytes of a block's tables stand undrained)
 
 // LZ77.Composites.swift:25-110 in closed form (table loads from HBM would sit on the serial path):
@@ -73,7 +61,7 @@ __device__ __forceinline__ uint32_t dist_decade(uint32_t d)
 
 struct DLdsFull {                                // the full search (levels >= 8) only
     // forward pass: the best way into each of the next vertices found so far, as one 64-bit key (depth << 32 | writer order:
-    // see full_forward)
+    // see d2_forward)
     uint64_t win[512];
     uint8_t  depths[544];                        // LZ77.DeflatorMatches.Depths: cost of every symbol in quarter bits
 };
@@ -90,30 +78,16 @@ struct DLds {                                    // what every kernel of this fi
     uint8_t  msym[320], mbits[320];              // code-length RLE terms
     uint8_t  cl[20];                             // code-length-code lengths in transmission order
 };
-struct DLdsSearch {                              // the match search of the one-kernel forms (greedy / lazy, full)
-    uint32_t head[(1 << HBITS) + 1];             // most recent position per bucket (low 32 bits); + a slot nobody reads
-    uint32_t cslot[2][30 * 64];                  // full: per lane and half, the best run of every distance decade (distance << 16 | run)
-};
 struct DLdsTerms {                               // greedy / lazy: the queued terms (of their own: dfl3_parse_kernel has no search in it)
     uint32_t terms[2][2048];                     // two blocks' worth: dfl3_parse_kernel's parser fills one while its writer emits the other
     uint32_t cmd[2];                             // parser -> writer, per buffer: 0 free, else D3_CMD_* | terms
     uint64_t fin_w;                              // the parse position a SAVE / NEED_MORE command carries
 };
-struct DLdsOld {                                 // the one-kernel full search (deflate_full_kernel)
-    uint32_t batch[64 * 30];                     // the edge slots of the 64 vertices at hand
-    // the full kernel's helper waves (forward pass): what wave 0 hands them per pass and per batch of 64 vertices
-    // (per-batch words twice: a helper may still be reading one batch's while wave 0 sets up the next)
-    uint64_t fw_bbase, fw_ems[2][16];            // which vertices of the next sixteen batches have edges
-    uint32_t fw_cmd, fw_count, fw_carry[2];
-    uint32_t fw_cin[2][64];
-};
 // One instance per workgroup, at namespace scope so that the (non-inlined) block writer reaches it
 // with LDS instructions instead of through a generic pointer.
 __shared__ __attribute__((aligned(16))) DLds g_lds;
 __shared__ __attribute__((aligned(16))) DLdsFull g_full;
-__shared__ __attribute__((aligned(16))) DLdsSearch g_sea;
 __shared__ __attribute__((aligned(16))) DLdsTerms g_trm;
-__shared__ __attribute__((aligned(16))) DLdsOld g_old;
 
 struct Bits {                                    // LSB-first bit writer (LZ77.DeflatorOut.append)
     uint64_t acc; uint32_t nacc;
@@ -524,326 +498,6 @@ __device__ __attribute__((noinline)) Bits write_block_global(Bits b_, int count_
 
 __device__ __forceinline__ uint32_t load32(const gbyte *p) { return ((const gU32u *)p)->v; }
 
-// bytes of position q.. and p.. agree for how many bytes (<= limit)?  Eight at a time from the input.
-struct __attribute__((packed)) U64u { uint64_t v; };
-typedef U64u __attribute__((address_space(1))) gU64u;
-__device__ __forceinline__ uint64_t load64(const gbyte *p) { return ((const gU64u *)p)->v; }
-__device__ __forceinline__ uint32_t common_prefix(const gbyte *in, uint64_t q, uint64_t p, uint32_t limit)
-{
-    uint32_t i = 0;
-    while (i + 8 <= limit) {
-        const uint64_t x = load64(in + q + i) ^ load64(in + p + i);
-        if (x) return i + ((uint32_t)__builtin_ctzll(x) >> 3);
-        i += 8;
-    }
-    if (i + 4 <= limit) {
-        const uint32_t x = load32(in + q + i) ^ load32(in + p + i);
-        if (x) return i + (__builtin_ctz(x) >> 3);
-        i += 4;
-    }
-    while (i < limit && in[q + i] == in[p + i]) ++i;
-    return i;
-}
-
-// LZ77.DeflatorWindow.match (:132-212) for TWO positions per lane at once (pA, pB: the lane's position in
-// each half of a 128-position batch): both chains hop together, so the latency of a hop -- the link and,
-// speculatively, the candidate's first four bytes -- is paid once for the pair.  hit(which, distance, run)
-// sees every candidate whose tag and key match, in chain order, and the reference's stop rules apply per
-// chain: `attempts` candidates, a run >= `goal`, the window 2^exponent.
-template <class F>
-__device__ __forceinline__ void chain_walk2(const gbyte *in, const gword *ring, uint64_t n, uint64_t pA, uint64_t pB,
-                                            bool liveA, bool liveB, uint32_t keyA, uint32_t keyB, uint32_t wmask,
-                                            int attempts, int goal, F &&hit)
-{
-    uint32_t tagA = 0, tagB = 0, dA = 0, dB = 0, accA = 0, accB = 0;
-    int remA = attempts, remB = attempts;
-    bool firstA = true, firstB = true;
-    if (liveA) { const uint32_t m = ring[pA & 65535]; tagA = m >> 16; dA = m & 0xffff; }
-    if (liveB) { const uint32_t m = ring[pB & 65535]; tagB = m >> 16; dB = m & 0xffff; }
-    const uint32_t limA = n - pA < 258 ? (uint32_t)(n - pA) : 258u, limB = n - pB < 258 ? (uint32_t)(n - pB) : 258u;
-    while (dA | dB) {
-        bool goA = dA != 0, goB = dB != 0;
-        if (goA) { accA += dA; if (accA > wmask || (!firstA && accA >= wmask)) goA = false; }
-        if (goB) { accB += dB; if (accB > wmask || (!firstB && accB >= wmask)) goB = false; }
-        uint32_t eA = 0, eB = 0, kA = 0, kB = 0;
-        if (goA) { eA = ring[(pA - accA) & 65535]; kA = load32(in + pA - accA); }
-        if (goB) { eB = ring[(pB - accB) & 65535]; kB = load32(in + pB - accB); }
-        if (goA && (eA >> 16) == tagA && kA == keyA) {
-            const uint32_t run = common_prefix(in, pA - accA, pA, limA);
-            hit(0, accA, run);
-            firstA = false; remA -= 1;
-            if (!(remA > 0 && goal > (int)run)) goA = false;
-        }
-        if (goB && (eB >> 16) == tagB && kB == keyB) {
-            const uint32_t run = common_prefix(in, pB - accB, pB, limB);
-            hit(1, accB, run);
-            firstB = false; remB -= 1;
-            if (!(remB > 0 && goal > (int)run)) goB = false;
-        }
-        dA = goA ? eA & 0xffff : 0u;
-        dB = goB ? eB & 0xffff : 0u;
-    }
-}
-
-// the 4-byte key of position p (zero-extended at the end of the input)
-__device__ __forceinline__ uint32_t load_key(const gbyte *in, uint64_t n, uint64_t p)
-{
-    if (p + 4 <= n) return load32(in + p);
-    uint32_t key = 0;
-    for (int k = 0; k < 4; ++k) if (p + k < n) key |= (uint32_t)in[p + k] << (8 * k);
-    return key;
-}
-
-// Hash insertion of the 64 positions inserted .. inserted + 63 (LZ77.DeflatorWindow.update, :78-128): every
-// lane hashes its 4-byte key; a position's link is the distance to the previous position of its bucket --
-// the nearest lower lane with the same bucket (radix match over the hash bits: one ballot per bit), else
-// the bucket head -- and the last lane of every bucket becomes the new head.  Adler-32 sums ride along.
-__device__ __forceinline__ void insert_batch(uint32_t *head, const gbyte *in, uint64_t n, gword *ring, uint64_t inserted, uint32_t key,
-                                             uint32_t &accS, uint32_t &accI, int lane, bool sum = true)
-{
-    const uint64_t p = inserted + lane;
-    const bool live = p + 4 <= n;                              // the last three positions never start a match
-    if (p < n && sum) {                                        // Adler-32 accumulators
-        const uint32_t byte = key & 0xff;
-        accS += byte;
-        accI = (accI + (uint32_t)(p % 65521) * byte) % 65521;
-    }
-    const uint32_t mix = key * 0x9E3779B1u;
-    const uint32_t h = mix >> (32 - HBITS);
-    const uint32_t tag = (mix >> 3) & 0xffffu;
-    unsigned long long same = __ballot(live);
-#pragma unroll
-    for (int k = 0; k < HBITS; ++k) {
-        const unsigned long long bk = __ballot((h >> k) & 1);
-        same &= (h >> k) & 1 ? bk : ~bk;
-    }
-    const unsigned long long lower = (1ull << lane) - 1;
-    const unsigned long long below = same & lower, above = same & ~lower & ~(1ull << lane);
-    uint32_t prev = live ? head[h] : NONE;
-    if (below) prev = (uint32_t)(inserted + (63 - __clzll((long long)below)));
-    uint32_t dist = 0;
-    if (live && prev != NONE) {
-        const uint64_t d = (uint32_t)((uint32_t)p - prev);
-        dist = d <= 32767 ? (uint32_t)d : 0;
-    }
-    if (p < n) ring[p & 65535] = dist | tag << 16;
-    head[live && !above ? h : 1u << HBITS] = (uint32_t)p;      // (idle lanes: the spare slot)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-}
-
-#ifdef SPNG_DEFLATE_PROF
-// full kernel: cycles per phase, kept in LDS so that the non-inlined passes can add to them
-__shared__ uint64_t g_prof[12];
-#define FPROF(k) do { const uint64_t now_ = __builtin_readcyclecounter(); if (threadIdx.x == 0) { g_prof[k] += now_ - g_prof[11]; g_prof[11] = now_; } } while (0)
-#define DPROF_DECL uint64_t pt[6] = {0,0,0,0,0,0}, p_t0 = 0;
-#define DPROF_BEGIN() p_t0 = __builtin_readcyclecounter()
-#define DPROF_END(k) pt[k] += __builtin_readcyclecounter() - p_t0
-#else
-#define FPROF(k)
-#define DPROF_DECL
-#define DPROF_BEGIN()
-#define DPROF_END(k)
-#endif
-
-__global__ __launch_bounds__(64) void deflate_kernel(const DeflateJob *__restrict__ jobs,
-                                                     spng_result *__restrict__ results)
-{
-    DLds &s = g_lds;
-    const DeflateJob *jp = jobs + blockIdx.x;
-    const int lane = threadIdx.x;
-    // job fields are wave-uniform: pinned to scalar registers, typed as global memory
-    const gbyte *in = (const gbyte *)uni64((uint64_t)jp->src);
-    const uint64_t n = uni64(jp->src_len);
-    gword *ring = (gword *)uni64((uint64_t)jp->ring);          // 65536 links: distance | tag << 16
-    struct { gbyte *dst; uint64_t dst_cap; int32_t format, level; uint32_t image; } job = {
-        (gbyte *)uni64((uint64_t)jp->dst), uni64(jp->dst_cap), (int32_t)UNI(jp->format), (int32_t)UNI(jp->level), UNI(jp->image) };
-
-    // DeflatorSearch.init(level:) (:13-35), greedy and lazy rows
-    const int level = job.level < 0 ? 0 : job.level;
-    const bool lazy = level >= 4;
-    // (packed constants: run-time indexed local arrays would live in scratch memory)
-    const int lv = level & 7;
-    const int attempts = lv == 0 ? 1 : lv == 1 ? 2 : lv == 2 ? 4 : lv == 3 ? 40 : lv == 4 ? 20 : lv == 5 ? 40 : lv == 6 ? 64 : 100;
-    const int goal = lv == 0 ? 6 : lv == 1 ? 8 : lv == 2 ? 10 : lv == 3 ? 24 : lv == 4 ? 32 : lv == 5 ? 54 : lv == 6 ? 80 : 160;
-
-    for (int i = lane; i < OUTB / 4; i += 64) s.out32[i] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    Bits b = {0, 0, 0, 0, job.dst, job.dst_cap, false};
-    const uint32_t wmask = (1u << UNI(jp->exponent)) - 1;    // window 2^exponent (LZ77.Deflator(exponent:); PNG: 15)
-    // spng_deflate_resume_batch: the stream arrives in pieces.  `more`: src_len is what has arrived so far; st1: where the
-    // previous push left off (parse position, queued terms, bit writer, Adler sums)
-    const bool more = UNI(jp->more) != 0;
-    D1State *st1 = (D1State *)uni64((uint64_t)jp->state);
-    const bool resumed = st1 && UNI(st1->started);
-    if (resumed) { b.acc = uni64(st1->acc); b.nacc = UNI(st1->nacc); b.total = b.flushed = uni64(st1->total); b.overflow = UNI(st1->overflow) != 0; }
-    if (n < 3 && more) {
-        // (nothing can be decided yet: not even whether this will be a stored tail)
-        if (lane == 0) {
-            spng_result &res = results[job.image];
-            res.status = SPNG_NEED_MORE_INPUT; res.reserved = 0; res.written = b.total; res.consumed = resumed ? uni64(st1->w) : 0;
-            res.aux[0] = res.consumed; res.aux[1] = 0;
-        }
-        return;
-    }
-    if (resumed) {}
-    else if (job.format == SPNG_FORMAT_ZLIB) {
-        // StreamHeader.write (StreamHeader.swift:56-62)
-        const uint32_t unpaired = (UNI(jp->exponent) - 8) << 4 | 0x08;
-        const uint32_t check = ~(((unpaired << 8 | unpaired >> 8) & 0xffff) % 31) & 31;
-        put(s, b, check << 8 | unpaired, 16, lane);
-    } else if (job.format == SPNG_FORMAT_GZIP) {
-        // Gzip.StreamHeader.write (Gzip.StreamHeader.swift:84-96): sigil, method 8, no flags, MTIME 0, XFL 0, OS 255;
-        // the trailer (CRC-32, byte count) is appended by gzip.hip
-        put(s, b, 0x8b1f, 16, lane); put(s, b, 0x0008, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0xff00, 16, lane);
-    }
-    for (int i = lane; i <= (1 << HBITS); i += 64) g_sea.head[i] = NONE;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-
-    DPROF_DECL
-    uint32_t accS = 0, accI = 0;                               // Adler-32 of the input, as in inflate.hip
-    int count = 0;                                             // queued terms
-    const int limit_terms = 2048;
-    auto unfilled = [&]() { return limit_terms - 1 - count; };
-    uint64_t w0 = 0, summed = 0;                               // where the parse goes on; positions below `summed` are in the sums already
-    if (resumed) {
-        w0 = uni64(st1->w); summed = uni64(st1->inserted); count = (int)UNI(st1->count);
-        for (int i = lane; i < count; i += 64) g_trm.terms[0][i] = st1->terms[i];
-        if (lane == 0) { accS = st1->adlerS; accI = st1->adlerI; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    }
-
-    if (n < 3) {
-        // Stream.compressBlocks stored tail (:45-60, :417-434)
-        put(s, b, 1, 3, lane);
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, (uint32_t)n, 16, lane); put(s, b, ~(uint32_t)n & 0xffff, 16, lane);
-        for (uint64_t k = 0; k < n; ++k) put(s, b, in[k], 8, lane);
-        if ((uint64_t)lane < n) { accS = in[lane]; accI = (uint32_t)lane * in[lane]; }
-    } else {
-        const uint64_t last_main = n - 4 + 1;                  // positions 0 .. n-4 are searched
-        // (a resumed stream: the 32 KiB in front of the parse position enter the window again)
-        uint64_t inserted = (w0 >= 32768 ? w0 - 32768 : 0) & ~(uint64_t)63;    // positions < inserted are in the window
-        uint64_t w = w0;                                       // parse position
-        uint32_t key_next = load_key(in, n, inserted + (uint64_t)lane);      // (keys travel one batch ahead of their insertion)
-        auto insert_upto = [&](uint64_t target) {
-            while (inserted < target && inserted < n) {
-                const uint32_t key = key_next;
-                key_next = load_key(in, n, inserted + 64 + lane);
-                insert_batch(g_sea.head, in, n, ring, inserted, key, accS, accI, lane, inserted + lane >= summed);
-                inserted = uni64(inserted + 64);
-            }
-        };
-
-        // (more input to come: a batch of 128 positions is only searched when each of them sees its whole look-ahead)
-        while (w < last_main && (!more || w + 128 + 259 <= n)) {
-            // keep the window filled well ahead of the 64 positions searched now (+258 of look-ahead
-            // is irrelevant for insertion: links only point backwards)
-            DPROF_BEGIN();
-            insert_upto(w + 192);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // our own ring stores, before we read them back
-            DPROF_END(0); DPROF_BEGIN();
-            // ---- match search: lane i answers window.match(from: w + i) and (from: w + 64 + i)
-            const uint64_t pA = w + lane, pB = pA + 64;
-            const bool liveA = pA < last_main, liveB = pB < last_main;
-            const uint32_t keyA = liveA ? load32(in + pA) : 0u, keyB = liveB ? load32(in + pB) : 0u;
-            uint32_t brA = 5, bdA = 1, brB = 5, bdB = 1;
-            chain_walk2(in, ring, n, pA, pB, liveA, liveB, keyA, keyB, wmask, attempts, goal,
-                        [&](int which, uint32_t dist, uint32_t run) {
-                            // the first strictly longest run wins (:145-208)
-                            if (which == 0) { if (brA < run) { brA = run; bdA = dist; } }
-                            else            { if (brB < run) { brB = run; bdB = dist; } }
-                        });
-            const uint32_t mrunA = brA > 5 ? brA : 0, mrunB = brB > 5 ? brB : 0;   // 0: no match (run must exceed 5, :129)
-            const uint32_t litA = keyA & 0xff, litB = keyB & 0xff;
-            auto at = [&](uint32_t xa, uint32_t xb, uint32_t t) -> uint32_t {
-                return t < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)xa, (int)t) : (uint32_t)__builtin_amdgcn_readlane((int)xb, (int)(t - 64));
-            };
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            DPROF_END(1); DPROF_BEGIN();
-
-            // ---- the parse: Stream.compress greedy (:209-252) / lazy (:268-323) over these 128 answers
-            uint32_t t = 0;
-            bool stop = false;
-            while (t < 128 && w + t < last_main && !stop) {
-                if (!(unfilled() > (lazy ? 1 : 0))) { DPROF_END(2); DPROF_BEGIN(); b = uni_bits(write_block(b, count, false, lane)); count = 0; DPROF_END(3); DPROF_BEGIN(); }
-                const uint32_t run = at(mrunA, mrunB, t);
-                const uint32_t lit = at(litA, litB, t);
-                if (!run) { g_trm.terms[0][count] = 0xf8000000u | lit; ++count; t += 1; continue; }
-                uint32_t use_run = run, use_dist = at(bdA, bdB, t);
-                uint32_t adv = run;
-                if (lazy) {
-                    // the answer for position w+t+1 is needed: restart the search there if it is not in this batch
-                    if (t + 1 >= 128) { stop = true; break; }
-                    // lazy match at a+1 (:293-299); it exists only if that position is still searched
-                    const uint32_t lrun = (w + t + 1 < last_main) ? at(mrunA, mrunB, t + 1) : 0u;
-                    if (lrun > run) {
-                        g_trm.terms[0][count] = 0xf8000000u | lit;
-                        ++count;
-                        use_run = lrun; use_dist = at(bdA, bdB, t + 1);
-                        adv = 1 + lrun;
-                    }
-                }
-                // LZ77.DeflatorTerm.init(run:distance:) (DeflatorTerm.swift:34-56)
-                const uint32_t rd = run_decade(use_run), dd = dist_decade(use_dist);
-                g_trm.terms[0][count] = dd << 27 | 0x100u | rd | dist_extra_value(use_dist, dd) << 14 | run_extra_value(use_run, rd) << 9;
-                ++count;
-                t += adv;
-            }
-            w = uni64(w + t);
-            DPROF_END(2);
-        }
-        if (more) {
-            // on with the next push: whole bytes out, the rest into the state
-            drain(s, b, b.total, lane);
-            uint32_t S = accS % 65521, I = accI % 65521;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) { S += __shfl_xor(S, m, 64); I += __shfl_xor(I, m, 64); }
-            for (int i = lane; i < count; i += 64) st1->terms[i] = g_trm.terms[0][i];
-            if (lane == 0) {
-                st1->w = w; st1->inserted = inserted > summed ? inserted : summed; st1->acc = b.acc; st1->nacc = b.nacc; st1->total = b.total;
-                st1->overflow = b.overflow ? 1u : 0u; st1->count = (uint32_t)count; st1->started = 1;
-                st1->adlerS = S % 65521; st1->adlerI = I % 65521;
-                spng_result &res = results[job.image];
-                res.status = b.overflow ? SPNG_E_OUTPUT_CAPACITY : SPNG_NEED_MORE_INPUT; res.reserved = 0;
-                res.written = b.total; res.consumed = w; res.aux[0] = w; res.aux[1] = 0;
-            }
-            return;
-        }
-        insert_upto(n);                                        // Adler-32 over the tail
-        // epilogue: the positions still in the window pipeline become literals (:254-265, :331-342)
-        for (uint64_t p = w; p < n; ++p) {
-            if (!(unfilled() > 0)) { b = uni_bits(write_block(b, count, false, lane)); count = 0; }
-            g_trm.terms[0][count] = 0xf8000000u | UNI(in[p]);
-            ++count;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        b = uni_bits(write_block(b, count, true, lane));
-    }
-
-    if (job.format == SPNG_FORMAT_ZLIB) {
-        // Adler-32 (see inflate.hip): s1 = 1 + S, s2 = N + N*S - I
-        uint32_t S = accS % 65521, I = accI % 65521;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { S += __shfl_xor(S, m, 64); I += __shfl_xor(I, m, 64); }
-        S %= 65521; I %= 65521;
-        const uint32_t N = (uint32_t)(n % 65521);
-        const uint32_t sum = ((N + (uint64_t)N * S % 65521 + 65521 - I) % 65521) << 16 | (1 + S) % 65521;
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, sum >> 24, 8, lane); put(s, b, (sum >> 16) & 0xff, 8, lane);
-        put(s, b, (sum >> 8) & 0xff, 8, lane); put(s, b, sum & 0xff, 8, lane);
-    }
-    if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);                // DeflatorOut.pull flushes padding bits
-    drain(s, b, b.total, lane);
-#ifdef SPNG_DEFLATE_PROF
-    if (lane == 0 && blockIdx.x == 0) printf("deflate prof cycles: insert %llu search %llu parse %llu write_block %llu\n", pt[0], pt[1], pt[2], pt[3]);
-#endif
-    if (lane == 0) {
-        spng_result &res = results[job.image];
-        res.status = b.overflow ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE; res.reserved = 0;
-        res.written = b.total; res.consumed = n; res.aux[0] = res.aux[1] = 0;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // levels >= 8: the shortest-path ("full") search
 // ------------------------------------------------------------------------------------------------
@@ -852,35 +506,9 @@ __global__ __launch_bounds__(64) void deflate_kernel(const DeflateJob *__restric
 // vertices (the limit doubles per block, 2048 ... 2^21) and finds the cheapest path through the block
 // with per-symbol costs in quarter bits that it re-derives from the trees of the previous pass
 // (trees(iterations:), :225-260; minimize / explore, :262-379; Depths, ...Depths.swift:31-98).
-// Here, per stream:
-//   * candidates: the 128-positions-at-a-time chain walk of the greedy / lazy kernel, every candidate
-//     recorded (per lane and half, thirty decade slots in LDS); the serial part is only deciding which
-//     positions are searched at all (behind a run > 100 the next run - 100 vertices get no edges,
-//     DeflatorBuffers.Stream.swift:376-380).  Vertices live in HBM: a flag (has edges) and, for those
-//     that have, 30 slots.
-//   * forward pass (full_forward / forward_body): the best way into a vertex as the minimum of one 64-bit
-//     key over its incoming edges; along 64 vertices the depths are a min-plus prefix scan, match edges
-//     go through ds_min_u64 into an LDS ring, three vertices at a time; with helper waves on
-//     compressible input.
-//   * back-trace (full_backward): 64 vertices at a time from the end, the path hopping through the
-//     batch on the scalar unit; path vertices tally the symbol frequencies and hand their edge to the
-//     vertex it starts from.
-//   * trees, cost update, repeat (2 x iterations passes for the first block, iterations after);
-//     then the block is written: the path's terms 64 at a time.
-struct FullArrays {      // (two registers' worth: passed to the non-inlined passes in SGPRs, not through scratch memory)
-    gword *base; uint32_t vcap;
-    // [vertex][30]: distance << 16 | longest run of that distance decade
-    __device__ __forceinline__ gword *slots_() const { return base; }
-    // [vertex]: incoming edge of the cheapest path, run << 16 | decade << 8 (literal: 1 << 16 | 0xff00)
-    __device__ __forceinline__ gword *up_() const { return base + (uint64_t)vcap * 30; }
-    // [vertex]: the path's edge that STARTS here (set by the back-trace)
-    __device__ __forceinline__ gword *step_() const { return up_() + vcap + 1; }
-    // [vertex]: on the path
-    __device__ __forceinline__ gbyte *pathb_() const { return (gbyte *)(step_() + vcap + 1); }
-    // [vertex]: has edges (its thirty slots are valid); vertices without ones never touch `slots`
-    __device__ __forceinline__ gbyte *flag_() const { return pathb_() + vcap + 1; }
-};
-
+// Here: the search and the parse in kernels of their own, round by round (below); per block the parse
+// runs the forward pass (d2_forward), the back-trace (d2_backward), the trees and the cost update,
+// 2 x iterations times for the first block and iterations times after, then writes the path's terms.
 __device__ __forceinline__ uint32_t run_base(uint32_t dec)       // LZ77.Composites.swift:25-63
 {
     if (dec < 9) return dec + 2;
@@ -904,11 +532,9 @@ __device__ __forceinline__ uint32_t depth_default(uint32_t i)    // Depths.defau
 // the vertex it leaves.  So, 64 vertices at a time:
 //   * the keys the matches have offered so far sit in an LDS ring (ds_min_u64);
 //   * depth(v) = min(offered(v), depth(v - 1) + literal cost) along the batch is a prefix scan under
-//     (a1, b1) o (a2, b2) = (a1 + a2, min(b1 + a2, b2)), in DPP steps, no memory;
+//     (a1, b1) o (a2, b2) = (a1 + a2, min(b1 + a2, b2)), in DPP steps, no memory (minplus_scan);
 //   * a match is at least 3 long: the depths of three consecutive vertices are final before any of their
-//     own edges is relaxed.  Vertices with edges are taken three positions at a time (lanes spread over the
-//     run lengths, costs in registers), then the scan is repeated.  Batches without edges (incompressible
-//     data) cost one scan.
+//     own edges is relaxed, so vertices with edges are taken three positions at a time between two scans.
 static constexpr uint32_t DINF = 0x3fffffffu;    // "no way in yet" (real depths stay below 2^28)
 __device__ __forceinline__ uint32_t minplus_scan(uint32_t a, uint32_t b, uint32_t x, int lane)
 {
@@ -935,211 +561,6 @@ __device__ __forceinline__ uint32_t minplus_scan(uint32_t a, uint32_t b, uint32_
     const uint32_t xin = lane < 16 ? x : lane < 32 ? x1 : lane < 48 ? x2 : x3;
     return xin + a < b ? xin + a : b;
 }
-
-// One forward pass, run by all four waves of the workgroup.  Wave 0 owns the pass: it fetches, keeps the ring
-// initialised, scans alone through batches without edges and finalises every batch.  In a batch with edges the
-// three vertices of a group (their depths are final together, see above) are relaxed by waves 0, 1 and 2 at the
-// same time -- each wave scans for itself (same ring, same result), so the only things exchanged are the ring and
-// one workgroup barrier per group; wave 3 only keeps the barrier count (256-thread workgroups place evenly).
-enum { FW_PASS = 1, FW_EXIT = 2 };
-// (WAVES == 1: the same pass on the one wave of a 64-thread workgroup -- no helpers, no barriers)
-template <int WAVES> __device__ __forceinline__ void wg_sync()
-{
-    if (WAVES > 1) __syncthreads();
-    else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-}
-template <int WAVES>
-__device__ __attribute__((noinline)) void forward_body(const FullArrays g, const gbyte *in, uint64_t bbase, uint32_t count, int lane, int wave)
-{
-    DLds &s = g_lds;
-    // costs in registers: distance decade `lane`; run lengths 3 + lane + 64 j
-    const uint32_t dcost = lane < 30 ? g_full.depths[512 + lane] : 0u;
-    uint32_t rc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const uint32_t L = 3u + (uint32_t)lane + 64u * j; rc[j] = L <= 258 ? g_full.depths[253 + L] : 0u; }
-    if (wave == 0 && lane == 0) g_full.win[0] = 0;                  // vertex 0: depth 0
-    uint32_t inited = 1, carry = DINF;                         // carry: depth of the vertex in front of the batch
-    // (the literal byte of a batch is fetched while the batch before it is worked on)
-    uint32_t lb_next = 0, fl_next = 0;
-    if (wave == 0) {
-        lb_next = (lane >= 1 && (uint32_t)lane <= count) ? in[bbase + lane - 1] : 0u;
-        fl_next = (uint32_t)lane < count ? g.flag_()[lane] : 0u;
-    }
-    for (uint32_t sb0 = 0; sb0 <= count; sb0 += 1024) {
-        // sixteen batches at a time, wave 0 tells the helpers which vertices have edges: through incompressible
-        // data they then sleep from one of these barriers to the next, one per 1024 vertices
-        const uint32_t spar = (sb0 >> 10) & 1;
-        if (WAVES > 1 && wave == 0) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const uint32_t vq = sb0 + 64u * q + (uint32_t)lane;
-                const unsigned long long e = __ballot(vq < count && g.flag_()[vq] != 0);
-                if (lane == 0) g_old.fw_ems[spar][q] = e;
-            }
-        }
-        if (WAVES > 1) __syncthreads();
-    for (uint32_t b0 = sb0; b0 <= count && b0 < sb0 + 1024; b0 += 64) {
-        const uint32_t nv = count + 1 - b0 < 64 ? count + 1 - b0 : 64;      // vertices b0 .. b0 + nv - 1 (the last one: `count`, the end)
-        const uint32_t v = b0 + (uint32_t)lane;
-        const uint32_t par = (b0 >> 6) & 1;
-        // (wave 0 has its own copy of the flags, fetched a batch ahead: no LDS round trip on its way through
-        //  edge-less batches)
-        unsigned long long em;
-        if (wave == 0) {
-            em = __ballot(fl_next != 0);
-            const uint32_t vn = b0 + 64 + (uint32_t)lane;
-            fl_next = vn < count ? g.flag_()[vn] : 0u;
-        } else {
-            em = uni64(g_old.fw_ems[spar][(b0 - sb0) >> 6]);
-            if (!em) continue;                                 // (wave 0 scans through it alone)
-        }
-        uint32_t cin = 0;
-        if (wave == 0) {
-            const uint32_t lb = lb_next;
-            {
-                const uint32_t vn = b0 + 64 + (uint32_t)lane;
-                lb_next = vn <= count ? in[bbase + vn - 1] : 0u;
-            }
-            const uint32_t need = (b0 + 64 + 258 < count ? b0 + 64 + 258 : count) + 1;
-            for (uint32_t j = inited + lane; j < need; j += 64) g_full.win[j & 511] = ~0ull;
-            inited = inited > need ? inited : need;
-            if (em) {
-                const uint32_t ns = count - b0 < 64 ? count - b0 : 64;
-                for (uint32_t i = lane; i < ns * 30; i += 64) g_old.batch[i] = g.slots_()[(uint64_t)b0 * 30 + i];
-            }
-            cin = (v >= 1 && v <= count) ? g_full.depths[lb] : 0u;   // the literal edge INTO v
-            if (WAVES > 1 && em) {
-                g_old.fw_cin[par][lane] = cin;
-                if (lane == 0) g_old.fw_carry[par] = carry;
-            }
-        }
-        if (WAVES > 1 && em) {
-            __syncthreads();                                   // the batch is set up
-            if (wave != 0) { cin = g_old.fw_cin[par][lane]; carry = UNI(g_old.fw_carry[par]); }
-        } else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        uint64_t W; uint32_t Wd, D;
-        uint32_t k = 0;
-        for (;;) {
-            W = (uint32_t)lane < nv ? g_full.win[v & 511] : ~0ull;
-            Wd = (uint32_t)(W >> 32) < DINF ? (uint32_t)(W >> 32) : DINF;
-            D = minplus_scan(cin, Wd, carry, lane);
-            const unsigned long long rest = k < 64 ? (em >> k) << k : 0ull;
-            if (!rest) break;
-            const uint32_t kk = (uint32_t)__ffsll((long long)rest) - 1;
-            // (four waves: this wave's vertex of the group; one wave: all three in turn)
-            for (uint32_t kq = kk + (WAVES > 1 ? (uint32_t)wave : 0u); kq < kk + (WAVES > 1 ? (uint32_t)wave + 1u : 3u); ++kq) {
-                if (!((WAVES == 1 || wave < 3) && kq < 64 && ((em >> kq) & 1) && count - (b0 + kq) >= 3)) continue;
-                const uint32_t vv = b0 + kq, rem = count - vv;
-                const uint32_t Dk = (uint32_t)__builtin_amdgcn_readlane((int)D, (int)kq);
-                const uint32_t run = lane < 30 ? g_old.batch[kq * 30 + lane] & 0xffffu : 0u;
-                unsigned long long m = __ballot(run > 0);
-                // Of the decades that reach a length, only the cheapest (first among equals: the lowest) can be
-                // the way into that target from this vertex: one key per length instead of one per decade.
-                uint32_t bc[4] = {~0u, ~0u, ~0u, ~0u}, bd[4] = {0, 0, 0, 0}, reach = 0;
-                while (m) {
-                    const int dec = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)run, dec);
-                    const uint32_t maxlen = r < rem ? r : rem;
-                    const uint32_t dc = (uint32_t)__builtin_amdgcn_readlane((int)dcost, dec);
-                    reach = maxlen > reach ? maxlen : reach;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (3u + 64u * j > maxlen) break;
-                        const uint32_t L = 3u + (uint32_t)lane + 64u * j;
-                        if (L <= maxlen && dc < bc[j]) { bc[j] = dc; bd[j] = (uint32_t)dec; }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (3u + 64u * j > reach) break;
-                    const uint32_t L = 3u + (uint32_t)lane + 64u * j;
-                    if (bc[j] != ~0u) {
-                        const uint64_t key = (uint64_t)(Dk + bc[j] + rc[j]) << 32 | (258u - L) << 8 | (bd[j] + 1u);
-                        __hip_atomic_fetch_min(&g_full.win[(vv + L) & 511], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-            }
-            k = kk + 3;
-            wg_sync<WAVES>();                                  // the group's keys are in the ring
-        }
-        if (wave != 0) continue;
-        // the way in: the literal only when strictly cheaper than what the matches offer
-        if ((uint32_t)lane < nv && v >= 1) {
-            const uint32_t low = (uint32_t)W;
-            g.up_()[v] = D < Wd ? 0x0001ff00u : (258u - (low >> 8)) << 16 | ((low & 0xff) - 1u) << 8;
-        }
-        carry = (uint32_t)__builtin_amdgcn_readlane((int)D, (int)(nv - 1));
-    }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// (wave 0) one forward pass, with the helper waves if there are any
-template <int WAVES>
-__device__ __attribute__((noinline)) void full_forward(const FullArrays g, const gbyte *in, uint64_t bbase, uint32_t count, int lane)
-{
-    DLds &s = g_lds;
-    if (WAVES > 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the vertices' flags and slots are in memory
-        if (lane == 0) { g_old.fw_cmd = FW_PASS; g_old.fw_bbase = bbase; g_old.fw_count = count; }
-        __syncthreads();
-    }
-    forward_body<WAVES>(g, in, bbase, count, lane, 0);
-    if (WAVES > 1) __syncthreads();                            // (the helpers are back in their loop before anything else changes)
-}
-
-// minimize() backwards (:282-320): the path from the last vertex to the first, symbol frequencies into
-// s.freq, every path edge handed to the vertex it starts from.  64 vertices at a time, descending from a
-// vertex on the path: lane i holds the way into vertex hi - i; the path hops through the batch on the
-// scalar unit (v_readlane with the hop's length), and a batch of nothing but literals is all path.
-__device__ __attribute__((noinline)) void full_backward(const FullArrays g, const gbyte *in, uint64_t bbase, uint32_t count, int lane)
-{
-    DLds &s = g_lds;
-    for (int i = lane; i < 320; i += 64) s.freq[i] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    uint32_t hi = count;
-    // (the ways into the next 64 vertices are fetched ahead on the guess that the path leaves this batch
-    //  exactly at its end, as it does through literals; a longer hop refetches)
-    uint32_t u_next = ((uint32_t)lane < hi) ? g.up_()[hi - (uint32_t)lane] : 0u, hi_next = hi;
-    for (;;) {
-        const bool valid = (uint32_t)lane <= hi;
-        const uint32_t c = valid ? hi - (uint32_t)lane : 0u;
-        uint32_t u = u_next;
-        if (hi_next != hi) u = (valid && c > 0) ? g.up_()[c] : 0u;
-        if (hi >= 64) { hi_next = hi - 64; u_next = ((uint32_t)lane < hi_next) ? g.up_()[hi_next - (uint32_t)lane] : 0u; }
-        const uint32_t len = u >> 16;                          // 0: vertex 0 (or nothing)
-        unsigned long long pm = 0;
-        uint32_t pos = 0;
-        if (!__ballot(valid && c > 0 && len != 1)) { pm = __ballot(valid); pos = 64; }
-        else {
-            while (pos < 64) {
-                pm |= 1ull << pos;
-                const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)len, (int)pos);
-                if (!l) break;
-                pos += l;
-            }
-        }
-        const bool on = ((pm >> lane) & 1) != 0;
-        if (valid && c < count) g.pathb_()[c] = on ? 1 : 0;
-        if (on && c > 0) {
-            const uint32_t nxt = c - len;
-            g.step_()[nxt] = u & 0xffffff00u;
-            if (len == 1) atomicAdd(&s.freq[in[bbase + nxt]], 1u);
-            else { atomicAdd(&s.freq[256 | run_decade(len)], 1u); atomicAdd(&s.freq[288 + ((u >> 8) & 0xff)], 1u); }
-        }
-        if (hi < 64 || pos > hi) break;                        // vertex 0 was in this batch
-        if (pos < 64) break;                                   // (cannot happen: a hop of length 0 above vertex 0)
-        const uint32_t nhi = hi - pos;
-        // vertices the leaving hop jumped over are not on the path
-        for (uint32_t cc = nhi + 1 + (uint32_t)lane; cc + 64 <= hi; cc += 64) g.pathb_()[cc] = 0;
-        hi = nhi;
-    }
-    if (lane == 0) s.freq[256] = 1;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 // Depths.update (Depths.swift:53-86): the cost of a symbol = the length of its code (+ extra bits) in
 // quarter bits; symbols without a code keep their cost.  The reference writes in (code length, symbol)
 // order and run 258 belongs to two symbols (284 with extra bits 31, and 285): the later write wins.
@@ -1165,262 +586,21 @@ __device__ __forceinline__ void full_depths_update(int lane)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
 }
 
-// Stream.writeBlock (DeflatorBuffers.Stream.swift:440-709), full form: trees(iterations:), header, the path's tokens
-template <int WAVES>
-__device__ __attribute__((noinline)) Bits full_block(Bits b_, const FullArrays g_, const gbyte *in_, uint64_t bbase_, uint32_t count_,
-                                                     bool final_, int iterations_, bool generic_, int lane)
-{
-    Bits b = uni_bits(b_);
-    FullArrays g; g.base = UNIP(gword *, g_.base); g.vcap = UNI(g_.vcap);
-    const gbyte *in = UNIP(const gbyte *, in_);
-    const uint64_t bbase = uni64(bbase_);
-    const uint32_t count = UNI(count_);
-    const bool final = UB(final_), generic = UB(generic_);
-    const int iterations = (int)UNI(iterations_);
-    DLds &s = g_lds;
-    for (int i = generic ? -iterations : 0;;) {
-        if (count) { FPROF(2); full_forward<WAVES>(g, in, bbase, count, lane); FPROF(4); full_backward(g, in, bbase, count, lane); FPROF(5); }
-        else {
-            for (int k = lane; k < 320; k += 64) s.freq[k] = k == 256 ? 1u : 0u;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        }
-        build_tree(s.freq, 286, 15, s.ll, lane);
-        build_tree(s.freq + 288, 30, 15, s.dl, lane);
-        ++i;
-        FPROF(6);
-        if (!(i < iterations)) break;
-        full_depths_update(lane);
-    }
-    b = uni_bits(write_tables(b, final, lane));
-    FPROF(7);
-    // writeBlock(with:) (:661-707): the path's terms, 64 vertices at a time
-    uint32_t pb_next = (uint32_t)lane < count ? g.pathb_()[lane] : 0u, st_next = (uint32_t)lane < count ? g.step_()[lane] : 0u,
-             lt_next = (uint32_t)lane < count ? in[bbase + lane] : 0u;
-    for (uint32_t b0 = 0; b0 < count; b0 += 64) {
-        const uint32_t v = b0 + lane;
-        const bool on = v < count && pb_next != 0;
-        const uint32_t st = st_next, lt = lt_next;
-        {
-            const uint32_t vn = v + 64;
-            const bool inn = vn < count;
-            pb_next = inn ? g.pathb_()[vn] : 0u; st_next = inn ? g.step_()[vn] : 0u; lt_next = inn ? in[bbase + vn] : 0u;
-        }
-        uint64_t bits = 0; uint32_t nb = 0;
-        if (on) {
-            const uint32_t cnt = st >> 16, dd = (st >> 8) & 0xff;
-            if (cnt == 1) bits = literal_bits(s, lt, nb);
-            else {
-                const uint32_t off = g.slots_()[(uint64_t)v * 30 + dd] >> 16, rd = run_decade(cnt);
-                bits = match_bits(s, rd, run_extra_value(cnt, rd), dd, dist_extra_value(off, dd), nb);
-            }
-        }
-        bulk_put(s, b, bits, nb, lane);
-        maybe_drain(s, b, lane);
-    }
-    put(s, b, s.lcode[256], s.ll[256], lane);
-    maybe_drain(s, b, lane);
-    FPROF(8);
-    // resetGraph -> Depths.generalize (Depths.swift:88-98)
-    for (uint32_t i = lane; i < 542; i += 64) {
-        const uint32_t x = g_full.depths[i], d = depth_default(i);
-        g_full.depths[i] = (uint8_t)((x & d) + ((x ^ d) >> 1));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    return b;
-}
-
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void deflate_full_kernel(const DeflateJob *__restrict__ jobs, spng_result *__restrict__ results)
-{
-    DLds &s = g_lds;
-    const DeflateJob *jp = jobs + blockIdx.x;
-    // Which of the four waves is the stream's main wave rotates with the workgroup: the waves of a workgroup go one to
-    // each SIMD, and the two workgroups a CU holds (placed 256 apart) should not keep their busy waves on the same one.
-    const int lane = threadIdx.x & 63;
-    const int wave = WAVES > 1 ? (int)UNI(((threadIdx.x >> 6) - (blockIdx.x + (blockIdx.x >> 8))) & 3) : 0;
-    if (WAVES > 1 && wave != 0) {
-        // helper waves: they serve the forward passes wave 0 announces (forward_body) until it says it is done
-        FullArrays gh;
-        gh.base = (gword *)uni64((uint64_t)jp->graph); gh.vcap = UNI(jp->graph_vertices);
-        const gbyte *inh = (const gbyte *)uni64((uint64_t)jp->src);
-        for (;;) {
-            __syncthreads();
-            if (UNI(g_old.fw_cmd) != FW_PASS) return;
-            forward_body<WAVES>(gh, inh, uni64(g_old.fw_bbase), UNI(g_old.fw_count), lane, wave);
-            __syncthreads();
-        }
-    }
-    const gbyte *in = (const gbyte *)uni64((uint64_t)jp->src);
-    const uint64_t n = uni64(jp->src_len);
-    gword *ring = (gword *)uni64((uint64_t)jp->ring);
-    struct { gbyte *dst; uint64_t dst_cap; int32_t format, level; uint32_t image; } job = {
-        (gbyte *)uni64((uint64_t)jp->dst), uni64(jp->dst_cap), (int32_t)UNI(jp->format), (int32_t)UNI(jp->level), UNI(jp->image) };
 #ifdef SPNG_DEFLATE_PROF
-    if (lane < 12) g_prof[lane] = lane == 11 ? __builtin_readcyclecounter() : 0;
+// dfl2_parse_kernel: cycles per phase, kept in LDS so that the non-inlined passes can add to them
+__shared__ uint64_t g_prof[12];
+#define FPROF(k) do { const uint64_t now_ = __builtin_readcyclecounter(); if (threadIdx.x == 0) { g_prof[k] += now_ - g_prof[11]; g_prof[11] = now_; } } while (0)
+#else
+#define FPROF(k)
 #endif
-    const uint32_t vcap = UNI(jp->graph_vertices);             // vertices the scratch arrays hold
-    FullArrays g;
-    {
-        g.base = (gword *)uni64((uint64_t)jp->graph); g.vcap = vcap;
-    }
-    // DeflatorSearch.init(level:) (:13-35), full rows
-    const int lv = job.level > 13 ? 13 : job.level;
-    const int attempts = lv == 8 ? 14 : lv == 9 ? 20 : lv == 10 ? 30 : lv == 11 ? 60 : lv == 12 ? 100 : 0x7fffffff;
-    const int goal = lv == 8 ? 20 : lv == 9 ? 32 : lv == 10 ? 50 : lv == 11 ? 80 : lv == 12 ? 133 : 258;
-    const int iterations = lv - 7;
-    const uint32_t wmask = (1u << UNI(jp->exponent)) - 1;
-
-    for (int i = lane; i < OUTB / 4; i += 64) s.out32[i] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    Bits b = {0, 0, 0, 0, job.dst, job.dst_cap, false};
-    if (job.format == SPNG_FORMAT_ZLIB) {
-        // StreamHeader.write (StreamHeader.swift:56-62)
-        const uint32_t unpaired = (UNI(jp->exponent) - 8) << 4 | 0x08;
-        const uint32_t check = ~(((unpaired << 8 | unpaired >> 8) & 0xffff) % 31) & 31;
-        put(s, b, check << 8 | unpaired, 16, lane);
-    } else if (job.format == SPNG_FORMAT_GZIP) {
-        // Gzip.StreamHeader.write (Gzip.StreamHeader.swift:84-96): sigil, method 8, no flags, MTIME 0, XFL 0, OS 255;
-        // the trailer (CRC-32, byte count) is appended by gzip.hip
-        put(s, b, 0x8b1f, 16, lane); put(s, b, 0x0008, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0xff00, 16, lane);
-    }
-    for (int i = lane; i <= (1 << HBITS); i += 64) g_sea.head[i] = NONE;
-    for (uint32_t i = lane; i < 542; i += 64) g_full.depths[i] = (uint8_t)depth_default(i);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-
-    uint32_t accS = 0, accI = 0;
-    uint32_t count = 0, limit = 2048;
-    bool generic = true;
-    uint64_t bbase = 0;
-    auto unfilled = [&]() { return (int)limit - 1 - (int)count; };
-    auto close_block = [&](bool final) {
-        const uint32_t doubled = 2 * limit < (1u << 21) ? 2 * limit : 1u << 21;     // trees(iterations:) :229
-        b = uni_bits(full_block<WAVES>(b, g, in, bbase, count, final, iterations, generic, lane));
-        generic = false; count = 0; limit = doubled < vcap + 1 ? doubled : vcap + 1;
-    };
-
-    if (n < 3) {
-        // Stream.compressBlocks stored tail (:45-60, :417-434)
-        put(s, b, 1, 3, lane);
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, (uint32_t)n, 16, lane); put(s, b, ~(uint32_t)n & 0xffff, 16, lane);
-        for (uint64_t k = 0; k < n; ++k) put(s, b, in[k], 8, lane);
-        if ((uint64_t)lane < n) { accS = in[lane]; accI = (uint32_t)lane * in[lane]; }
-    } else {
-        const uint64_t last_main = n - 4 + 1;
-        uint64_t inserted = 0, w = 0;
-        uint32_t key_next = load_key(in, n, (uint64_t)lane);      // (keys travel one batch ahead of their insertion)
-        auto insert_upto = [&](uint64_t target) {
-            while (inserted < target && inserted < n) {
-                const uint32_t key = key_next;
-                key_next = load_key(in, n, inserted + 64 + lane);
-                insert_batch(g_sea.head, in, n, ring, inserted, key, accS, accI, lane);
-                inserted = uni64(inserted + 64);
-            }
-        };
-        while (w < last_main) {
-            FPROF(2);
-            insert_upto(w + 192);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            FPROF(0);
-            // ---- every candidate of positions w + lane and w + 64 + lane becomes an edge (DeflatorWindow.match, :132-212)
-            const uint64_t pA = w + lane, pB = pA + 64;
-            const bool liveA = pA < last_main, liveB = pB < last_main;
-            const uint32_t keyA = liveA ? load32(in + pA) : 0u, keyB = liveB ? load32(in + pB) : 0u;
-#pragma unroll
-            for (int d = 0; d < 30; ++d) { g_sea.cslot[0][d * 64 + lane] = 0; g_sea.cslot[1][d * 64 + lane] = 0; }
-            uint32_t extA = 1, extB = 1;
-            chain_walk2(in, ring, n, pA, pB, liveA, liveB, keyA, keyB, wmask, attempts, goal,
-                        [&](int which, uint32_t dist, uint32_t run) {
-                            uint32_t &ext = which ? extB : extA;
-                            ext = run > ext ? run : ext;
-                            uint32_t *slot = &g_sea.cslot[which][dist_decade(dist) * 64 + lane];
-                            if (run > (*slot & 0xffff)) *slot = dist << 16 | run;
-                        });
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            FPROF(1);
-            // ---- which positions are vertices with edges (Stream.compress full, :344-400)
-            uint32_t t = 0;
-            while (t < 128 && w + t < last_main) {
-                const uint32_t hf = t >> 6, tl = t & 63;
-                const uint32_t extent = hf ? extB : extA;
-                if (tl == 0 && !__ballot(extent > 100) && w + t + 64 <= last_main && unfilled() >= 64) {
-                    // a whole half with nothing to skip and no block to close: 64 vertices at once
-                    if (count == 0) bbase = w + t;
-                    const bool has = extent > 1;               // (a candidate matched: at least the four key bytes)
-                    g.flag_()[count + lane] = has ? 1 : 0;
-                    if (__ballot(has))
-                        for (uint32_t i = lane; i < 64 * 30; i += 64) { const uint32_t vtx = i / 30, d = i - vtx * 30; g.slots_()[(uint64_t)count * 30 + i] = g_sea.cslot[hf][d * 64 + vtx]; }
-                    count += 64;
-                    t += 64;
-                    continue;
-                }
-                if (!(unfilled() > 0)) close_block(false);
-                if (count == 0) bbase = w + t;
-                const int ext = __builtin_amdgcn_readlane((int)extent, (int)tl);
-                if (ext > 1) { if (lane < 30) g.slots_()[(uint64_t)count * 30 + lane] = g_sea.cslot[hf][lane * 64 + tl]; }
-                if (lane == 0) g.flag_()[count] = ext > 1 ? 1 : 0;
-                count += 1;
-                int skip = ext - 100 < unfilled() ? ext - 100 : unfilled();
-                if (skip > 0) {
-                    for (uint32_t i = lane; i < (uint32_t)skip; i += 64) g.flag_()[count + i] = 0;
-                    count += (uint32_t)skip;
-                } else skip = 0;
-                t += 1 + (uint32_t)skip;
-            }
-            w = uni64(w + t);
-        }
-        insert_upto(n);
-        // epilogue: the three positions still in the window pipeline (:254-265)
-        for (uint64_t p = w; p < n; ++p) {
-            if (!(unfilled() > 0)) close_block(false);
-            if (count == 0) bbase = p;
-            if (lane == 0) g.flag_()[count] = 0;
-            count += 1;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        close_block(true);
-    }
-
-    if (job.format == SPNG_FORMAT_ZLIB) {
-        uint32_t S = accS % 65521, I = accI % 65521;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { S += __shfl_xor(S, m, 64); I += __shfl_xor(I, m, 64); }
-        S %= 65521; I %= 65521;
-        const uint32_t N = (uint32_t)(n % 65521);
-        const uint32_t sum = ((N + (uint64_t)N * S % 65521 + 65521 - I) % 65521) << 16 | (1 + S) % 65521;
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, sum >> 24, 8, lane); put(s, b, (sum >> 16) & 0xff, 8, lane);
-        put(s, b, (sum >> 8) & 0xff, 8, lane); put(s, b, sum & 0xff, 8, lane);
-    }
-    if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-    drain(s, b, b.total, lane);
-    if (WAVES > 1) {
-        if (lane == 0) g_old.fw_cmd = FW_EXIT;                     // the helper waves leave
-        __syncthreads();
-    }
-#ifdef SPNG_DEFLATE_PROF
-    if (lane == 0 && blockIdx.x == 0)
-        printf("deflate_full prof Mcycles: insert %llu search %llu register %llu forward %llu backward %llu trees %llu tables %llu emit %llu\n",
-               g_prof[0] >> 20, g_prof[1] >> 20, g_prof[2] >> 20, g_prof[4] >> 20, g_prof[5] >> 20, g_prof[6] >> 20, g_prof[7] >> 20, g_prof[8] >> 20);
-#endif
-    if (lane == 0) {
-        spng_result &res = results[job.image];
-        res.status = b.overflow ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE; res.reserved = 0;
-        res.written = b.total; res.consumed = n; res.aux[0] = res.aux[1] = 0;
-    }
-}
 
 // =====================================================================================================================
 // levels >= 8, round 4: the search and the parse in kernels of their own
 // =====================================================================================================================
-// deflate_full_kernel above keeps a stream on ONE wave: insertion, chain walks, the shortest path, the trees and the bits, one
-// after the other -- a quarter of the chip's SIMDs with a single, latency-bound wave each, and a per-stream graph scratch (130
-// bytes per vertex) that lets ~370 streams of 64 MiB in at a time.  But the candidates of a position are a pure function of the
-// input (the design note at the top of this file), and the block boundaries of the full search are fixed vertex counts
-// (2047, 4095, ... 2^21 - 1: LZ77.DeflatorMatches.swift:229): nothing about them has to wait for the parse.  So a batch now
-// goes through in ROUNDS of up to 2^21 vertices per stream (the small blocks of a stream's start together, then one block at
-// the cap per round), each round two launches:
+// The candidates of a position are a pure function of the input (the design note at the top of this file), and the block
+// boundaries of the full search are fixed vertex counts (2047, 4095, ... 2^21 - 1: LZ77.DeflatorMatches.swift:229): nothing
+// about them has to wait for the parse.  So a batch goes through in ROUNDS of up to 2^21 vertices per stream (the small
+// blocks of a stream's start together, then one block at the cap per round), each round two launches:
 //   * the search kernel (round 4: dfl2_search_kernel, links in HBM; round 5: dfl3_search_kernel below, the window in LDS) --
 //     every stream's round cut into chunks, a workgroup per chunk: wave 0 inserts (32 KiB of warm-up in front of the chunk),
 //     the others take 64 positions at a time behind it, walk the chains and leave, per position, the longest run
@@ -1428,12 +608,12 @@ __global__ __launch_bounds__(WAVES * 64) void deflate_full_kernel(const DeflateJ
 //     a batch of 64 positions takes what it needs from a pool shared by all streams.  Incompressible input leaves no words.
 //   * dfl2_parse_kernel -- one wave per stream, 38 KB of LDS (four per CU): the skip rule of runs > 100 (which vertices lose
 //     their edges: the only thing about the graph that IS sequential), then per block the forward passes, the back-trace,
-//     the trees and the bits as before, its state (bit writer, symbol costs, block limit) kept in HBM from round to round.
+//     the trees and the bits, its state (bit writer, symbol costs, block limit) kept in HBM from round to round.
 //     Forward pass: what a vertex offers each target length -- the cheapest decade that reaches it -- does not depend on the
 //     vertex's depth, so it is tabulated for the 64 vertices of a batch at once (LDS atomic min per candidate word, one
 //     suffix-min sweep over the lengths, all lanes busy) and the dependent part per vertex shrinks to one row read, one add
 //     and one ds_min_u64 per lane.
-// The old kernel stays as the path for streams the pool could not serve (dfl2 marks them; api.hip runs them afterwards).
+// A stream the pool could not serve is marked (D2State::fail); api.hip runs it once more with a pool of its worst case.
 static constexpr uint32_t D2_RV = 1u << 21;                     // vertices per stream and round
 static constexpr uint32_t D2_PCOLS = 64, D2_PSTRIDE = 65;       // offer table: lengths 3 .. 66, rows padded against bank conflicts
 __shared__ uint32_t g_ptab[66 * D2_PSTRIDE];                    // (parse kernel only; two rows of padding: a group of three vertices is read blind)
@@ -2033,15 +1213,14 @@ __global__ __launch_bounds__(SPNG_D3_WAVES * 64) void dfl3_search_kernel(const D
 }
 
 // ---- levels 0-7 in rounds: dfl3_search_kernel<false> + dfl3_parse_kernel ----------------------------------------------------
-// deflate_kernel keeps insertion, chain walk, parse, trees and bits of a stream on ONE wave (2.6 MB/s per stream at level 6, two
-// thirds of it the chain walk, 512 streams resident).  What DeflatorWindow.match answers is a function of the input alone at
-// these levels too (the design note at the top of this file), so the search goes chip-wide exactly as at levels >= 8: a stream's
-// positions in rounds of 2^21, every round cut into chunks for the search workgroups above, which leave ONE word per position --
-// the first strictly longest run > 5 within `attempts` candidates, stopped at `goal` (:132-212) -- and a parse wave per stream
-// that only walks those answers with the greedy / lazy rules (DeflatorBuffers.Stream.swift:209-342), queues terms and writes
-// blocks; its state (parse position, queued terms, bit writer) is the D1State of spng_deflate_resume_batch, kept in HBM from
-// round to round.  The search of round r + 1 runs beside the parse of round r.  A round's search covers one position more than
-// the round (a lazy parse looks at position + 1).
+// What DeflatorWindow.match answers is a function of the input alone at these levels too (the design note at the top of this
+// file), so the search goes chip-wide exactly as at levels >= 8: a stream's positions in rounds of 2^21, every round cut into
+// chunks for the search workgroups above, which leave ONE word per position -- the first strictly longest run > 5 within
+// `attempts` candidates, stopped at `goal` (:132-212) -- and a parse wave per stream that only walks those answers with the
+// greedy / lazy rules (DeflatorBuffers.Stream.swift:209-342), queues terms and writes blocks; its state (parse position, queued
+// terms, bit writer) is the D1State of spng_deflate_resume_batch, kept in HBM from round to round.  The search of round r + 1
+// runs beside the parse of round r.  A round's search covers one position more than the round (a lazy parse looks at
+// position + 1).
 static constexpr uint32_t D3_RV = 1u << 21;
 uint64_t deflate3_round_positions() { return D3_RV; }
 // the positions a call may parse: all of them, or -- more input to come -- those whose look-ahead (their own and that of the
@@ -2728,7 +1907,7 @@ __device__ __forceinline__ unsigned long long d2_offers(const D2Arrays g, uint32
     return longm;
 }
 
-// a vertex with a run beyond the table: the per-entry form of the one-kernel search (forward_body), lane = candidate word
+// a vertex with a run beyond the table: its candidate words relaxed one by one (lane = candidate word, run lengths in registers)
 __device__ __forceinline__ void d2_relax_long(const D2Arrays g, uint64_t vr, uint32_t vv, uint32_t count, uint32_t Dk, const uint32_t (&rc)[4], int lane)
 {
     DLds &s = g_lds;
@@ -2779,8 +1958,9 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t v)
            (uint32_t)__builtin_amdgcn_readlane((int)incl, 47) + (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 }
 
-// minimize() forwards, as full_forward; keys: depth << 32 | (258 - length) << 23 | (decade + 1) << 15 | distance (the distance
-// rides along -- one per vertex and decade, it never decides -- so that the way in knows it without a look-up).
+// minimize() forwards (why one key and a scan: minplus_scan above); keys: depth << 32 | (258 - length) << 23 | (decade + 1) << 15 |
+// distance (the distance rides along -- one per vertex and decade, it never decides -- so that the way in knows it without a
+// look-up).
 //   * A batch without edges that no earlier edge reaches is a run of literals: its depths are a plain sum, its ways in are not
 //     written at all (g.litb[batch] = 1 says so to the back-trace) -- the whole of an incompressible stream but a few batches.
 //   * In a batch with edges the depths are scanned over all 64 lanes only at its start and at its end; between two groups of
@@ -3031,7 +2211,8 @@ __device__ __attribute__((noinline)) void d2_forward(const D2Arrays g_, const gb
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// minimize() backwards (:282-320), as full_backward with the wider ways-in
+// minimize() backwards (:282-320): 64 vertices at a time from the end, the path hopping through the batch on the scalar unit;
+// path vertices tally the symbol frequencies and hand their edge to the vertex it starts from
 __device__ __attribute__((noinline)) void d2_backward(const D2Arrays g_, const gbyte *in_, uint64_t bbase_, uint64_t vr0_, uint32_t count_, int lane)
 {
     const D2Arrays g = uni_arrays(g_);
@@ -3417,71 +2598,4 @@ hipError_t launch_deflate2_parse(const D2Stream *d_streams, uint32_t count, cons
     dfl2_parse_kernel<<<count, 64, 0, stream>>>(d_streams, d_pool, d_results, parity);
     return hipGetLastError();
 }
-
-// bytes of graph scratch a stream of n bytes needs at levels >= 8 (api.hip sizes the slab with it)
-uint64_t deflate_graph_vertices(uint64_t n)
-{
-    const uint64_t cap = (1u << 21) - 1;
-    return n + 2 < cap ? n + 2 : cap;
-}
-uint64_t deflate_graph_bytes(uint64_t vertices)
-{
-    return ((vertices + 1) * (30 * 4 + 4 + 4 + 1 + 1) + 1024 + 255) & ~(uint64_t)255;
-}
-
-// How often does a 4-byte key repeat close by?  Sampled (four windows of 8192 positions, a 4096-entry table of the
-// last key per bucket): the full-search kernel is launched with helper waves only for streams whose vertices will
-// have edges to relax -- on incompressible input the four-wave form costs a few per cent and buys nothing.
-__global__ __launch_bounds__(64) void deflate_density_kernel(const DeflateJob *__restrict__ jobs, uint32_t *__restrict__ dense)
-{
-    __shared__ uint32_t tab[4096];
-    const int lane = threadIdx.x;
-    const DeflateJob *jp = jobs + blockIdx.x;
-    const gbyte *in = (const gbyte *)uni64((uint64_t)jp->src);
-    const uint64_t n = uni64(jp->src_len);
-    uint32_t hits = 0, seen = 0;
-    if (n >= 64) {
-        const uint64_t win = n / 4 < 8192 ? n / 4 : 8192;
-        for (int w = 0; w < 4; ++w) {
-            const uint64_t from = (uint64_t)w * (n / 4);
-            for (int i = lane; i < 4096; i += 64) tab[i] = 0x9e3779b9u + (uint32_t)i;       // (no key hashes to its own filler)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            for (uint64_t p0 = 0; p0 + 4 <= win; p0 += 64) {
-                const uint64_t p = from + p0 + lane;
-                const bool live = p0 + lane + 4 <= win && p + 4 <= n;
-                const uint32_t key = live ? load32(in + p) : 0u;
-                const uint32_t h = (key * 0x9E3779B1u) >> 20;
-                const bool hit = live && tab[h] == key;
-                if (live) tab[h] = key;
-                hits += (uint32_t)__popcll(__ballot(hit));
-                seen += (uint32_t)__popcll(__ballot(live));
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            }
-        }
-    }
-    if (lane == 0) dense[blockIdx.x] = (seen && hits * 20u >= seen) ? 1u : 0u;             // >= 5 % of the positions
-}
-
-hipError_t launch_deflate_density(const DeflateJob *d_jobs, uint32_t count, uint32_t *d_dense, hipStream_t stream)
-{
-    if (!count) return hipSuccess;
-    deflate_density_kernel<<<count, 64, 0, stream>>>(d_jobs, d_dense);
-    return hipGetLastError();
-}
-
-hipError_t launch_deflate_full(const DeflateJob *d_jobs, uint32_t count, bool helpers, spng_result *d_results, hipStream_t stream)
-{
-    if (!count) return hipSuccess;
-    if (helpers) deflate_full_kernel<4><<<count, 256, 0, stream>>>(d_jobs, d_results);
-    else deflate_full_kernel<1><<<count, 64, 0, stream>>>(d_jobs, d_results);
-    return hipGetLastError();
-}
-
-hipError_t launch_deflate(const DeflateJob *d_jobs, uint32_t count, spng_result *d_results, hipStream_t stream)
-{
-    if (!count) return hipSuccess;
-    deflate_kernel<<<count, 64, 0, stream>>>(d_jobs, d_results);
-    return hipGetLastError();
-}
-
 }  // namespace spng

@@ -1,6 +1,6 @@
 """The deflate kernels of csrc/deflate.hip -- levels >= 8: dfl2_begin -> dfl3_search -> dfl2_advance -> dfl2_parse, round by round;
 levels 0-7: dfl3_begin -> dfl3_search_fast -> dfl3_advance -> dfl4_walk / dfl4_block / dfl4_scan / dfl4_place (one-shot streams) or
-dfl3_parse (streams that arrive in pieces), and the one-kernel form, deflate_kernel -- run on the CPU by the wave emulator of tools/emu and compared with the oracle's stream bit for bit.  The build container has no GPU:
+dfl3_parse (streams that arrive in pieces) -- run on the CPU by the wave emulator of tools/emu and compared with the oracle's stream bit for bit.  The build container has no GPU:
 this is how the LOGIC of the device deflater -- hash chains and candidate records, the skip rule, offer tables, the shortest-path
 passes, trees, the bit writer -- is checked before a GPU minute is spent.  The emulator compiles a COPY of the source prepared by
 tools/emu/prep_deflate.py (launches blanked, a few meetings of the wave where the source relies on lock-step execution); timing
@@ -121,21 +121,6 @@ def test_emulated_two_wave_parse_and_raw_format(emu, emu_small_rounds, tmp_path,
                                timeout=900, env=dict(os.environ, **env))
             assert r.returncode == 0, (name, level, env, r.stdout[-300:], r.stderr[-300:])
             assert ("blocks side by side" in r.stdout) == (not env)
-
-
-@pytest.mark.parametrize("level", [1, 6])
-@pytest.mark.parametrize("name", ["walk", "rows", "mixed", "two"])
-def test_emulated_one_kernel_greedy_lazy_form(emu, tmp_path, name, level):
-    """SPNG_DEFLATE_ONE_KERNEL at levels 0-7: `deflate_kernel`, one wave per stream does everything (the fallback when the search
-    records find no memory)"""
-    data = INPUTS[name]
-    want = ph.orc_deflate(data, level)
-    (tmp_path / "in").write_bytes(data)
-    (tmp_path / "want").write_bytes(want)
-    r = subprocess.run([str(emu), str(tmp_path / "in"), str(tmp_path / "want"), str(level), "0"], capture_output=True, text=True, timeout=900,
-                       env=dict(os.environ, EMU_ONE_KERNEL="1"))
-    assert r.returncode == 0, (name, level, r.stdout[-300:], r.stderr[-300:])
-    assert "greedy / lazy kernel" in r.stdout
 
 
 @pytest.mark.parametrize("level,name", [(0, "walk"), (4, "rows"), (6, "mixed"), (7, "runs"), (6, "noise")])

@@ -517,19 +517,32 @@ def test_deflate_vs_oracle(gpu, level):
         assert zlib.decompress(got if fmt == 0 else want) == data if fmt == 0 else True
 
 
-def test_deflate_one_kernel_mode(gpu):
-    """SPNG_CFG_DEFLATE_MODE = SPNG_DEFLATE_ONE_KERNEL: a wave per stream does everything (`deflate_kernel` at levels 0-7,
-    `deflate_full_kernel` from 8 on) -- the form the rounds of search + parse kernels fall back to when their records find no
-    memory: the same bytes"""
+def test_deflate_dry_pool_second_pass(gpu):
+    """Levels >= 8, a batch whose candidate words overflow the pool its group shares (SPNG_CFG_DEFLATE_BYTES at its minimum: a
+    pool of 64 MiB = 16 M words for five one-shot streams of 700 000 positions, each of which leaves ~8 words): the streams the
+    pool ran dry under go through the rounds once more, with pools of their worst case.  Every stream is the oracle's, and the
+    search launches outnumber the one round the batch needs (its five streams in one group).  Key 6 of spng_configure (the
+    retired one-kernel mode) is refused."""
+    import torch
     s = gpu.load()
-    payloads = _deflate_payloads()
+    assert s.lib.spng_configure(s.ctx, 6, 0) == gpu.E_ARGUMENT
+    # random bytes over four symbols: candidates in many distance decades for every position, their runs far below `goal`
+    datas = [np.random.default_rng(90 + i).integers(0, 4, 700_000, dtype=np.uint8).tobytes() for i in range(5)]
+    tens = [torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda() for d in datas]
     try:
-        s.configure(gpu.CFG_DEFLATE_MODE, gpu.DEFLATE_ONE_KERNEL)
-        for level in (1, 6, 9):
-            for kind in ("text", "noise", "sparse", "ramp"):
-                assert s.deflate(payloads[kind], level) == ph.orc_deflate(payloads[kind], level), (kind, level)
+        s.configure(gpu.CFG_DEFLATE_BYTES, 1)
+        for level in (9, 13):
+            s.profile(True)
+            outs, res = s.deflate_batch(tens, level)
+            searches = s.profile_get(gpu.K_DFL_SEARCH)[1]
+            s.profile(False)
+            for i, (d, o, r) in enumerate(zip(datas, outs, res)):
+                assert r.status == gpu.DONE, (level, i, r.status)
+                assert bytes(o[:r.written].cpu().numpy()) == ph.orc_deflate(d, level), (level, i, r.written)
+            assert searches > 1, (level, searches)
     finally:
-        s.configure(gpu.CFG_DEFLATE_MODE, gpu.DEFLATE_AUTO)
+        s.profile(False)
+        s.configure(gpu.CFG_DEFLATE_BYTES, 0)
 
 
 def test_deflate_inserter_forms(gpu):

@@ -30,26 +30,6 @@ int main(int argc, char **argv)
     std::vector<uint8_t> dst(want.size() + 4096, 0xEE);
     src.resize(n + 64);                                          // (the kernels read keys a few bytes past positions they search)
 
-    if (level < 8 && getenv("EMU_ONE_KERNEL")) {
-        // levels 0-7, the one-kernel form (SPNG_DEFLATE_ONE_KERNEL): one wave per stream does everything
-        std::vector<uint32_t> ring(65536, 0);
-        DeflateJob j;
-        memset(&j, 0, sizeof j);
-        j.src = src.data(); j.dst = dst.data(); j.src_len = n; j.dst_cap = dst.size(); j.ring = ring.data();
-        j.format = format == 1 ? SPNG_FORMAT_IOS : SPNG_FORMAT_ZLIB; j.level = level; j.image = 0; j.exponent = 15;
-        spng_result r1;
-        memset(&r1, 0xff, sizeof r1);
-        emu::launch(1, 64, [&] { deflate_kernel(&j, &r1); });
-        if (r1.status != SPNG_DONE) { printf("status %d\n", r1.status); return 1; }
-        if (r1.written != want.size() || memcmp(dst.data(), want.data(), want.size())) {
-            size_t k = 0;
-            while (k < want.size() && k < r1.written && dst[k] == want[k]) ++k;
-            printf("stream differs: %llu bytes against %zu expected, first difference at %zu\n", (unsigned long long)r1.written, want.size(), k);
-            return 1;
-        }
-        printf("ok: %llu -> %llu bytes (greedy / lazy kernel)\n", (unsigned long long)n, (unsigned long long)r1.written);
-        return 0;
-    }
     if (level < 8) {
         // levels 0-7 in rounds: dfl3_begin -> (dfl3_search_fast + dfl3_advance, dfl3_parse) per round, the two sets of answers
         // alternating; `cut ...`: a call per piece with `more` set and the state kept, as spng_deflate_resume_batch drives it

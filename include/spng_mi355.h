@@ -147,7 +147,12 @@ enum { SPNG_CFG_INFLATE_MODE = 0,   /* SPNG_INFLATE_AUTO: parallel pipeline, ser
                                               memory.  Streams that do not fit side by side go in groups */
        SPNG_CFG_MULTI_GROUPS = 8,          /* spng_decode_batch_multi: calls a context's shard is cut into when its rasters leave for another
                                               device (a group's copies run beside the next group's decode); 0 = 2, at most 2 */
-       SPNG_CFG_COUNT = 9 };
+       SPNG_CFG_BLOCK_CUT_BYTES = 9,       /* parallel inflate, one-shot calls: a run of segments in which no block starts -- one huge block, or
+                                              blocks without a findable header (fixed codes) -- of at least so many compressed bytes (rounded up
+                                              to whole segments) is cut: every segment of it decoded by a wave of its own from a guessed bit
+                                              and joined to the chain afterwards.  0 = 1 MiB; SPNG_BLOCK_CUT_NEVER = never */
+       SPNG_CFG_COUNT = 10 };
+enum { SPNG_BLOCK_CUT_AUTO = 0, SPNG_BLOCK_CUT_NEVER = 1 };
 enum { SPNG_INFLATE_AUTO = 0, SPNG_INFLATE_SERIAL = 1 };
 enum { SPNG_OVERLAP_AUTO = 0, SPNG_OVERLAP_ALWAYS = 1, SPNG_OVERLAP_NEVER = 2 };
 int32_t spng_configure(spng_ctx *ctx, int key, int64_t value);
@@ -170,6 +175,9 @@ int32_t spng_profile_get(spng_ctx *ctx, int kernel, double *total_ms, uint64_t *
  * reads by design, rounded up to pages --, the DEFLATE blocks it decoded, and whether a pass found the pool empty.  No reference
  * counterpart (measurement: bench.py's per-kernel design bytes).  Any pointer may be NULL. */
 int32_t spng_token_stats(spng_ctx *ctx, uint64_t *page_bytes, uint64_t *blocks, int32_t *ran_dry);
+/* Block cuts of the most recent parallel-inflate call (read back behind its kernels; any pointer may be NULL): cut segments tried,
+ * cuts whose join to the chain was proven, streams that were decoded again without cuts because one of theirs was not. */
+int32_t spng_cut_stats(spng_ctx *ctx, uint64_t *tried, uint64_t *joined, uint64_t *streams_redone);
 
 /* ---- decode: device batch entry points (asynchronous on the context's stream) -------------- */
 /* replaces LZ77.Inflator.push/pull over whole streams: LZ77.Inflator.swift:30-61,

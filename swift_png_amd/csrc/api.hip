@@ -89,7 +89,8 @@ struct spng_ctx {
     // token pool of the pipeline (pinflate2.hip): halfwords a compressed byte turned into in the last batch (learned,
     // so that the next batch of the same kind takes one pass), and the pinned word the page counter is read back into
     double   pool_ratio = 0;
-    uint32_t *h_pool_used = nullptr;
+    uint32_t *h_pool_used = nullptr;                 // ([8 .. 10]: block cuts tried, joined, streams redone of the last call that could try any)
+    bool cut_stats_valid = false;                    // (the last parallel-inflate call could)
     uint64_t pool_pages_planned = 0, pool_src_bytes = 0, pool_src_pending = 0;   // (source bytes of the batch planned / of the one whose counters are on their way)
     double   block_bytes = 0;        // compressed bytes per DEFLATE block in the last batch (0: not known)
     hipEvent_t pool_ev = nullptr; bool pool_pending = false;
@@ -323,6 +324,19 @@ int32_t spng_token_stats(spng_ctx *c, uint64_t *page_bytes, uint64_t *blocks, in
     return SPNG_DONE;
 }
 
+int32_t spng_cut_stats(spng_ctx *c, uint64_t *tried, uint64_t *joined, uint64_t *streams_redone)
+{
+    if (!c) return SPNG_E_ARGUMENT;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t *h = c->h_pool_used && c->cut_stats_valid ? c->h_pool_used + 8 : nullptr;
+    if (tried) *tried = h ? h[0] : 0;
+    if (joined) *joined = h ? h[1] : 0;
+    if (streams_redone) *streams_redone = h ? h[2] : 0;
+    return SPNG_DONE;
+}
+
 int32_t spng_profile_get(spng_ctx *c, int kernel, double *total_ms, uint64_t *launches)
 {
     if (!c || kernel < 0 || kernel >= SPNG_K_COUNT) return SPNG_E_ARGUMENT;
@@ -547,11 +561,14 @@ struct InflatePlan {
     std::vector<uint64_t> state;     // {bit, written} per stream: spng_inflate_resume_batch's, else the library's own zeros
     bool internal = true;            // (the latter)
     size_t jobs_at = 0, streams_at = 0, segs_at = 0, done_at = 0, gz_at = 0, gzparts_at = 0, state_at = 0, sumparts_at = 0;
+    bool cuts = false;               // block cuts may be tried for some stream: a PCut per segment, device side only, behind everything
+    size_t cuts_at = 0;              // else in the arena (take_cuts)
+    size_t take_cuts(Arena &a) { if (cuts) cuts_at = a.take(segs.size() * sizeof(PCut)); return cuts_at; }
     size_t bytes() const
     {
         return jobs.size() * (sizeof(InflateJob) + sizeof(PStream) + 4 + (size_t)pmax * sizeof(PPart) + 256 + (gzip ? 8 + 4 * (size_t)gzip_pieces() : 0) +
                               (state.empty() ? 0 : 32 + 8 * (size_t)gzip_pieces())) +
-               segs.size() * sizeof(PSeg) + 8192 + 512;
+               segs.size() * (sizeof(PSeg) + (cuts ? sizeof(PCut) : 0)) + 8192 + 1024;
     }
 };
 
@@ -559,6 +576,7 @@ struct InflatePlan {
 #define SPNG_PARTS_MAX 128        // parts a stream's chain is cut into at most (round 5: 64 -- one to four images left half the chip idle)
 #endif
 static constexpr uint64_t RESUME_SERIAL_BITS = 8ull << 20;      // 1 MiB of input inside one block: resume there, not at its header
+                                                                // (and, one-shot calls: cut there -- SPNG_CFG_BLOCK_CUT_BYTES)
 
 // Cuts every stream into segments and makes sure the context owns what the pipeline needs.  Segment length: long
 // enough that the search for a block header (which costs more per bit than decoding) stays a small part of a
@@ -641,6 +659,16 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         if (k < 1) k = 1;
         if (p.segs.size() + k > 0x7fffffffu) return SPNG_E_ARGUMENT;
         st.seg_count = (uint32_t)k; st.seg_bytes = seg_bytes;
+        // block cuts (pinflate2.hip): one-shot calls only, and only a stream long enough to hold such a run of segments without a start
+        {
+            const int64_t cb = c->cfg[SPNG_CFG_BLOCK_CUT_BYTES];
+            const uint64_t cut_bytes = cb == 0 ? RESUME_SERIAL_BITS / 8 : (uint64_t)cb;
+            if (p.internal && cb != SPNG_BLOCK_CUT_NEVER && !st.start_bit && !st.serial_only && j.src_len >= cut_bytes) {
+                const uint64_t cs = (cut_bytes + seg_bytes - 1) / seg_bytes;
+                st.cut_segs = (uint32_t)(cs > 0x7fffffffu ? 0x7fffffffu : cs < 1 ? 1 : cs);
+                p.cuts = true;
+            }
+        }
         for (uint64_t q = 0; q < k; ++q) {
             PSeg sg;
             memset(&sg, 0, sizeof sg);
@@ -657,6 +685,11 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         uint64_t e = (uint64_t)(per_byte * (double)j.src_len);
         if (e > 2 * (j.dst_cap + 64)) e = 2 * (j.dst_cap + 64);
         est[i] = e + k * 65536 + 65536;                                            // (every segment ends inside a page)
+        // (block cuts: a cut segment's first chunks -- tokens nobody reads --, the padding of its records and its join's bridge take room
+        // too, and EVERY segment of the stream ends inside a page, not only those with a start: a second page per segment.
+        // Not for a stream whose like the last batch showed to be made of ordinary blocks: there nothing will be cut, and a batch of
+        // 1024 images would ask for 10 GiB it never touches.  A wrong guess costs the stream the retry pass, not its result.)
+        if (st.cut_segs && !(c->block_bytes > 0 && c->block_bytes < 262144)) est[i] += k * 65536;
     }
     log *= 4;
     p.log_bytes = log;
@@ -863,6 +896,7 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
             HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
             HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
         }
+        c->cut_stats_valid = false;
         for (size_t gi = 0; gi <= p.groups.size(); ++gi) {
             const bool retry = gi == p.groups.size();
             const InflatePlan::Group g = retry ? InflatePlan::Group{0, n, 0, (uint32_t)p.segs.size(), 0, p.pool_pages} : p.groups[gi];
@@ -877,11 +911,25 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
             if (gi && !second) HIP_TRY(hipMemsetAsync(ctr, 0, 4, q));
             { Timed t(c, SPNG_K_PINF_FIND, q); HIP_TRY(launch_pinf2_find(ds, dg, g.g0, g.g1 - g.g0, retry, q)); }
             if (second) HIP_TRY(hipStreamWaitEvent(q, c->ev_mid, 0));
+            // block cuts: only a group with a stream they may be tried for takes the kernels that know them (the plan in front of
+            // the decode, the join behind it, their instantiations of decode and scan); dnext[12 ..] = {tried, joined, streams redone}
+            bool cuts = false;
+            if (!retry) for (uint32_t i = g.s0; i < g.s1 && !cuts; ++i) cuts = p.streams[i].cut_segs != 0;
+            PCut *dc = p.cuts ? a.dev<PCut>(p.cuts_at) : nullptr;
+            if (cuts) {
+                c->cut_stats_valid = true;
+                Timed t(c, SPNG_K_PINF_DECODE, q);
+                HIP_TRY(hipMemsetAsync(dc + g.g0, 0, (size_t)(g.g1 - g.g0) * sizeof(PCut), q));
+                HIP_TRY(launch_pinf2_cutplan(ds + g.s0, g.s1 - g.s0, dg, dc, dnext + 12, q));
+                HIP_TRY(launch_pinf2_cutdecode(ds, dg, dc, g.g0, g.g1 - g.g0, (uint32_t *)c->d_log, pool, ctr, g.pages, q));
+                HIP_TRY(launch_pinf2_cutjoin(ds, dg, dc, g.g0, g.g1 - g.g0, (uint32_t *)c->d_log, pool, ctr, g.pages, dnext + 12, q));
+            } else
             { Timed t(c, SPNG_K_PINF_DECODE, q); HIP_TRY(launch_pinf2_decode(ds, dg, g.g0, g.g1 - g.g0, (uint32_t *)c->d_log, pool, ctr, g.pages, retry, q)); }
             if (p.overlap && gi == 0) HIP_TRY(hipEventRecord(c->ev_mid, q));
             PPart *dparts = p.pmax ? a.dev<PPart>(p.parts_at) + (size_t)g.s0 * p.pmax : nullptr;
             const uint32_t pm = retry ? 0u : p.pmax;                 // (the retry pass: one workgroup per stream)
-            HIP_TRY(launch_pinf2_scan(ds + g.s0, g.s1 - g.s0, dg, dparts, retry, q));
+            if (cuts) HIP_TRY(launch_pinf2_cutscan(ds + g.s0, g.s1 - g.s0, dg, dc, dparts, dnext + 12, q));
+            else HIP_TRY(launch_pinf2_scan(ds + g.s0, g.s1 - g.s0, dg, dparts, retry, q));
             {
                 Timed t(c, SPNG_K_PINF_RESOLVE, q);
                 // (the parts behind the first on the second stream, beside the first parts: 79 KB -- 93 KB when they have a CU each -- and 61 KB of LDS share a CU)
@@ -906,6 +954,7 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
             }
             HIP_TRY(launch_pinf2_account(ctr, dnext + 8, g.pages, q));
         }
+        if (c->cut_stats_valid) HIP_TRY(hipMemcpyAsync(c->h_pool_used + 8, dnext + 12, 12, hipMemcpyDeviceToHost, c->stream));
         if (!c->pool_pending) {
             // pages this batch took: read at the start of the next one (never waited for)
             HIP_TRY(hipMemcpyAsync(c->h_pool_used, dnext + 8, 16, hipMemcpyDeviceToHost, c->stream));
@@ -947,9 +996,11 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
                     (unsigned long long)st.ntok, (unsigned long long)st.end_bit);
             for (uint32_t k = 0; k < st.seg_count && k < 12; ++k) {
                 const PSeg &sg = hg[st.seg_first + k];
-                fprintf(stderr, "   seg %u: start %lld end %lld status %d used %u ntok %llu tok_base %llu\n", k,
+                fprintf(stderr, "   seg %u: start %lld end %lld status %d used %u ntok %llu tok_base %llu next %u", k,
                         (long long)sg.start_bit, (long long)sg.end_bit, sg.status, sg.used, (unsigned long long)sg.ntok,
-                        (unsigned long long)sg.tok_base);
+                        (unsigned long long)sg.tok_base, sg.next);
+                if (sg.head) fprintf(stderr, " head %u", sg.head);
+                fprintf(stderr, "\n");
             }
         }
     }
@@ -1010,6 +1061,7 @@ static int32_t inflate_batch(spng_ctx *c, const spng_stream_desc *descs, const u
     const size_t res = a.take(count * sizeof(spng_result));
     if (plan.gzip) { plan.gz_at = a.take(count * 8); plan.gzparts_at = a.take((size_t)count * 4 * gzip_pieces()); }
     plan.sumparts_at = a.take((size_t)count * 8 * gzip_pieces());
+    plan.take_cuts(a);
     if (int32_t st = c->upload(0, upload)) return st;
     spng_result *dr = d_results ? d_results : a.dev<spng_result>(res);
     poison_results_kernel<<<(count + 255) / 256, 256, 0, c->stream>>>(dr, count);
@@ -1203,6 +1255,7 @@ int32_t spng_decode_batch(spng_ctx *c, const spng_image_desc *descs, uint32_t co
     const size_t first = (res_bytes + 255) & ~(size_t)255;
     const size_t staged = a.off;
     ip.sumparts_at = a.take((size_t)count * 8 * gzip_pieces());
+    ip.take_cuts(a);
     if (int32_t st = c->upload(first, staged)) return st;
     poison_results_kernel<<<(count + 255) / 256, 256, 0, c->stream>>>(dr, count);
     HIP_TRY(hipGetLastError());

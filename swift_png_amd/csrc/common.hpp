@@ -155,13 +155,16 @@ struct PStream {
     // resumable streams (spng_inflate_resume_batch): where to start, and where to note how far the chain got
     uint64_t       start_bit, out_pos;
     uint64_t      *state;
-    uint32_t       serial_only, pad_;      // the caller's state stands deep inside a huge block: the serial kernel goes on THERE (the pipeline would decode the block again)
+    uint32_t       serial_only, cut_segs;  // cut_segs (host): block cuts are tried for runs of at least so many segments without a start (0: never).  serial_only: the caller's state stands deep inside a huge block: the serial kernel goes on THERE (the pipeline would decode the block again)
     // several workgroups per stream: parts_max slots in the part table (0: one workgroup), how many the chain was cut into
     uint32_t       parts_max, parts;
     uint64_t       out_total;              // scan: bytes of the whole chain
     uint64_t       sym_off;                // its 16-bit symbols in the symbol scratch (in symbols)
+    uint32_t       cut_on, pad_;           // plan (device side): some of its segments are cut
 };
-enum { PSEG_FAIL = 0, PSEG_CONT = 1, PSEG_FINAL = 2, PSEG_PARTIAL = 3, PSEG_NOPAGE = 4 };
+enum { PSEG_FAIL = 0, PSEG_CONT = 1, PSEG_FINAL = 2, PSEG_PARTIAL = 3, PSEG_NOPAGE = 4,
+       PSEG_CUT = 5 };                     // stopped INSIDE a block, in front of a cut segment (block cuts: pinflate2.hip)
+static constexpr uint32_t PCUT_RECS = 4;   // chunk ends a cut segment's wave records of its chain's head
 // One segment: the blocks that start in [index * seg_bytes, (index + 1) * seg_bytes).
 struct PSeg {
     uint32_t stream, index;
@@ -173,9 +176,23 @@ struct PSeg {
     uint64_t tok_base;                     // scan: first token, relative to the stream's
     int32_t  status;                       // count: PSEG_*
     uint32_t used;                         // scan: part of the chain
-    uint32_t next, pad;                    // count: index of the segment that starts where this one stopped
+    uint32_t next, head;                   // count: index of the segment that starts where this one stopped; scan: token halfwords at
+                                           // its front that are not on the chain (a multiple of 8; 0 in every segment that is not cut)
     uint64_t nbytes;                       // decode: bytes its tokens stand for
     uint64_t out_base;                     // scan: its first byte, counted from the stream's first byte of this call
+};
+// What block cuts (pinflate2.hip) keep per segment: a table beside the PSeg table, same index, device side only -- it exists, zeroed,
+// only in a batch in which cuts may be tried, so that every other batch stages and uploads what it always did.
+struct PCut {
+    uint32_t cut, anchor;                  // plan: decoded from a guessed bit with the tables of the block at segment `anchor`'s start
+    uint32_t nrec, joined;                 // decode: records below; join (PSEG_CUT): this segment's chain provably runs into segment `next`'s ...
+    uint32_t next_head, pad;               // ... behind that one's first next_head halfwords, which stand for next_sub bytes
+    uint64_t tbl, tbl_id;                  // decode, PSEG_CUT: the header of the block end_bit lies in, and which tables that makes (table_id)
+    uint64_t head_tbl;                     // decode, cut segments: the tables its records were decoded with
+    uint64_t add_tok, add_bytes;           // join: bridge tokens it appended behind ntok on the way there, their bytes
+    uint64_t next_sub;
+    struct { uint64_t bit; uint32_t hw, bytes; } rec[PCUT_RECS];   // decode: a chunk end of its first block: the token start there,
+                                                                   // halfwords (padded to 8) and bytes emitted in front of it
 };
 // A part of a stream's segment chain that one workgroup resolves (pinflate2.hip, "Several workgroups per stream").
 struct PPart {
@@ -286,6 +303,12 @@ hipError_t launch_pinf2_parts(PStream *d_streams, uint32_t nstreams, PSeg *d_seg
                               spng_result *d_results, int32_t *d_done, PPart *d_parts, uint32_t pmax, uint16_t *d_sym, hipStream_t stream);
 hipError_t launch_pinf2_join(PStream *d_streams, uint32_t nstreams, spng_result *d_results, int32_t *d_done, PPart *d_parts, uint32_t pmax,
                              uint16_t *d_sym, uint8_t *d_win, hipStream_t stream);
+hipError_t launch_pinf2_cutplan(PStream *d_streams, uint32_t nstreams, PSeg *d_segs, PCut *d_cuts, uint32_t *d_stats, hipStream_t stream);
+hipError_t launch_pinf2_cutdecode(PStream *d_streams, PSeg *d_segs, PCut *d_cuts, uint32_t seg0, uint32_t nsegs, uint32_t *d_pt, uint8_t *d_pool,
+                                  uint32_t *d_next, uint32_t pages, hipStream_t stream);
+hipError_t launch_pinf2_cutjoin(PStream *d_streams, PSeg *d_segs, PCut *d_cuts, uint32_t seg0, uint32_t nsegs, uint32_t *d_pt, uint8_t *d_pool,
+                                uint32_t *d_next, uint32_t pages, uint32_t *d_stats, hipStream_t stream);
+hipError_t launch_pinf2_cutscan(PStream *d_streams, uint32_t nstreams, PSeg *d_segs, PCut *d_cuts, PPart *d_parts, uint32_t *d_stats, hipStream_t stream);
 hipError_t launch_pinf2_account(uint32_t *d_ctr, uint32_t *d_totals, uint32_t pages, hipStream_t stream);
 // gzip.hip
 static constexpr uint64_t GZ_NONE = ~0ull;

@@ -125,8 +125,10 @@ struct DPool { uint8_t *base; uint32_t *next; uint32_t pages, pad; };   // next[
 // Emulator builds can count how often the rare paths of the decode rounds ran (tests/test_emu_pinflate.py asserts that its cases
 // reach every one of them): COV(k) is nothing in the product.
 #if defined(SPNG_EMU) && defined(SPNG_EMU_COV)
-static long g_cov[8];      // 0 reference on a subsequence's last bit, 1 reference on a word's last bit, 2 chunks with marks for references,
+static long g_cov[12];     // 0 reference on a subsequence's last bit, 1 reference on a word's last bit, 2 chunks with marks for references,
                            // 3 chunks with kind masks, 4 pairs cut at a subsequence's end, 5 round-1 landings on a reference's second mark
+                           // block cuts: 6 a guess slid on after a bogus end of block or an undefined code, 7 a join decoded more than one
+                           // chunk, 8 a stream sent to the retry pass
 #define COV(k) __atomic_fetch_add(&g_cov[k], 1, __ATOMIC_RELAXED)
 #else
 #define COV(k) ((void)0)
@@ -831,10 +833,14 @@ __device__ __forceinline__ void advance_tokens(Cursor &c, uint32_t count, g8 *pb
 // front of it (two neighbouring marks can only be a back-reference).  A back-reference on the last bit of a subsequence has
 // no bit behind it to mark: `edge`.  !RM (a code of one bit exists: neighbouring marks may be two tokens): the kinds of a
 // lane's tokens by ordinal in two 64-bit masks, as rounds 1-4 did it.
-template <bool PAIRS, bool RM>
+//
+// CLAMP (block cuts): the chunk ends at absolute bit `stop` (cb < stop <= cb + the chunk's bits) and ends EXACTLY: `next` is the first
+// token start of the chain at or behind `stop` -- a pair of literals whose second one starts there is cut to its first -- so that
+// two waves that decode the same chain on different chunk grids leave a chunk that ends at the same bit at the same token.
+template <bool PAIRS, bool RM, bool CLAMP = false>
 __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_t n, uint64_t cb,
                                                  uint64_t entry, uint32_t sdw, const DPool &pool, g32 *pt, uint32_t pt_cap, Cursor &cur,
-                                                 uint64_t &next, uint64_t &nbytes, int lane DP_ARG)
+                                                 uint64_t &next, uint64_t &nbytes, uint64_t stop, int lane DP_ARG)
 {
     DP(0);
     const uint32_t sb = sdw * 32, chb = sb * 64;
@@ -844,8 +850,9 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
     const uint64_t left = n * 8 - sbit;
     // (positions inside the chunk: bits from sbit, + QB)
     const uint32_t lim = left > 0xffffffffull - QB ? 0xffffffffu : (uint32_t)left + QB;
-    const uint32_t off0 = (uint32_t)(cb - sbit) + QB, cend = off0 + chb;
+    const uint32_t off0 = (uint32_t)(cb - sbit) + QB, cend = CLAMP ? (uint32_t)(stop - sbit) + QB : off0 + chb;
     const uint32_t sub0 = off0 + (uint32_t)lane * sb, sub1 = sub0 + sb;
+    const uint32_t r0end = CLAMP ? (sub1 < cend ? sub1 : cend) : sub1;      // where round 0 of this lane ends
 #pragma unroll
     for (int w = 0; w < SDW_MAX; ++w) s.c.vmap[w * 64 + lane] = 0;
     s.c.flag[lane] = 0;
@@ -859,7 +866,7 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
     uint64_t mb0 = 0, mb1 = 0;                                  // !RM: which of my tokens (by ordinal) are back-references
     uint32_t ntk = 0, edge = 0;
     uint32_t qx = 0;
-    while (q < sub1) {
+    while (q < r0end) {
         DPN(16, 1);
         uint32_t k, len0;
         uint32_t nb = decode_at2<false, PAIRS>(s, q, k, len0, d0, d1);
@@ -883,7 +890,7 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
         }
         if (PAIRS && k == C_LIT2) {                             // two literals in one step: two tokens, two marks
             const uint32_t b2 = b + len0;                       // (the second one may belong to the next subsequence: not mine)
-            if (b2 < sb) {
+            if (b2 < (CLAMP ? r0end - sub0 : sb)) {
                 atomicOr(&s.c.vmap[(b2 >> 5) * 64 + lane], 1u << (b2 & 31));
                 if (!RM) ntk += 1;
             } else { nb = len0; COV(4); }
@@ -920,6 +927,7 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
             if (RM && ((mword & front) >> (b & 31)) & 1) COV(5);
             if (((mword & ~front) >> (b & 31)) & 1) { link = j; qx = q; q = 0xffffffffu; continue; }
             if (RARE((k & 1) != 0)) { st = k == D2_EOB ? 1u : 2u; qx = k == D2_EOB ? q + nb : q; q = 0xffffffffu; continue; }
+            if (CLAMP && PAIRS && k == C_LIT2 && q + len0 >= cend) { cnt2 += 1; q += len0; continue; }      // (a pair across the clamp: its first literal)
             cnt2 += 1 + (PAIRS ? (k >> 1) & 1 : k >> 1);
             q += nb;
         }
@@ -1045,22 +1053,72 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
     return ste;
 }
 
+// ---- block cuts ---------------------------------------------------------------------------------------------
+// A segment in which find saw no start (an ORPHAN) lies inside a block -- or a run of blocks without a findable header -- that began
+// in an earlier segment, the nearest one with a start: its ANCHOR.  Where such a run is long (PStream.cut_segs: 1 MiB of input by
+// default; never in a stream that may be resumed) pinf2_cutplan_kernel marks its segments as CUT, and the instantiation
+// pinf2_cutdecode_kernel<2> gives each a wave of its own: it builds the tables of the anchor's block and decodes from a GUESSED
+// bit, its nominal start, as lanes 1-63 of a chunk do.  The tokens of its first chunk are never on the chain: the chunk serves to
+// synchronise (an end-of-block or an undefined code there: the guess slides on by a chunk).  Of its first PCUT_RECS chunks that end
+// inside the block -- the synchronising one is the first of them -- it records where they end: (token start, halfwords and bytes
+// emitted so far).  The wave in FRONT of a cut segment j stops inside the block (PSEG_CUT), at the first token at
+// or behind j's nominal start + one chunk -- with the same tables that is where j's first chunk ends, and when j's chain had merged
+// into the true one by then the two positions are the same bit.  pinf2_cutjoin_kernel, one wave per cut, decodes from that stop to
+// j's next record until the positions coincide with the same tables in force (usually at once: nothing to decode), appends those
+// bridge tokens to the segment in front and tells j how many of its own to skip (PSeg.head).  Scan takes a cut segment on the chain
+// only with its join proven, and a stream whose chain met a cut but did not reach its final block by proven joins takes the retry
+// pass, which knows no cuts: what today's pipeline does with it.
+//
+// Which tables: a dynamic block's are its header's bit; all fixed blocks share theirs, but not what follows their end.
+static constexpr uint64_t TBL_FIXED = 1ull << 63, TBL_FINAL = 1ull << 62;
+__device__ __forceinline__ uint64_t table_id(const Hdr2 &h, uint64_t pos) { return h.type == 1 ? TBL_FIXED | (h.bfinal ? TBL_FINAL : 0) : pos; }
+static constexpr uint32_t CUT_SLIDES = 16;             // chunks a guess slides on at most
+static constexpr uint32_t CUT_JOIN_CHUNKS = 20;        // chunks a join decodes at most
+// a clamped chunk of whichever kind the block's tables ask for
+template <bool CLAMP>
+__device__ __forceinline__ uint32_t cut_chunk(DLds &s, const Hdr2 &h, const g8 *src, uint64_t n, uint64_t cb, uint64_t entry, uint32_t sdw, const DPool &pool,
+                                              g32 *pt, uint32_t pt_cap, Cursor &cur, uint64_t &next, uint64_t &nbytes, uint64_t stop, int lane)
+{
+#ifdef SPNG_D_PROF
+    uint64_t dpv[32], *dp = dpv;
+    for (int i = 0; i < 32; ++i) dp[i] = 0;
+#endif
+    if (h.minlen >= 2)
+        return h.pairs ? UNI((decode_chunk<true, true, CLAMP>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, stop, lane DP_PASS)))
+                       : UNI((decode_chunk<false, true, CLAMP>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, stop, lane DP_PASS)));
+    return h.pairs ? UNI((decode_chunk<true, false, CLAMP>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, stop, lane DP_PASS)))
+                   : UNI((decode_chunk<false, false, CLAMP>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, stop, lane DP_PASS)));
+}
+__device__ __forceinline__ uint32_t chunk_dwords(uint32_t minlen)
+{
+    uint32_t big = minlen >= 5 ? 17u : minlen == 4 ? 15u : minlen == 3 ? 11u : minlen == 2 ? 7u : 3u;
+    return big > (uint32_t)SDW_MAX ? (uint32_t)SDW_MAX : big;
+}
+
 #ifndef SPNG_D_WAVES
 #define SPNG_D_WAVES 4
 #endif
-template <uint32_t RETRY>
-__global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PStream *__restrict__ streams, PSeg *__restrict__ segs,
-                                                          uint32_t *__restrict__ pt_slab, DPool pool, uint32_t seg0)
+// WHICH: 0 = every stream, no cuts (a batch in which none can be tried, and the retry pass); a batch in which some may be tried is
+// launched twice: 1 = the streams in which the plan cut nothing, through the same code as 0, 2 = the streams with cut segments.
+template <uint32_t RETRY, int WHICH>
+__device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restrict__ streams, PSeg *__restrict__ segs,
+                                               uint32_t *__restrict__ pt_slab, const DPool &pool, uint32_t seg0, PCut *__restrict__ cuts)
 {
+    constexpr bool CUT = WHICH == 2;
     constexpr uint32_t retry = RETRY;
     // (segs = the whole table -- a stream's seg_first counts from its beginning; this launch's segments start at seg0)
-    __shared__ __attribute__((aligned(16))) DLds s;
     const int lane = threadIdx.x;
     PSeg &sg = segs[seg0 + blockIdx.x];
     const PStream &st = streams[UNI(sg.stream)];
     if (retry && UNI(st.pass) != 1) return;
+    if (WHICH && (UNI(st.cut_on) != 0) != CUT) return;
     const uint64_t start = uni64(sg.start_bit);
-    if (start == NONE2) return;
+    bool mid = false;                                          // CUT: a cut segment's wave in the block it was started inside of
+    if (start == NONE2) {
+        if constexpr (!CUT) return;
+        else if (!UNI(cuts[seg0 + blockIdx.x].cut)) return;
+        mid = true;
+    }
     const g8 *src = (const g8 *)uni64((uint64_t)st.src);
     const uint64_t n = uni64(st.src_len);
     // this segment ends where a later one begins: at the first found start it stops ON.  One it runs past
@@ -1076,7 +1134,9 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
             if (v != NONE2 && v >= from) { limit = v; break; }
         }
     };
-    advance(start + 1);
+    const uint64_t segbits = CUT ? uni64(st.seg_bytes) * 8 : 0;
+    uint64_t guess = CUT ? (uint64_t)UNI(sg.index) * segbits : 0;      // a cut segment: where its chain starts
+    advance(CUT && mid ? guess + 1 : start + 1);
     // the page table: my own entries and those of the segments behind me in which no start was found (nobody else
     // writes there; a stream whose stored or fixed blocks hide every later start needs them)
     g32 *pt = (g32 *)(pt_slab + uni64(sg.log_off));
@@ -1087,6 +1147,14 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
         const uint64_t room = end - uni64(sg.log_off);
         pt_cap = room > 0xffffff00ull ? 0xffffff00u : (uint32_t)room;
     }
+    uint32_t tgt = UNI(sg.index) + 1;                          // CUT: the cut segment this wave stops in front of
+    if (CUT && tgt < seg_count && UNI(cuts[seg_first + tgt].cut)) {      // (the segment behind me has a wave, and a page table, of its own)
+        const uint64_t room = uni64(sg.log_cap);
+        pt_cap = room > 0xffffff00ull ? 0xffffff00u : (uint32_t)room;
+    }
+    uint32_t nrec = 0, slides = 0;
+    bool fresh = true, stopped = false;
+    uint64_t tbl = 0, tbl_id = 0, head_tbl = 0;
     Cursor cur;
     cur.nhw = 0; cur.npages = 0; cur.pa = nullptr; cur.dry = false;
     uint64_t pos = start;
@@ -1103,8 +1171,9 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
     dp[31] = __builtin_readcyclecounter();
     const uint64_t dp_t0 = dp[31];
 #endif
+    if (CUT && mid) pos = uni64(segs[seg_first + UNI(cuts[seg0 + blockIdx.x].anchor)].start_bit);      // (the header of the anchor's block)
     for (;;) {
-        if (pos >= limit) {
+        if (!(CUT && mid) && pos >= limit) {
             if (pos == limit) { status = PSEG_CONT; break; }
             nk += 1; advance(pos);
             continue;
@@ -1119,6 +1188,7 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
         if (!hok_ && lane == 0) fprintf(stderr, "header at bit %llu rejected\n", (unsigned long long)pos);
 #endif
         if (!hok_) break;
+        if (CUT && mid && h.type == 0) break;                    // (the plan saw a Huffman block there)
         if (h.type == 0) {
             // stored bytes are literal tokens
             const uint64_t from = h.payload / 8;
@@ -1136,6 +1206,56 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
             }
             if (!ok) break;
             pos = h.payload + (uint64_t)h.stored * 8;
+        } else if constexpr (CUT) {
+            const uint32_t sdw = chunk_dwords(h.minlen);
+            const uint64_t chb = (uint64_t)sdw * 32 * 64;
+            const uint64_t id = table_id(h, pos);
+            if (mid) head_tbl = id;
+            uint64_t entry = mid ? guess : h.payload, cb = entry;
+            uint32_t state = 0;
+            for (;;) {
+                // the cut segment to stop in front of: the first whose stop bit -- its nominal start + a chunk -- lies behind this chunk's first
+                uint64_t stop_at = NONE2;
+                for (; tgt < seg_count && UNI(cuts[seg_first + tgt].cut); ++tgt) {
+                    const uint64_t v = (uint64_t)tgt * segbits + chb;
+                    if (v > cb) { stop_at = v; break; }
+                }
+                const bool last = stop_at != NONE2 && cb + chb >= stop_at;
+                uint64_t next;
+                if (last || (mid && nrec < PCUT_RECS))
+                    state = cut_chunk<true>(s, h, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, last ? stop_at : cb + chb, lane);
+                else
+                    state = cut_chunk<false>(s, h, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, 0, lane);
+                entry = uni64(next);
+                if (mid && fresh && state) {
+                    // not synchronised yet, and a bogus end of block or an undefined code: the guess slides on to the next chunk
+                    if (cur.dry || ++slides > CUT_SLIDES || cb + chb >= n * 8) { state = 2; break; }
+                    COV(6);
+                    guess = cb + chb; entry = cb = guess;
+                    continue;
+                }
+                fresh = false;
+                if (mid && nrec < PCUT_RECS && !state) {
+                    // a record: the halfwords so far padded to a whole unit, so that resolve can start behind them
+                    const uint32_t padn = (8 - (uint32_t)(cur.nhw & 7)) & 7;
+                    g8 *pb;
+                    if (!UB(reserve_tokens(pool, pt, pt_cap, cur, padn, pb, lane))) { state = 2; break; }
+                    if (padn) {
+                        const uint32_t r0 = (uint32_t)(cur.nhw & (PAGE_HW - 1));
+                        if ((uint32_t)lane < padn) *token_at(cur.pa, pb, r0 + (uint32_t)lane) = (uint16_t)TK_NULL;
+                        advance_tokens(cur, padn, pb);
+                    }
+                    if (lane == 0) { PCut &ct = cuts[seg0 + blockIdx.x]; ct.rec[nrec].bit = entry; ct.rec[nrec].hw = (uint32_t)cur.nhw; ct.rec[nrec].bytes = (uint32_t)nbytes; }
+                    nrec += 1;
+                }
+                if (last && !state) { stopped = true; break; }
+                if (state) break;
+                cb += chb;
+            }
+            if (stopped) { status = PSEG_CUT; tbl = pos; tbl_id = id; pos = entry; break; }
+            if (state != 1) break;
+            pos = entry;
+            mid = false;
         } else {
             // subsequence length: at most 128 tokens may start in one (their kinds are kept in two 64-bit masks), and
             // no token may jump a whole subsequence (it is at most 48 bits long)
@@ -1150,11 +1270,11 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
                 uint64_t next;
                 // (two instances of the loops: without pairs in the table a step skips their bookkeeping)
                 if (h.minlen >= 2)
-                    state = h.pairs ? UNI((decode_chunk<true, true>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, lane DP_PASS)))
-                                    : UNI((decode_chunk<false, true>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, lane DP_PASS)));
+                    state = h.pairs ? UNI((decode_chunk<true, true>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, 0, lane DP_PASS)))
+                                    : UNI((decode_chunk<false, true>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, 0, lane DP_PASS)));
                 else
-                    state = h.pairs ? UNI((decode_chunk<true, false>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, lane DP_PASS)))
-                                    : UNI((decode_chunk<false, false>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, lane DP_PASS)));
+                    state = h.pairs ? UNI((decode_chunk<true, false>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, 0, lane DP_PASS)))
+                                    : UNI((decode_chunk<false, false>(s, src, n, cb, entry, sdw, pool, pt, pt_cap, cur, next, nbytes, 0, lane DP_PASS)));
                 entry = uni64(next);
                 if (state) break;
                 cb += (uint64_t)sdw * 32 * 64;
@@ -1171,15 +1291,190 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
     // The pool ran dry (a batch unlike the one it was sized by): the stream takes the retry pass, with the pool to itself and
     // its like; dry again there, it stops in front of this block like any other block that cannot be taken.
     if (status == PSEG_FAIL && cur.dry && !retry) status = PSEG_NOPAGE;
-    else if (status == PSEG_FAIL && resumable) { status = PSEG_PARTIAL; nhw = hw_block; nbytes = bytes_block; }   // (pos is still the block's first bit)
+    else if (status == PSEG_FAIL && resumable && !(CUT && mid)) { status = PSEG_PARTIAL; nhw = hw_block; nbytes = bytes_block; }   // (pos is still the block's first bit)
+    // (a cut segment that fails inside the block it was started in has no block boundary to stop at: FAIL, and scan sends the stream to the retry pass)
     // (no padding: resolve reads whole 16-byte units, inside the last page, and masks what lies behind nhw)
-    if (lane == 0) { sg.end_bit = pos; sg.ntok = nhw; sg.nbytes = nbytes; sg.status = status; sg.next = nk; }
+    if (lane == 0) { sg.end_bit = pos; sg.ntok = nhw; sg.nbytes = nbytes; sg.status = status; sg.next = CUT && stopped ? tgt : nk; }
+    // (the retry pass: a first pass with cuts may have told this segment to skip tokens -- scan writes `head` before it knows that the
+    // stream is redone --; these are new tokens, all of them on the chain)
+    if (retry && lane == 0) sg.head = 0;
+    if (CUT && lane == 0) { PCut &ct = cuts[seg0 + blockIdx.x]; ct.tbl = tbl; ct.tbl_id = tbl_id; ct.nrec = nrec; ct.head_tbl = head_tbl; }
 #ifdef SPNG_D_PROF
     if (blockIdx.x == 1 && lane == 0)
         printf("decode: %lu blocks %lu chunks %lu halfwords %lu windows; lane-0 steps r0 %lu r1 %lu replay %lu; cycles: total %lu stage %lu setup %lu round0 %lu "
                "round1 %lu path %lu replay %lu flush %lu header %lu (stage %lu clut %lu lengths %lu tables %lu) other %lu\n",
                dp[23], dp[20], dp[21], dp[22], dp[16], dp[17], dp[18], __builtin_readcyclecounter() - dp_t0, dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], dp[8] + dp[24] + dp[25] + dp[26] + dp[27], dp[24], dp[25], dp[26], dp[27], dp[7]);
 #endif
+}
+
+template <uint32_t RETRY>
+__global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PStream *__restrict__ streams, PSeg *__restrict__ segs,
+                                                          uint32_t *__restrict__ pt_slab, DPool pool, uint32_t seg0)
+{
+    __shared__ __attribute__((aligned(16))) DLds s;
+    decode_segment<RETRY, 0>(s, streams, segs, pt_slab, pool, seg0, nullptr);
+}
+// (a kernel of its own name: in traces, and in tests/test_codegen.py, pinf2_decode_kernel is the one every batch without cuts takes)
+template <int WHICH>
+__global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_cutdecode_kernel(const PStream *__restrict__ streams, PSeg *__restrict__ segs,
+                                                             uint32_t *__restrict__ pt_slab, DPool pool, uint32_t seg0, PCut *__restrict__ cuts)
+{
+    __shared__ __attribute__((aligned(16))) DLds s;
+    decode_segment<0, WHICH>(s, streams, segs, pt_slab, pool, seg0, cuts);
+}
+
+// Block cuts, the plan (one wave per stream, between find and decode): every segment without a start learns its anchor, and the
+// runs of such segments that are long enough and lie behind a Huffman block's header are marked as cut.  stats[0] += cuts tried.
+__global__ __launch_bounds__(64) void pinf2_cutplan_kernel(PStream *__restrict__ streams, PSeg *__restrict__ segs, PCut *__restrict__ cuts, uint32_t *__restrict__ stats)
+{
+    __shared__ __attribute__((aligned(16))) DLds s;
+    const int lane = threadIdx.x;
+    PStream &st = streams[blockIdx.x];
+    const uint32_t need = UNI(st.cut_segs);
+    if (!need || UNI(st.serial_only) || uni64(st.start_bit)) return;
+    const uint32_t first = UNI(st.seg_first), count = UNI(st.seg_count);
+    const g8 *src = (const g8 *)uni64((uint64_t)st.src);
+    const uint64_t n = uni64(st.src_len), sb = uni64(st.seg_bytes);
+    // A start that find saw behind a run long enough to be cut is more often a look-alike inside the huge block than a block's header
+    // (compressed data is full of bit patterns that parse): it is kept only if the bits in front of it are the end-of-block code of the
+    // block the run lies in, as far as this kernel can tell -- that of the segment with a start in front of the run (a code of at
+    // most LB bits).  A start dropped here is a segment without one to everybody behind this kernel, as if find had not seen it.
+    {
+        uint32_t prev = ~0u;                                   // the last start kept
+        for (uint32_t base = 0; base < count; base += 64) {
+            const uint32_t i = base + (uint32_t)lane;
+            unsigned long long mask = __ballot(i < count && segs[first + i].start_bit != NONE2);
+            while (mask) {
+                const uint32_t f = base + (uint32_t)__ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                bool keep = true;
+                if (prev != ~0u && f - prev - 1 >= need) {
+                    const uint64_t at = uni64(segs[first + f].start_bit);
+                    Hdr2 h;
+                    if (UB(parse_header2(s, src, n, uni64(segs[first + prev].start_bit), h, lane)) && h.type != 0) {
+                        uint32_t len = 0, code = 0;
+                        for (uint32_t k = 0; k < (1u << LB) / 64; ++k) {
+                            const uint32_t idx = k * 64 + (uint32_t)lane, e = s.lit[idx];
+                            const unsigned long long m = __ballot(((e >> 5) & 7) == C_EOB);
+                            if (m && !len) {
+                                const int l = __ffsll((long long)m) - 1;
+                                len = (uint32_t)__shfl((int)((e >> 8) & 15), l, 64);
+                                code = (k * 64 + (uint32_t)l) & ((1u << len) - 1);
+                            }
+                        }
+                        if (len && at >= len) {
+                            const uint64_t b = at - len;
+                            uint32_t v = 0;
+                            for (uint32_t k = 0; k < 3; ++k) if ((b >> 3) + k < n) v |= (uint32_t)src[(b >> 3) + k] << (8 * k);
+                            keep = ((v >> (b & 7)) & ((1u << len) - 1)) == code;
+                        }
+                    }
+                }
+                if (keep) prev = f;
+                else if (lane == 0) segs[first + f].start_bit = NONE2;
+            }
+        }
+        __threadfence();
+    }
+    uint32_t carry = ~0u;                                      // the last segment with a start so far
+    for (uint32_t base = 0; base < count; base += 64) {
+        const uint32_t i = base + (uint32_t)lane;
+        const bool has = i < count && segs[first + i].start_bit != NONE2;
+        const unsigned long long mask = __ballot(has);
+        const unsigned long long low = mask & ((2ull << lane) - 1);
+        if (i < count) cuts[first + i].anchor = low ? base + 63 - (uint32_t)__clzll((long long)low) : carry;
+        if (mask) carry = base + 63 - (uint32_t)__clzll((long long)mask);
+    }
+    uint32_t nxt = count, tried = 0;                           // the first segment with a start behind the ones at hand
+    for (uint32_t base = (count - 1) & ~63u;; base -= 64) {
+        const uint32_t i = base + (uint32_t)lane;
+        const bool has = i < count && segs[first + i].start_bit != NONE2;
+        const unsigned long long mask = __ballot(has);
+        const unsigned long long high = mask >> lane;
+        const uint32_t nf = high ? i + (uint32_t)__ffsll((long long)high) - 1 : nxt;
+        bool cut = false;
+        if (i < count && !has) {
+            const uint32_t a = cuts[first + i].anchor;
+            if (a != ~0u) {
+                const uint64_t lo = (uint64_t)(a + 1) * sb, hi = (uint64_t)nf * sb < n ? (uint64_t)nf * sb : n;
+                const uint64_t b = segs[first + a].start_bit;
+                if (hi > lo && hi - lo >= (uint64_t)need * sb && b + 3 <= n * 8) {
+                    const uint32_t v = (uint32_t)src[b >> 3] | ((b >> 3) + 1 < n ? (uint32_t)src[(b >> 3) + 1] << 8 : 0u);
+                    const uint32_t type = (v >> ((b & 7) + 1)) & 3;
+                    cut = type == 1 || type == 2;
+                }
+            }
+            cuts[first + i].cut = cut ? 1u : 0u;
+        }
+        tried += (uint32_t)__popcll(__ballot(cut));
+        if (mask) nxt = base + (uint32_t)__ffsll((long long)mask) - 1;
+        if (base == 0) break;
+    }
+    if (lane == 0 && tried) { atomicAdd(stats, tried); st.cut_on = 1; }
+}
+
+// Block cuts, the join (one wave per segment, between decode and scan; every wave but that of a segment that stopped in front of a
+// cut one returns at once): see "block cuts" above.  What it finds is kept with the segment in FRONT of the cut -- several waves
+// may have stopped in front of the same cut segment (a guess that slid over a short segment), scan knows which of them is on the
+// chain.  stats[1] += joins proven.
+__global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_cutjoin_kernel(const PStream *__restrict__ streams, PSeg *__restrict__ segs,
+                                                                        PCut *__restrict__ cuts, uint32_t *__restrict__ pt_slab, DPool pool, uint32_t seg0,
+                                                                        uint32_t *__restrict__ stats)
+{
+    __shared__ __attribute__((aligned(16))) DLds s;
+    const int lane = threadIdx.x;
+    const PSeg &pd = segs[seg0 + blockIdx.x];
+    PCut &pc = cuts[seg0 + blockIdx.x];
+    if ((int32_t)UNI(pd.status) != PSEG_CUT) return;
+    const PStream &st = streams[UNI(pd.stream)];
+    const uint32_t j = UNI(pd.next);
+    if (j <= UNI(pd.index) || j >= UNI(st.seg_count)) return;
+    const PCut &sg = cuts[UNI(st.seg_first) + j];
+    const uint32_t nrec = UNI(sg.nrec);
+    if (!UNI(sg.cut) || !nrec) return;
+    const g8 *src = (const g8 *)uni64((uint64_t)st.src);
+    const uint64_t n = uni64(st.src_len);
+    const uint64_t want = uni64(sg.head_tbl);
+    uint64_t pos = uni64(pd.end_bit), id = uni64(pc.tbl_id);
+    // the tokens go on behind the last one of this segment
+    g32 *pt = (g32 *)(pt_slab + uni64(pd.log_off));
+    const uint32_t pt_cap = uni64(pd.log_cap) > 0xffffff00ull ? 0xffffff00u : (uint32_t)uni64(pd.log_cap);
+    Cursor cur;
+    cur.nhw = uni64(pd.ntok); cur.npages = (uint32_t)((cur.nhw + PAGE_HW - 1) >> (PAGE_SHIFT - 1)); cur.dry = false;
+    cur.pa = (cur.nhw & (PAGE_HW - 1)) ? (g8 *)(pool.base + ((uint64_t)UNI(pt[cur.nhw >> (PAGE_SHIFT - 1)]) << PAGE_SHIFT)) : nullptr;
+    const uint64_t hw0 = cur.nhw;
+    uint64_t nbytes = 0;
+    uint32_t c = 0, chunks = 0;
+    bool mid = true, have = false, ok = false;
+    Hdr2 h;
+    for (uint32_t steps = 0; steps < 4 * CUT_JOIN_CHUNKS; ++steps) {
+        while (c < nrec && uni64(sg.rec[c].bit) < pos) ++c;
+        if (c == nrec) break;
+        if (mid && uni64(sg.rec[c].bit) == pos) { ok = id == want; break; }      // (the same bit with other tables in force: no join)
+        if (chunks == CUT_JOIN_CHUNKS) break;
+        if (!have || !mid) {
+            // the tables: of the block the stop lies in, or of the block that starts here
+            const uint64_t at = mid ? uni64(pc.tbl) : pos;
+            if (!UB(parse_header2(s, src, n, at, h, lane)) || h.type == 0) break;
+            have = true;
+            if (!mid) { id = table_id(h, pos); pos = h.payload; mid = true; continue; }
+        }
+        const uint32_t sdw = chunk_dwords(h.minlen);
+        const uint64_t chb = (uint64_t)sdw * 32 * 64, upto = uni64(sg.rec[c].bit);
+        uint64_t next;
+        const uint32_t state = cut_chunk<true>(s, h, src, n, pos, pos, sdw, pool, pt, pt_cap, cur, next, nbytes, upto - pos < chb ? upto : pos + chb, lane);
+        chunks += 1;
+        if (state == 2) break;
+        pos = uni64(next);
+        if (state == 1) { if (h.bfinal) break; mid = false; }
+    }
+    if (!ok) return;
+    if (chunks > 1) COV(7);
+    if (lane == 0) {
+        pc.add_tok = cur.nhw - hw0; pc.add_bytes = nbytes;
+        pc.next_head = UNI(sg.rec[c].hw); pc.next_sub = UNI(sg.rec[c].bytes); pc.joined = 1;
+        atomicAdd(stats + 1, 1u);
+    }
 }
 
 // ---- scan: the segment chain of every stream -----------------------------------------------------------------
@@ -1192,8 +1487,13 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_decode_kernel(const PS
 // the first does not know the 32 KiB in front of it and resolves to 16-bit SYMBOLS -- a byte, or a marker "byte o of the
 // window in front of this part" -- which a second, memory-bound pass turns into bytes once the windows are known
 // (pinf2_resolve_kernel<_, true>, pinf2_window_kernel, pinf2_fixup_kernel, pinf2_verdict_kernel).
-template <uint32_t RETRY>
-__global__ __launch_bounds__(64) void pinf2_scan_kernel(PStream *__restrict__ streams, PSeg *__restrict__ segs, PPart *__restrict__ parts)
+//
+// CUT (block cuts): a segment that stopped in front of a cut one (PSEG_CUT) hands on to it only if that one's join was proven,
+// from THIS segment; the bridge tokens the join appended and the head it told the cut segment to skip are put into the segments'
+// counts here.  A chain that met a cut and did not reach its final block: the retry pass (stats[2] += 1).
+template <uint32_t RETRY, bool CUT>
+__device__ __forceinline__ void scan_stream(PStream *__restrict__ streams, PSeg *__restrict__ segs, PPart *__restrict__ parts, uint32_t *__restrict__ stats,
+                                            const PCut *__restrict__ cuts)
 {
     constexpr uint32_t retry = RETRY;
     const int lane = threadIdx.x;
@@ -1206,21 +1506,48 @@ __global__ __launch_bounds__(64) void pinf2_scan_kernel(PStream *__restrict__ st
     bool ok = false, partial = false, dry = false;
     uint64_t tok = 0, end_bit = 0, out = 0;
     uint32_t k = 0;
+    bool met_cut = false, by_cut = false;                         // CUT: the chain met a cut; this segment was reached through one ...
+    uint32_t skip_hw = 0; uint64_t skip_bytes = 0;             // ... and its first tokens are not on the chain
     for (uint32_t hops = 0; hops < count; ++hops) {
         PSeg *sg = segs + first + k;
         const uint64_t start = uni64(sg->start_bit), end = uni64(sg->end_bit);
         const int32_t status = (int32_t)UNI(sg->status);
-        if (status == PSEG_NOPAGE && start != NONE2) dry = true;
-        if (start == NONE2 || status == PSEG_FAIL || status == PSEG_NOPAGE) break;
+        if (status == PSEG_NOPAGE && (start != NONE2 || (CUT && by_cut))) dry = true;
+        if ((start == NONE2 && !(CUT && by_cut)) || status == PSEG_FAIL || status == PSEG_NOPAGE) break;
+        if constexpr (CUT) {
+            uint64_t nt = uni64(sg->ntok), nb = uni64(sg->nbytes);
+            const uint32_t hd = by_cut ? skip_hw : 0u;
+            if (by_cut) nb -= skip_bytes;
+            uint32_t nx = 0;
+            if (status == PSEG_CUT) {
+                met_cut = true;
+                nx = UNI(sg->next);
+                const PCut &ct = cuts[first + k];
+                if (nx <= k || nx >= count || !UNI(cuts[first + nx].cut) || !UNI(ct.joined)) break;
+                nt += uni64(ct.add_tok); nb += uni64(ct.add_bytes);
+                skip_hw = UNI(ct.next_head); skip_bytes = uni64(ct.next_sub);
+            }
+            if (lane == 0) { sg->tok_base = tok; sg->out_base = out; sg->used = 1; sg->ntok = nt; sg->nbytes = nb; sg->head = hd; }
+            tok += nt - hd;
+            out += nb;
+            if (status == PSEG_CUT) { k = nx; by_cut = true; continue; }
+            by_cut = false;
+        } else {
         if (lane == 0) { sg->tok_base = tok; sg->out_base = out; sg->used = 1; }
         tok += uni64(sg->ntok);
         out += uni64(sg->nbytes);
+        }
         if (status == PSEG_FINAL) { ok = true; end_bit = end; break; }
         if (status == PSEG_PARTIAL) { ok = true; partial = true; end_bit = end; break; }
         const uint32_t nx = UNI(sg->next);
         if (nx <= k || nx >= count) break;
         if (uni64(segs[first + nx].start_bit) != end) break;
         k = nx;
+    }
+    if (CUT && met_cut && !(ok && !partial)) {                     // (before the parts: `ok` decides whether there are any)
+        ok = false; partial = false; dry = true;
+        if (lane == 0) atomicAdd(stats + 2, 1u);
+        COV(8);
     }
     // the parts: a new one begins with the first chain segment whose first byte is at or behind the next multiple of 1 / P of
     // the output (and behind the first 32 KiB, so that every marker names a byte that exists); a stream from its first byte only (no resumed one), and one
@@ -1261,6 +1588,17 @@ __global__ __launch_bounds__(64) void pinf2_scan_kernel(PStream *__restrict__ st
     // pass: 1 = the chain broke where the token pool was empty: once more, with the pool to itself and its like (retry)
     if (lane == 0) { st.ok = ok ? (partial ? 2 : 1) : 0; st.ntok = tok; st.end_bit = end_bit; st.pass = (!retry && dry) ? 1 : 0; st.tok_base = 0;
                      st.out_total = out; st.parts = np; }
+}
+
+template <uint32_t RETRY>
+__global__ __launch_bounds__(64) void pinf2_scan_kernel(PStream *__restrict__ streams, PSeg *__restrict__ segs, PPart *__restrict__ parts)
+{
+    scan_stream<RETRY, false>(streams, segs, parts, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void pinf2_cutscan_kernel(PStream *__restrict__ streams, PSeg *__restrict__ segs, const PCut *__restrict__ cuts,
+                                                           PPart *__restrict__ parts, uint32_t *__restrict__ stats)
+{
+    scan_stream<0, true>(streams, segs, parts, stats, cuts);
 }
 
 // ---- resolve: tokens -> bytes -------------------------------------------------------------------------------
@@ -1426,7 +1764,7 @@ __global__ __launch_bounds__(RT2, SPNG_R_WAVES) void pinf2_resolve_kernel(const 
         const uint64_t nhw = uni64(sg.ntok);
         const g32 *ptg = (const g32 *)(pt_slab + uni64(sg.log_off));
         const int32_t sstatus = (int32_t)UNI(sg.status);
-        uint64_t cursor = 0;                           // halfwords of this segment consumed
+        uint64_t cursor = UNI(sg.head);                // halfwords of this segment consumed (a cut segment: the ones its join told it to skip)
         uint64_t pt_lo = 0;                            // first page in s.pt
         __syncthreads();
         for (uint32_t i = (uint32_t)tid; i < PTC; i += RT2) s.pt[i] = (pt_lo + i) * PAGE_UNITS * 8 < nhw + 8 ? ptg[pt_lo + i] : 0u;
@@ -1445,7 +1783,7 @@ __global__ __launch_bounds__(RT2, SPNG_R_WAVES) void pinf2_resolve_kernel(const 
                 else { const v2u v = ((const gPV2 *)q)->v; tv[0] = v[0]; tv[1] = v[1]; }
             }
         };
-        load_window(0);
+        load_window(cursor);
         while (cursor < nhw) {
             RP2(0);
             // ---- the window: HPT2 halfwords per thread (a window starts on a multiple of HPT2: see the cut below)
@@ -1834,6 +2172,32 @@ hipError_t launch_pinf2_decode(PStream *d_streams, PSeg *d_segs, uint32_t seg0, 
     DPool pool{d_pool, d_next, pages, 0};
     if (retry) pinf2_decode_kernel<1><<<nsegs, 64, 0, stream>>>(d_streams, d_segs, d_pt, pool, seg0);
     else pinf2_decode_kernel<0><<<nsegs, 64, 0, stream>>>(d_streams, d_segs, d_pt, pool, seg0);
+    return hipGetLastError();
+}
+// block cuts: the plan in front of the decode that knows cut segments, the join behind it, the scan that follows the joins
+hipError_t launch_pinf2_cutplan(PStream *d_streams, uint32_t nstreams, PSeg *d_segs, PCut *d_cuts, uint32_t *d_stats, hipStream_t stream)
+{
+    pinf2_cutplan_kernel<<<nstreams, 64, 0, stream>>>(d_streams, d_segs, d_cuts, d_stats);
+    return hipGetLastError();
+}
+hipError_t launch_pinf2_cutdecode(PStream *d_streams, PSeg *d_segs, PCut *d_cuts, uint32_t seg0, uint32_t nsegs, uint32_t *d_pt, uint8_t *d_pool,
+                                  uint32_t *d_next, uint32_t pages, hipStream_t stream)
+{
+    DPool pool{d_pool, d_next, pages, 0};
+    pinf2_cutdecode_kernel<1><<<nsegs, 64, 0, stream>>>(d_streams, d_segs, d_pt, pool, seg0, d_cuts);
+    pinf2_cutdecode_kernel<2><<<nsegs, 64, 0, stream>>>(d_streams, d_segs, d_pt, pool, seg0, d_cuts);
+    return hipGetLastError();
+}
+hipError_t launch_pinf2_cutjoin(PStream *d_streams, PSeg *d_segs, PCut *d_cuts, uint32_t seg0, uint32_t nsegs, uint32_t *d_pt, uint8_t *d_pool,
+                                uint32_t *d_next, uint32_t pages, uint32_t *d_stats, hipStream_t stream)
+{
+    DPool pool{d_pool, d_next, pages, 0};
+    pinf2_cutjoin_kernel<<<nsegs, 64, 0, stream>>>(d_streams, d_segs, d_cuts, d_pt, pool, seg0, d_stats);
+    return hipGetLastError();
+}
+hipError_t launch_pinf2_cutscan(PStream *d_streams, uint32_t nstreams, PSeg *d_segs, PCut *d_cuts, PPart *d_parts, uint32_t *d_stats, hipStream_t stream)
+{
+    pinf2_cutscan_kernel<<<nstreams, 64, 0, stream>>>(d_streams, d_segs, d_cuts, d_parts, d_stats);
     return hipGetLastError();
 }
 hipError_t launch_pinf2_scan(PStream *d_streams, uint32_t nstreams, PSeg *d_segs, PPart *d_parts, uint32_t retry, hipStream_t stream)

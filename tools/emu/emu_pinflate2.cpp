@@ -3,6 +3,8 @@
 // expected output.  Built and used by tests/test_emu_pinflate.py; never part of the product.
 //
 //   emu_pinflate2 <stream file> <expected output file> <format 0|1> <segment bytes> [pool pages] [resume: start_bit out_pos]
+//   EMU_CUT_BYTES=n: block cuts for runs of segments without a start of at least n bytes (api.hip: SPNG_CFG_BLOCK_CUT_BYTES), with
+//   the retry pass behind them for a stream whose cuts do not stitch; prints "cuts tried=<n> joined=<n> redone=<n>"
 //   exit code 0: the pipeline produced SPNG_DONE and identical bytes;  3: the pipeline left the whole stream to the serial
 //   kernel;  4: it decoded a prefix (printed: the block boundary and byte count the serial kernel would start from) and that
 //   prefix is right;  5: it reported an error of its own (printed);  1: wrong bytes / wrong result
@@ -20,7 +22,11 @@ static std::vector<uint8_t> slurp(const char *path)
 }
 
 #ifdef SPNG_EMU_COV
-static void cov_print() { fprintf(stderr, "COV"); for (int i = 0; i < 6; ++i) fprintf(stderr, " %ld", spng::g_cov[i]); fprintf(stderr, "\n"); }
+static void cov_print()
+{
+    fprintf(stderr, "COV"); for (int i = 0; i < 6; ++i) fprintf(stderr, " %ld", spng::g_cov[i]); fprintf(stderr, "\n");
+    if (getenv("EMU_CUT_BYTES")) fprintf(stderr, "COVCUT %ld %ld %ld\n", spng::g_cov[6], spng::g_cov[7], spng::g_cov[8]);
+}
 #endif
 int main(int argc, char **argv)
 {
@@ -44,11 +50,11 @@ int main(int argc, char **argv)
     st.format = format; st.image = 0;
     uint64_t state[4] = {0, 0, 0, 0};                          // (four words: the pipeline moves the first pair and clears the second)
     st.state = state;                                          // (api.hip: every stream has a state slot, {0, 0} unless resumed)
+    const bool resumed = argc > 7;
     if (argc > 7) {
         state[0] = st.start_bit = strtoull(argv[6], nullptr, 10); state[1] = st.out_pos = strtoull(argv[7], nullptr, 10);
         memcpy(dst.data(), want.data(), st.out_pos);
     }
-    const bool resumed = argc > 7;
     uint64_t k = (src.size() + seg_bytes - 1) / seg_bytes;
     if (k < 1) k = 1;
     st.seg_first = 0; st.seg_count = (uint32_t)k; st.seg_bytes = seg_bytes;
@@ -73,6 +79,22 @@ int main(int argc, char **argv)
 
     emu::launch((unsigned)k, 64, [&] { pinf2_find_kernel<0>(&st, segs.data(), 0); });
     if (verbose) for (uint64_t q = 0; q < k; ++q) fprintf(stderr, "seg %llu: start %lld\n", (unsigned long long)q, (long long)segs[q].start_bit);
+    // block cuts (api.hip: a batch with a stream they may be tried for)
+    const uint64_t cut_bytes = getenv("EMU_CUT_BYTES") ? strtoull(getenv("EMU_CUT_BYTES"), nullptr, 10) : 0;
+    uint32_t cstats[4] = {0, 0, 0, 0};                         // cuts tried, joined, streams redone
+    std::vector<PCut> cuts(k);                                 // (api.hip: a table of its own beside the segments, zeroed on the device)
+    memset(cuts.data(), 0, k * sizeof(PCut));
+    if (cut_bytes && !resumed) {
+        st.cut_segs = (uint32_t)((cut_bytes + seg_bytes - 1) / seg_bytes);
+        emu::launch(1, 64, [&] { pinf2_cutplan_kernel(&st, segs.data(), cuts.data(), cstats); });
+        emu::launch((unsigned)k, 64, [&] { pinf2_cutdecode_kernel<1>(&st, segs.data(), pt.data(), pool, 0, cuts.data()); });
+        emu::launch((unsigned)k, 64, [&] { pinf2_cutdecode_kernel<2>(&st, segs.data(), pt.data(), pool, 0, cuts.data()); });
+        emu::launch((unsigned)k, 64, [&] { pinf2_cutjoin_kernel(&st, segs.data(), cuts.data(), pt.data(), pool, 0, cstats); });
+        if (verbose) for (uint64_t q = 0; q < k; ++q)
+            fprintf(stderr, "seg %llu: cut %u anchor %d nrec %u joined %u head %u rec0 %lld tbl_id %llx head_tbl %llx add %llu\n", (unsigned long long)q, cuts[q].cut,
+                    (int)cuts[q].anchor, cuts[q].nrec, cuts[q].joined, cuts[q].next_head, (long long)cuts[q].rec[0].bit, (unsigned long long)cuts[q].tbl_id,
+                    (unsigned long long)cuts[q].head_tbl, (unsigned long long)cuts[q].add_tok);
+    } else
     emu::launch((unsigned)k, 64, [&] { pinf2_decode_kernel<0>(&st, segs.data(), pt.data(), pool, 0); });
     if (verbose) for (uint64_t q = 0; q < k; ++q)
         fprintf(stderr, "seg %llu: end %lld status %d nhw %llu next %u\n", (unsigned long long)q, (long long)segs[q].end_bit, segs[q].status,
@@ -84,7 +106,22 @@ int main(int argc, char **argv)
     std::vector<uint16_t> sym(pmax ? want.size() + 4096 + 64 : 8, 0xEEEE);
     std::vector<uint8_t> win((size_t)(pmax ? pmax : 1) * 32768, 0xCD);
     st.parts_max = pmax; st.sym_off = 0;
-    emu::launch(1, 64, [&] { pinf2_scan_kernel<0>(&st, segs.data(), parts.data()); });
+    if (st.cut_segs) emu::launch(1, 64, [&] { pinf2_cutscan_kernel(&st, segs.data(), cuts.data(), parts.data(), cstats); });
+    else emu::launch(1, 64, [&] { pinf2_scan_kernel<0>(&st, segs.data(), parts.data()); });
+    // a stream whose cuts did not stitch: the retry pass, which knows none, with a pool of its own
+    const bool redo = st.cut_segs && st.pass == 1;
+    std::vector<uint8_t> poolmem_redo;
+    uint32_t next_redo[4] = {0, 0, 0, 0};
+    DPool pool_redo = pool;
+    if (redo) {
+        poolmem_redo.assign((size_t)pages << PAGE_SHIFT, 0xAB);
+        pool_redo = DPool{poolmem_redo.data(), next_redo, pages, 0};
+        emu::launch((unsigned)k, 64, [&] { pinf2_find_kernel<1>(&st, segs.data(), 0); });
+        emu::launch((unsigned)k, 64, [&] { pinf2_decode_kernel<1>(&st, segs.data(), pt.data(), pool_redo, 0); });
+        emu::launch(1, 64, [&] { pinf2_scan_kernel<1>(&st, segs.data(), parts.data()); });
+    }
+    if (st.cut_segs) printf("cuts tried=%u joined=%u redone=%u\n", cstats[0], cstats[1], cstats[2]);
+    const uint8_t *tokmem = redo ? poolmem_redo.data() : poolmem.data();
     if (verbose && pmax) for (uint32_t q = 0; q < st.parts; ++q)
         fprintf(stderr, "part %u: seg %u .. %u out %llu + %llu\n", q, parts[q].seg, parts[q].seg_end, (unsigned long long)parts[q].out_pos, (unsigned long long)parts[q].out_len);
     if (verbose) fprintf(stderr, "stream: ok %d nhw %llu end_bit %llu pages used %u\n", st.ok, (unsigned long long)st.ntok, (unsigned long long)st.end_bit, next);
@@ -93,10 +130,10 @@ int main(int argc, char **argv)
         uint32_t sk = 0; bool okt = st.ok != 0;
         for (uint32_t hops = 0; okt && hops < k; ++hops) {
             const PSeg &sg = segs[sk];
-            for (uint64_t i = 0; i < sg.ntok; ++i) {
+            for (uint64_t i = sg.head; i < sg.ntok; ++i) {
                 auto hw = [&](uint64_t idx) -> uint32_t {
                     const uint64_t u = idx >> 3; const uint32_t pid = pt[sg.log_off + (u >> (PAGE_SHIFT - 4))];
-                    return ((const uint16_t *)(poolmem.data() + ((size_t)pid << PAGE_SHIFT) + ((u & (PAGE_UNITS - 1)) << 4)))[idx & 7];
+                    return ((const uint16_t *)(tokmem + ((size_t)pid << PAGE_SHIFT) + ((u & (PAGE_UNITS - 1)) << 4)))[idx & 7];
                 };
                 const uint32_t v = hw(i);
                 if (!(v & 0x8000)) out.push_back((uint8_t)v);
@@ -115,6 +152,8 @@ int main(int argc, char **argv)
         if (verbose || i != out.size() || (st.ok == 1 && out.size() != want.size()))
             fprintf(stderr, "token stream expands to %zu bytes, agrees with the expected bytes up to %zu of %zu\n", out.size(), i, want.size());
     }
+    if (redo) emu::launch(1, RT2, [&] { pinf2_resolve_kernel<1, false, true>(&st, segs.data(), pt.data(), pool_redo, &res, &done, parts.data(), 0, nullptr); });
+    else
     emu::launch(1, RT2, [&] { pinf2_resolve_kernel<0, false, true>(&st, segs.data(), pt.data(), pool, &res, &done, parts.data(), pmax, nullptr); });
     // EMU_RETRY_PAGES=n: a stream whose segments found the pool empty takes the retry pass (api.hip: the pool to itself and
     // its like -- here a second pool of n pages)
@@ -131,7 +170,7 @@ int main(int argc, char **argv)
         emu::launch(1, RT2, [&] { pinf2_resolve_kernel<1, false, true>(&st, segs.data(), pt.data(), pool2, &res, &done, parts.data(), 0, nullptr); });
         printf("retry pass: ok %d done %d pages %u\n", st.ok, done, next2);
     }
-    if (pmax >= 2) {
+    if (pmax >= 2 && !redo) {
         // (api.hip picks the marker parts' geometry by their number; here EMU_MARK_TILE=8192 asks for the big tiles)
         if (getenv("EMU_MARK_TILE") && atoi(getenv("EMU_MARK_TILE")) == 8192)
             emu::launch(pmax - 1, RT2, [&] { pinf2_resolve_kernel<0, true, true>(&st, segs.data(), pt.data(), pool, &res, &done, parts.data(), pmax, sym.data()); });

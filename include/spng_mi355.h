@@ -136,9 +136,7 @@ enum { SPNG_CFG_INFLATE_MODE = 0,   /* SPNG_INFLATE_AUTO: parallel pipeline, ser
        SPNG_CFG_SEGMENT_BYTES = 1,  /* parallel inflate: nominal segment length in compressed bytes */
        SPNG_CFG_TOKEN_BYTES = 2,    /* parallel inflate: size limit of the token page pool in bytes */
        SPNG_CFG_UNFILTER_PIECE_ROWS = 3,   /* unfilter: rows per piece a scanline chain is cut into */
-       SPNG_CFG_INFLATE_OVERLAP = 4,       /* parallel inflate: SPNG_OVERLAP_ALWAYS = every batch of >= 2 streams in two halves
-                                              on two streams, the decode of one beside the resolve of the other
-                                              (an experiment: slower than one pass on MI355X, so never by default) */
+                                           /* 4: reserved (spng_configure refuses it) */
        SPNG_CFG_RESOLVE_PARTS = 5,         /* parallel inflate, batches of <= 384 streams: workgroups that resolve ONE stream side by
                                               side (0: as many as fill the chip, at most 128 and not below ~1 MiB of output each; 1: one, as in large batches; n: n, at most 128) */
                                            /* 6: reserved (spng_configure refuses it) */
@@ -154,7 +152,6 @@ enum { SPNG_CFG_INFLATE_MODE = 0,   /* SPNG_INFLATE_AUTO: parallel pipeline, ser
        SPNG_CFG_COUNT = 10 };
 enum { SPNG_BLOCK_CUT_AUTO = 0, SPNG_BLOCK_CUT_NEVER = 1 };
 enum { SPNG_INFLATE_AUTO = 0, SPNG_INFLATE_SERIAL = 1 };
-enum { SPNG_OVERLAP_AUTO = 0, SPNG_OVERLAP_ALWAYS = 1, SPNG_OVERLAP_NEVER = 2 };
 int32_t spng_configure(spng_ctx *ctx, int key, int64_t value);
 
 /* Per-kernel timing with HIP events recorded on the context's stream around every launch. */

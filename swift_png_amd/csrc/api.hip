@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <array>
 #include <functional>
 #include <mutex>
 #include <vector>
@@ -95,9 +96,9 @@ struct spng_ctx {
     double   block_bytes = 0;        // compressed bytes per DEFLATE block in the last batch (0: not known)
     hipEvent_t pool_ev = nullptr; bool pool_pending = false;
     hipEvent_t ev_dfl[4] = {nullptr, nullptr, nullptr, nullptr};    // level >= 8 rounds: searched[parity], parsed[parity]
-    // second stream of the pipeline: the decode of one half of a batch runs beside the resolve of the other
+    // second stream (second_stream()): the parts of a stream's resolve beside its first, a deflate round's search beside the parse
     hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_mid = nullptr, ev_join = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // spng_decode_batch_multi: the stream a context's rasters leave on (so that a group's copies run beside the next group's
     // decode), the events between the two, its part of the results, the peers it has been given access to
     hipStream_t stream_out = nullptr;
@@ -112,17 +113,37 @@ struct spng_ctx {
     std::vector<hipEvent_t> pool;
     std::mutex mu;
 
+    // the buffers a batch sizes (spng_trim gives them back to the device; d_ws, the job tables', stays)
+    struct Buf { void **p; size_t *cap; };
+    std::array<Buf, 6> batch_buffers()
+    {
+        return {{{&d_graph, &graph_cap}, {&d_log, &log_cap}, {&d_tok, &tok_cap}, {&d_sym, &sym_cap}, {&d_win, &win_cap}, {&d_multi, &multi_cap}}};
+    }
+    // Makes a device buffer of the context hold `need` bytes.  Only when it has to grow: waits for the stream (kernels in
+    // flight may still read the old one), frees it and allocates need + slack.  A failed allocation is an error -- or, `failed`
+    // given, reported there: the sticky HIP error cleared, the pointer null, the capacity 0.
+    int32_t grow(void *&buf, size_t &cap, size_t need, size_t slack, bool *failed = nullptr)
+    {
+        if (failed) *failed = false;
+        if (need <= cap) return SPNG_DONE;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (buf) { HIP_TRY(hipFree(buf)); buf = nullptr; }
+        cap = 0;
+        const hipError_t e = hipMalloc(&buf, need + slack);
+        if (e != hipSuccess) {
+            buf = nullptr;
+            if (!failed) return fail_hip(e, "hipMalloc");
+            (void)hipGetLastError();
+            *failed = true;
+            return SPNG_DONE;
+        }
+        cap = need + slack;
+        return SPNG_DONE;
+    }
     // Starts a call: device table space for `bytes`, and a pinned slab nobody is reading any more.
     int32_t reserve(size_t bytes)
     {
-        if (bytes > d_ws_cap) {
-            // the previous tables may still be read by in-flight kernels
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (d_ws) { HIP_TRY(hipFree(d_ws)); d_ws = nullptr; }
-            const size_t cap = bytes + bytes / 2 + 4096;
-            HIP_TRY(hipMalloc(&d_ws, cap));
-            d_ws_cap = cap;
-        }
+        if (int32_t st = grow(d_ws, d_ws_cap, bytes, bytes / 2 + 4096)) return st;
         Slab &sl = slabs[slab_next];
         slab_next = (slab_next + 1) % SLABS;
         if (sl.pending) { HIP_TRY(hipEventSynchronize(sl.ev)); sl.pending = false; }
@@ -154,6 +175,25 @@ struct spng_ctx {
         return e;
     }
 };
+
+// The second stream and the events that fork to it and join from it, on first use.
+static int32_t second_stream(spng_ctx *c)
+{
+    if (c->stream2) return SPNG_DONE;
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+    for (hipEvent_t *e : {&c->ev_fork, &c->ev_join}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return SPNG_DONE;
+}
+
+// The tail of a call that hands something back: `bytes` from the device to the host behind everything the call enqueued, and
+// the wait for them.  No host pointer: nothing -- the call stays asynchronous.
+static int32_t read_back(spng_ctx *c, void *h, const void *d, size_t bytes)
+{
+    if (!h) return SPNG_DONE;
+    HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPNG_DONE;
+}
 
 struct Timed {            // records a pair of events around a launch when profiling is on
     spng_ctx *c; int k; hipEvent_t a = nullptr; hipStream_t s;
@@ -266,18 +306,13 @@ void spng_destroy(spng_ctx *c)
     for (auto e : c->pool) (void)hipEventDestroy(e);
     if (c->d_ws) (void)hipFree(c->d_ws);
     for (auto &sl : c->slabs) { if (sl.h) (void)hipHostFree(sl.h); if (sl.ev) (void)hipEventDestroy(sl.ev); }
-    if (c->d_graph) (void)hipFree(c->d_graph);
-    if (c->d_log) (void)hipFree(c->d_log);
-    if (c->d_tok) (void)hipFree(c->d_tok);
-    if (c->d_sym) (void)hipFree(c->d_sym);
-    if (c->d_win) (void)hipFree(c->d_win);
+    for (auto b : c->batch_buffers()) if (*b.p) (void)hipFree(*b.p);
     if (c->h_pool_used) (void)hipHostFree(c->h_pool_used);
     if (c->pool_ev) (void)hipEventDestroy(c->pool_ev);
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
     if (c->stream_out) { (void)hipStreamSynchronize(c->stream_out); (void)hipStreamDestroy(c->stream_out); }
     for (hipEvent_t e : c->ev_out) if (e) (void)hipEventDestroy(e);
-    if (c->d_multi) (void)hipFree(c->d_multi);
-    for (hipEvent_t e : {c->ev_fork, c->ev_mid, c->ev_join}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_fork, c->ev_join}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_dfl) if (e) (void)hipEventDestroy(e);
     if (c->owns_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -294,7 +329,7 @@ int32_t spng_sync(spng_ctx *c)
 
 int32_t spng_configure(spng_ctx *c, int key, int64_t value)
 {
-    if (!c || key < 0 || key >= SPNG_CFG_COUNT || key == 6 /* reserved */ || value < 0) return SPNG_E_ARGUMENT;
+    if (!c || key < 0 || key >= SPNG_CFG_COUNT || key == 4 || key == 6 /* reserved */ || value < 0) return SPNG_E_ARGUMENT;
     std::lock_guard<std::mutex> g(c->mu);
     c->cfg[key] = value;
     return SPNG_DONE;
@@ -551,9 +586,9 @@ struct InflatePlan {
     bool parallel = false;
     // pinflate2: the token pool and the groups of streams that share it, one after the other
     uint32_t pool_pages = 0;
-    struct Group { uint32_t s0, s1, g0, g1, page0, pages; };   // streams, segments, its pages of the pool
+    struct Group { uint32_t s0, s1, g0, g1; };                 // streams, segments
     std::vector<Group> groups;
-    bool overlap = false;            // two groups, each with its own half of the pool, on two streams (see launch_inflate_plan)
+    std::vector<uint64_t> est;       // token bytes every stream is expected to take (planning only)
     uint32_t pmax = 0;               // several workgroups per stream: part slots per stream (0: one workgroup per stream)
     size_t parts_at = 0;
     size_t next_at = 0;
@@ -578,28 +613,10 @@ struct InflatePlan {
 static constexpr uint64_t RESUME_SERIAL_BITS = 8ull << 20;      // 1 MiB of input inside one block: resume there, not at its header
                                                                 // (and, one-shot calls: cut there -- SPNG_CFG_BLOCK_CUT_BYTES)
 
-// Cuts every stream into segments and makes sure the context owns what the pipeline needs.  Segment length: long
-// enough that the search for a block header (which costs more per bit than decoding) stays a small part of a
-// segment's work, short enough that the batch yields several thousand segments, i.e. a few waves per SIMD.
-//
-// pinflate2 (the default): a page table per segment (c->d_log) and the token pool (c->d_tok, 64 KiB pages).  A
-// compressed byte becomes at most 8 token halfwords and a stream at most one per output byte; what a batch really
-// needs is far less (0.8 per byte for zlib-made PNG streams, 1.4 for swift-png's own), so the pool is sized by the
-// ratio the previous batch showed (3.2 bytes per byte before there is one), capped by SPNG_CFG_TOKEN_BYTES or half of
-// the free memory, and the streams take it in as many groups as that needs.  A segment that finds the pool empty
-// gives its stream to the serial kernel.
-static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
+// What the last batch taught about token volume (its page count comes back behind its kernels: when the planning
+// figure would cut THIS batch into groups, waiting for that number is cheaper than not knowing it).
+static int32_t learn_from_last_batch(spng_ctx *c, uint64_t total)
 {
-    p.internal = p.state.empty();
-    if (p.internal) p.state.assign(p.jobs.size() * 4, 0);
-    for (auto &j : p.jobs) j.internal = p.internal ? 1 : 0;
-    p.parallel = c->cfg[SPNG_CFG_INFLATE_MODE] != SPNG_INFLATE_SERIAL && !p.jobs.empty();
-    for (auto &j : p.jobs) p.gzip = p.gzip || j.format == SPNG_FORMAT_GZIP;
-    if (!p.parallel) return SPNG_DONE;
-    uint64_t total = 0;
-    for (auto &j : p.jobs) total += j.src_len;
-    // what the last batch taught about token volume (its page count comes back behind its kernels: when the planning
-    // figure would cut THIS batch into groups, waiting for that number is cheaper than not knowing it)
     if (c->pool_pending && c->pool_ratio == 0 && hipEventQuery(c->pool_ev) != hipSuccess) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -613,6 +630,12 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         else if (c->pool_src_pending > (1u << 20)) c->pool_ratio = (double)used * 65536.0 / (double)c->pool_src_pending;
         c->block_bytes = (blocks && c->pool_src_pending > (1u << 20)) ? (double)c->pool_src_pending / (double)blocks : 0;
     }
+    return SPNG_DONE;
+}
+
+// Segment length: SPNG_CFG_SEGMENT_BYTES, or by the batch's compressed bytes and the block size the last batch showed.
+static uint64_t segment_bytes(const spng_ctx *c, uint64_t total)
+{
     uint64_t seg_bytes = (uint64_t)c->cfg[SPNG_CFG_SEGMENT_BYTES];
     if (!seg_bytes) {
         // (~9 rounds of resident waves, so that the last, partly filled one costs little; the search costs 7 ms per 10^4 segments)
@@ -635,10 +658,16 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         if (least > hi) least = hi;
         if (seg_bytes < least) seg_bytes = least;
     }
-    seg_bytes = (seg_bytes + 255) & ~(uint64_t)255;
+    return (seg_bytes + 255) & ~(uint64_t)255;
+}
+
+// Cuts every stream into segments of seg_bytes (p.streams, p.segs, the page-table entries they may take: p.log_bytes) and
+// estimates the token bytes each stream will need (p.est).
+static int32_t cut_into_segments(spng_ctx *c, InflatePlan &p, uint64_t seg_bytes)
+{
     p.streams.resize(p.jobs.size());
     const double per_byte = c->pool_ratio > 0 ? (c->pool_ratio * 1.25 < 1.0 ? 1.0 : c->pool_ratio * 1.25) : 3.2;
-    std::vector<uint64_t> est(p.jobs.size(), 0);
+    p.est.assign(p.jobs.size(), 0);
     size_t log = 0;
     for (size_t i = 0; i < p.jobs.size(); ++i) {
         const InflateJob &j = p.jobs[i];
@@ -684,23 +713,24 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         }
         uint64_t e = (uint64_t)(per_byte * (double)j.src_len);
         if (e > 2 * (j.dst_cap + 64)) e = 2 * (j.dst_cap + 64);
-        est[i] = e + k * 65536 + 65536;                                            // (every segment ends inside a page)
+        p.est[i] = e + k * 65536 + 65536;                                          // (every segment ends inside a page)
         // (block cuts: a cut segment's first chunks -- tokens nobody reads --, the padding of its records and its join's bridge take room
         // too, and EVERY segment of the stream ends inside a page, not only those with a start: a second page per segment.
         // Not for a stream whose like the last batch showed to be made of ordinary blocks: there nothing will be cut, and a batch of
         // 1024 images would ask for 10 GiB it never touches.  A wrong guess costs the stream the retry pass, not its result.)
-        if (st.cut_segs && !(c->block_bytes > 0 && c->block_bytes < 262144)) est[i] += k * 65536;
+        if (st.cut_segs && !(c->block_bytes > 0 && c->block_bytes < 262144)) p.est[i] += k * 65536;
     }
-    log *= 4;
-    p.log_bytes = log;
-    if (log > c->log_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_log) { HIP_TRY(hipFree(c->d_log)); c->d_log = nullptr; c->log_cap = 0; }
-        HIP_TRY(hipMalloc(&c->d_log, log + log / 8));
-        c->log_cap = log + log / 8;
-    }
+    p.log_bytes = log * 4;
+    return SPNG_DONE;
+}
+
+// The page tables (c->d_log) and the token pool (c->d_tok), sized by the estimates within the budget.  No room for the pool:
+// the plan is not parallel any more.
+static int32_t size_token_pool(spng_ctx *c, InflatePlan &p)
+{
+    if (int32_t st = c->grow(c->d_log, c->log_cap, p.log_bytes, p.log_bytes / 8)) return st;
     uint64_t want = 0, largest = 0;
-    for (auto e : est) { want += e; if (e > largest) largest = e; }
+    for (auto e : p.est) { want += e; if (e > largest) largest = e; }
     uint64_t budget = (uint64_t)c->cfg[SPNG_CFG_TOKEN_BYTES];
     if (!budget) {
         size_t free_b = 0, total_b = 0;
@@ -712,19 +742,20 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
     uint64_t need = want < budget ? want : budget;
     if (need < largest) need = largest;                                            // (a stream is never split over groups)
     need = (need + 65535) & ~(uint64_t)65535;
-    if (need > c->tok_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_tok) { HIP_TRY(hipFree(c->d_tok)); c->d_tok = nullptr; c->tok_cap = 0; }
-        if (hipMalloc(&c->d_tok, need) != hipSuccess) {
-            // no room for the pipeline: the serial kernel takes the batch
-            (void)hipGetLastError();
-            c->d_tok = nullptr; c->tok_cap = 0;
-            p.parallel = false; p.streams.clear(); p.segs.clear();
-            return SPNG_DONE;
-        }
-        c->tok_cap = need;
+    bool failed = false;
+    if (int32_t st = c->grow(c->d_tok, c->tok_cap, need, 0, &failed)) return st;
+    if (failed) {
+        // no room for the pipeline: the serial kernel takes the batch
+        p.parallel = false; p.streams.clear(); p.segs.clear();
     }
-    // groups of consecutive streams whose estimates fit the pool together
+    return SPNG_DONE;
+}
+
+// Groups of consecutive streams whose estimates fit the pool together.
+static void group_streams(const spng_ctx *c, InflatePlan &p)
+{
+    uint64_t want = 0, largest = 0;
+    for (auto e : p.est) { want += e; if (e > largest) largest = e; }
     const uint64_t pool = c->tok_cap & ~(uint64_t)65535;
     p.pool_pages = (uint32_t)(pool >> 16 > 0xfffffff0ull ? 0xfffffff0ull : pool >> 16);
     // (as many groups as the estimates need, of equal share: 730 + 294 streams cost resolve three rounds of resident
@@ -737,42 +768,23 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         if (share > pool) share = pool;
     }
     uint64_t run = 0;
-    InflatePlan::Group g{0, 0, 0, 0, 0, p.pool_pages};
+    InflatePlan::Group g{0, 0, 0, 0};
     for (size_t i = 0; i < p.jobs.size(); ++i) {
-        if (run + est[i] > share && g.s1 > g.s0) {
+        if (run + p.est[i] > share && g.s1 > g.s0) {
             p.groups.push_back(g);
             g.s0 = g.s1; g.g0 = g.g1; run = 0;
         }
-        run += est[i];
+        run += p.est[i];
         g.s1 = (uint32_t)i + 1; g.g1 = p.streams[i].seg_first + p.streams[i].seg_count;
     }
     p.groups.push_back(g);
-    // On request (SPNG_CFG_INFLATE_OVERLAP) a batch that fits the pool at once goes in two halves, each with its share of
-    // the pool, the decode of the second beside the resolve of the first on a second stream.  Not by default: both
-    // kernels live on LDS (14 x 11 KB decode waves or 2 x 61 KB resolve workgroups fill a CU), so side by side they
-    // only displace each other -- 1024 x 4K images: 635 ms per step instead of 526 (profiles/r03_inflate_tuning.md).
-    const int64_t ovl = c->cfg[SPNG_CFG_INFLATE_OVERLAP];
-    if (p.groups.size() == 1 && p.jobs.size() >= 2 && ovl == SPNG_OVERLAP_ALWAYS) {
-        uint64_t half = 0, sum = 0;
-        size_t cut = 0;
-        for (auto e : est) sum += e;
-        while (cut + 1 < p.jobs.size() && 2 * (half + est[cut]) <= sum + est[cut]) half += est[cut++];
-        if (cut >= 1 && cut < p.jobs.size()) {
-            InflatePlan::Group a = p.groups[0], b = p.groups[0];
-            a.s1 = b.s0 = (uint32_t)cut;
-            a.g1 = b.g0 = p.streams[cut].seg_first;
-            uint64_t pa = (uint64_t)((double)p.pool_pages * ((double)half / (double)sum));
-            if (pa < 1) pa = 1;
-            if (pa >= p.pool_pages) pa = p.pool_pages - 1;
-            a.page0 = 0; a.pages = (uint32_t)pa;
-            b.page0 = (uint32_t)pa; b.pages = p.pool_pages - (uint32_t)pa;
-            p.groups = {a, b};
-            p.overlap = true;
-        }
-    }
-    // Few streams: a workgroup per stream would leave most of the chip idle while each resolves its stream at ~0.9 GB/s
-    // (one 4K image: 77 ms of an 89 ms decode).  Then a stream's chain is cut into parts that resolve side by side
-    // (pinflate2.hip, "Several workgroups per stream"): 16-bit symbols in c->d_sym, the windows in c->d_win.
+}
+
+// Few streams: a workgroup per stream would leave most of the chip idle while each resolves its stream at ~0.9 GB/s
+// (one 4K image: 77 ms of an 89 ms decode).  Then a stream's chain is cut into parts that resolve side by side
+// (pinflate2.hip, "Several workgroups per stream"): 16-bit symbols in c->d_sym, the windows in c->d_win.
+static int32_t plan_parts(spng_ctx *c, InflatePlan &p)
+{
     p.pmax = 0;
     if (p.internal && p.jobs.size() <= 384 && c->cfg[SPNG_CFG_RESOLVE_PARTS] != 1) {
         // (512 workgroups in all: the marker parts run two to a CU -- pinflate2.hip, RGeo --, so that is one round of resident
@@ -805,20 +817,14 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
             afford = syms * 2 + win <= (uint64_t)(free_b + c->sym_cap + c->win_cap) / 4;
         }
         if (pm >= 2 && afford) {
-            bool room = true;
+            bool failed = false;
             if (syms * 2 > c->sym_cap) {
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                if (c->d_sym) { HIP_TRY(hipFree(c->d_sym)); c->d_sym = nullptr; c->sym_cap = 0; }
-                if (hipMalloc(&c->d_sym, syms * 2) != hipSuccess) { (void)hipGetLastError(); room = false; c->sym_failed = syms * 2; }
-                else { c->sym_cap = syms * 2; c->sym_failed = 0; }
+                if (int32_t st = c->grow(c->d_sym, c->sym_cap, syms * 2, 0, &failed)) return st;
+                c->sym_failed = failed ? syms * 2 : 0;
             }
-            if (room && win > c->win_cap) {
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                if (c->d_win) { HIP_TRY(hipFree(c->d_win)); c->d_win = nullptr; c->win_cap = 0; }
-                if (hipMalloc(&c->d_win, win) != hipSuccess) { (void)hipGetLastError(); room = false; }
-                else c->win_cap = win;
-            }
-            if (room) {
+            if (!failed)
+                if (int32_t st = c->grow(c->d_win, c->win_cap, win, 0, &failed)) return st;
+            if (!failed) {
                 p.pmax = pm;
                 for (auto &st : p.streams) st.parts_max = pm;
             }
@@ -829,6 +835,36 @@ static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipFree(c->d_sym)); c->d_sym = nullptr; c->sym_cap = 0;
     }
+    return SPNG_DONE;
+}
+
+// Cuts every stream into segments and makes sure the context owns what the pipeline needs.  Segment length: long
+// enough that the search for a block header (which costs more per bit than decoding) stays a small part of a
+// segment's work, short enough that the batch yields several thousand segments, i.e. a few waves per SIMD.
+//
+// pinflate2 (the default): a page table per segment (c->d_log) and the token pool (c->d_tok, 64 KiB pages).  A
+// compressed byte becomes at most 8 token halfwords and a stream at most one per output byte; what a batch really
+// needs is far less (0.8 per byte for zlib-made PNG streams, 1.4 for swift-png's own), so the pool is sized by the
+// ratio the previous batch showed (3.2 bytes per byte before there is one), capped by SPNG_CFG_TOKEN_BYTES or half of
+// the free memory, and the streams take it in as many groups as that needs.  A segment that finds the pool empty
+// gives its stream to the serial kernel.
+static int32_t plan_inflate(spng_ctx *c, InflatePlan &p)
+{
+    p.internal = p.state.empty();
+    if (p.internal) p.state.assign(p.jobs.size() * 4, 0);
+    for (auto &j : p.jobs) j.internal = p.internal ? 1 : 0;
+    p.parallel = c->cfg[SPNG_CFG_INFLATE_MODE] != SPNG_INFLATE_SERIAL && !p.jobs.empty();
+    for (auto &j : p.jobs) p.gzip = p.gzip || j.format == SPNG_FORMAT_GZIP;
+    if (!p.parallel) return SPNG_DONE;
+    uint64_t total = 0;
+    for (auto &j : p.jobs) total += j.src_len;
+    if (int32_t st = learn_from_last_batch(c, total)) return st;
+    if (int32_t st = cut_into_segments(c, p, segment_bytes(c, total))) return st;
+    if (int32_t st = size_token_pool(c, p)) return st;
+    if (!p.parallel) return SPNG_DONE;
+    group_streams(c, p);
+    if (int32_t st = plan_parts(c, p)) return st;
+    // what the next batch will learn from: this one's pool and source bytes, and where its counters come back to
     c->pool_pages_planned = p.pool_pages;
     c->pool_src_bytes = total;
     if (!c->h_pool_used) {
@@ -872,6 +908,51 @@ static void stage_inflate(InflatePlan &p, Arena &a)
     memcpy(a.host<InflateJob>(p.jobs_at), p.jobs.data(), n * sizeof(InflateJob));
 }
 
+// SPNG_TRACE_PINFLATE -- diagnostic: how far every stream got in the pipeline (synchronises; never on by default)
+static int32_t trace_inflate_plan(spng_ctx *c, const InflatePlan &p, Arena &a)
+{
+    const uint32_t n = (uint32_t)p.jobs.size();
+    std::vector<PStream> hs(n);
+    std::vector<PSeg> hg(p.segs.size());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(hs.data(), a.dev<PStream>(p.streams_at), n * sizeof(PStream), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hg.data(), a.dev<PSeg>(p.segs_at), hg.size() * sizeof(PSeg), hipMemcpyDeviceToHost));
+    {
+        // anomalies over the whole batch: segments without a start, segments that did not end on the next one
+        uint64_t nostart = 0, fail = 0, skipped = 0; uint32_t shown = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const PStream &st = hs[i];
+            for (uint32_t k = 0; k < st.seg_count; ++k) {
+                const PSeg &sg = hg[st.seg_first + k];
+                const bool a = sg.start_bit == ~0ull, b = !a && sg.status != PSEG_CONT && sg.status != PSEG_FINAL, cskip = !a && !b && sg.status == PSEG_CONT && sg.next != k + 1;
+                nostart += a; fail += b; skipped += cskip;
+                if ((a || b || cskip) && shown < 12) {
+                    ++shown;
+                    fprintf(stderr, "[pinflate] anomaly: stream %u seg %u/%u start %lld end %lld status %d next %u ntok %llu\n", i, k, st.seg_count,
+                            (long long)sg.start_bit, (long long)sg.end_bit, sg.status, sg.next, (unsigned long long)sg.ntok);
+                }
+            }
+        }
+        fprintf(stderr, "[pinflate] %u streams, %zu segments in %zu groups, pool %u pages: %llu without a start, %llu failed, %llu ran past the next start\n", n,
+                hg.size(), p.groups.size(), p.pool_pages, (unsigned long long)nostart, (unsigned long long)fail, (unsigned long long)skipped);
+    }
+    for (uint32_t i = 0; i < n && i < 4; ++i) {
+        const PStream &st = hs[i];
+        fprintf(stderr, "[pinflate] stream %u: len %llu segs %u seg_bytes %llu ok %d pass %u ntok %llu end_bit %llu\n", i,
+                (unsigned long long)st.src_len, st.seg_count, (unsigned long long)st.seg_bytes, st.ok, st.pass,
+                (unsigned long long)st.ntok, (unsigned long long)st.end_bit);
+        for (uint32_t k = 0; k < st.seg_count && k < 12; ++k) {
+            const PSeg &sg = hg[st.seg_first + k];
+            fprintf(stderr, "   seg %u: start %lld end %lld status %d used %u ntok %llu tok_base %llu next %u", k,
+                    (long long)sg.start_bit, (long long)sg.end_bit, sg.status, sg.used, (unsigned long long)sg.ntok,
+                    (unsigned long long)sg.tok_base, sg.next);
+            if (sg.head) fprintf(stderr, " head %u", sg.head);
+            fprintf(stderr, "\n");
+        }
+    }
+    return SPNG_DONE;
+}
+
 static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_result *dr)
 {
     const uint32_t n = (uint32_t)p.jobs.size();
@@ -883,34 +964,19 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
         PStream *ds = a.dev<PStream>(p.streams_at);
         PSeg *dg = a.dev<PSeg>(p.segs_at);
         int32_t *dd = a.dev<int32_t>(p.done_at);
-        uint32_t *dnext = a.dev<uint32_t>(p.next_at);
-        // every group of streams in turn, then once more those whose segments found the pool empty (a batch unlike the
-        // one the pool was sized by): they get a second pass instead of the serial kernel.  Two overlapping groups: the
-        // first on the context's stream, the second on stream2 with its decode held back until the first one's is done
-        // (the two decodes side by side would only share the issue slots; decode beside resolve fills what either leaves).
-        if (p.overlap && !c->stream2) {
-            HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-            for (hipEvent_t *e : {&c->ev_fork, &c->ev_mid, &c->ev_join}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-        if (p.overlap) {
-            HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-            HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        }
+        uint32_t *dnext = a.dev<uint32_t>(p.next_at);      // {page counter, blocks} of the pass; dnext[8 ..] = the batch's totals
+        uint32_t *dlog = (uint32_t *)c->d_log;
+        uint8_t *pool = (uint8_t *)c->d_tok;
+        const uint32_t pages = p.pool_pages;
+        const hipStream_t q = c->stream;
+        // every group of streams in turn, each with the whole pool, then once more those whose segments found the pool empty
+        // (a batch unlike the one the pool was sized by): they get a second pass instead of the serial kernel
         c->cut_stats_valid = false;
         for (size_t gi = 0; gi <= p.groups.size(); ++gi) {
             const bool retry = gi == p.groups.size();
-            const InflatePlan::Group g = retry ? InflatePlan::Group{0, n, 0, (uint32_t)p.segs.size(), 0, p.pool_pages} : p.groups[gi];
-            const bool second = p.overlap && gi == 1;
-            hipStream_t q = second ? c->stream2 : c->stream;
-            uint32_t *ctr = dnext + 4 * (second ? 1 : 0);       // {page counter} of the pass; dnext[8 ..] = the batch's totals
-            uint8_t *pool = (uint8_t *)c->d_tok + ((uint64_t)g.page0 << 16);
-            if (p.overlap && retry) {
-                HIP_TRY(hipEventRecord(c->ev_join, c->stream2));
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            }
-            if (gi && !second) HIP_TRY(hipMemsetAsync(ctr, 0, 4, q));
+            const InflatePlan::Group g = retry ? InflatePlan::Group{0, n, 0, (uint32_t)p.segs.size()} : p.groups[gi];
+            if (gi) HIP_TRY(hipMemsetAsync(dnext, 0, 4, q));
             { Timed t(c, SPNG_K_PINF_FIND, q); HIP_TRY(launch_pinf2_find(ds, dg, g.g0, g.g1 - g.g0, retry, q)); }
-            if (second) HIP_TRY(hipStreamWaitEvent(q, c->ev_mid, 0));
             // block cuts: only a group with a stream they may be tried for takes the kernels that know them (the plan in front of
             // the decode, the join behind it, their instantiations of decode and scan); dnext[12 ..] = {tried, joined, streams redone}
             bool cuts = false;
@@ -921,38 +987,32 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
                 Timed t(c, SPNG_K_PINF_DECODE, q);
                 HIP_TRY(hipMemsetAsync(dc + g.g0, 0, (size_t)(g.g1 - g.g0) * sizeof(PCut), q));
                 HIP_TRY(launch_pinf2_cutplan(ds + g.s0, g.s1 - g.s0, dg, dc, dnext + 12, q));
-                HIP_TRY(launch_pinf2_cutdecode(ds, dg, dc, g.g0, g.g1 - g.g0, (uint32_t *)c->d_log, pool, ctr, g.pages, q));
-                HIP_TRY(launch_pinf2_cutjoin(ds, dg, dc, g.g0, g.g1 - g.g0, (uint32_t *)c->d_log, pool, ctr, g.pages, dnext + 12, q));
+                HIP_TRY(launch_pinf2_cutdecode(ds, dg, dc, g.g0, g.g1 - g.g0, dlog, pool, dnext, pages, q));
+                HIP_TRY(launch_pinf2_cutjoin(ds, dg, dc, g.g0, g.g1 - g.g0, dlog, pool, dnext, pages, dnext + 12, q));
             } else
-            { Timed t(c, SPNG_K_PINF_DECODE, q); HIP_TRY(launch_pinf2_decode(ds, dg, g.g0, g.g1 - g.g0, (uint32_t *)c->d_log, pool, ctr, g.pages, retry, q)); }
-            if (p.overlap && gi == 0) HIP_TRY(hipEventRecord(c->ev_mid, q));
+            { Timed t(c, SPNG_K_PINF_DECODE, q); HIP_TRY(launch_pinf2_decode(ds, dg, g.g0, g.g1 - g.g0, dlog, pool, dnext, pages, retry, q)); }
             PPart *dparts = p.pmax ? a.dev<PPart>(p.parts_at) + (size_t)g.s0 * p.pmax : nullptr;
             const uint32_t pm = retry ? 0u : p.pmax;                 // (the retry pass: one workgroup per stream)
             if (cuts) HIP_TRY(launch_pinf2_cutscan(ds + g.s0, g.s1 - g.s0, dg, dc, dparts, dnext + 12, q));
             else HIP_TRY(launch_pinf2_scan(ds + g.s0, g.s1 - g.s0, dg, dparts, retry, q));
             {
                 Timed t(c, SPNG_K_PINF_RESOLVE, q);
-                // (the parts behind the first on the second stream, beside the first parts: 79 KB -- 93 KB when they have a CU each -- and 61 KB of LDS share a CU)
-                hipStream_t q2 = q;
-                if (pm && !p.overlap) {
-                    if (!c->stream2) {
-                        HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-                        for (hipEvent_t *e : {&c->ev_fork, &c->ev_mid, &c->ev_join}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-                    }
-                    q2 = c->stream2;
-                    HIP_TRY(hipEventRecord(c->ev_fork, q));
-                    HIP_TRY(hipStreamWaitEvent(q2, c->ev_fork, 0));
-                }
-                if (pm) HIP_TRY(launch_pinf2_parts(ds + g.s0, g.s1 - g.s0, dg, (uint32_t *)c->d_log, pool, g.pages, dr, dd + g.s0, dparts, pm,
-                                                   (uint16_t *)c->d_sym, q2));
-                HIP_TRY(launch_pinf2_resolve(ds + g.s0, g.s1 - g.s0, dg, (uint32_t *)c->d_log, pool, g.pages, dr, dd + g.s0, dparts, pm, retry, q));
                 if (pm) {
-                    if (q2 != q) { HIP_TRY(hipEventRecord(c->ev_join, q2)); HIP_TRY(hipStreamWaitEvent(q, c->ev_join, 0)); }
+                    // (the parts behind the first on the second stream, beside the first parts: 79 KB -- 93 KB when they have a CU each -- and 61 KB of LDS share a CU)
+                    if (int32_t st = second_stream(c)) return st;
+                    HIP_TRY(hipEventRecord(c->ev_fork, q));
+                    HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+                    HIP_TRY(launch_pinf2_parts(ds + g.s0, g.s1 - g.s0, dg, dlog, pool, pages, dr, dd + g.s0, dparts, pm, (uint16_t *)c->d_sym, c->stream2));
+                }
+                HIP_TRY(launch_pinf2_resolve(ds + g.s0, g.s1 - g.s0, dg, dlog, pool, pages, dr, dd + g.s0, dparts, pm, retry, q));
+                if (pm) {
+                    HIP_TRY(hipEventRecord(c->ev_join, c->stream2));
+                    HIP_TRY(hipStreamWaitEvent(q, c->ev_join, 0));
                     HIP_TRY(launch_pinf2_join(ds + g.s0, g.s1 - g.s0, dr, dd + g.s0, dparts, pm, (uint16_t *)c->d_sym,
                                               (uint8_t *)c->d_win + (size_t)g.s0 * pm * 32768, q));
                 }
             }
-            HIP_TRY(launch_pinf2_account(ctr, dnext + 8, g.pages, q));
+            HIP_TRY(launch_pinf2_account(dnext, dnext + 8, pages, q));
         }
         if (c->cut_stats_valid) HIP_TRY(hipMemcpyAsync(c->h_pool_used + 8, dnext + 12, 12, hipMemcpyDeviceToHost, c->stream));
         if (!c->pool_pending) {
@@ -963,47 +1023,8 @@ static int32_t launch_inflate_plan(spng_ctx *c, InflatePlan &p, Arena &a, spng_r
             c->pool_pending = true;
         }
     }
-    if (p.parallel && getenv("SPNG_TRACE_PINFLATE")) {
-        // diagnostic: how far every stream got in the pipeline (synchronises; never on by default)
-        std::vector<PStream> hs(n);
-        std::vector<PSeg> hg(p.segs.size());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(hs.data(), a.dev<PStream>(p.streams_at), n * sizeof(PStream), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hg.data(), a.dev<PSeg>(p.segs_at), hg.size() * sizeof(PSeg), hipMemcpyDeviceToHost));
-        {
-            // anomalies over the whole batch: segments without a start, segments that did not end on the next one
-            uint64_t nostart = 0, fail = 0, skipped = 0; uint32_t shown = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                const PStream &st = hs[i];
-                for (uint32_t k = 0; k < st.seg_count; ++k) {
-                    const PSeg &sg = hg[st.seg_first + k];
-                    const bool a = sg.start_bit == ~0ull, b = !a && sg.status != PSEG_CONT && sg.status != PSEG_FINAL, cskip = !a && !b && sg.status == PSEG_CONT && sg.next != k + 1;
-                    nostart += a; fail += b; skipped += cskip;
-                    if ((a || b || cskip) && shown < 12) {
-                        ++shown;
-                        fprintf(stderr, "[pinflate] anomaly: stream %u seg %u/%u start %lld end %lld status %d next %u ntok %llu\n", i, k, st.seg_count,
-                                (long long)sg.start_bit, (long long)sg.end_bit, sg.status, sg.next, (unsigned long long)sg.ntok);
-                    }
-                }
-            }
-            fprintf(stderr, "[pinflate] %u streams, %zu segments in %zu groups, pool %u pages: %llu without a start, %llu failed, %llu ran past the next start\n", n,
-                    hg.size(), p.groups.size(), p.pool_pages, (unsigned long long)nostart, (unsigned long long)fail, (unsigned long long)skipped);
-        }
-        for (uint32_t i = 0; i < n && i < 4; ++i) {
-            const PStream &st = hs[i];
-            fprintf(stderr, "[pinflate] stream %u: len %llu segs %u seg_bytes %llu ok %d pass %u ntok %llu end_bit %llu\n", i,
-                    (unsigned long long)st.src_len, st.seg_count, (unsigned long long)st.seg_bytes, st.ok, st.pass,
-                    (unsigned long long)st.ntok, (unsigned long long)st.end_bit);
-            for (uint32_t k = 0; k < st.seg_count && k < 12; ++k) {
-                const PSeg &sg = hg[st.seg_first + k];
-                fprintf(stderr, "   seg %u: start %lld end %lld status %d used %u ntok %llu tok_base %llu next %u", k,
-                        (long long)sg.start_bit, (long long)sg.end_bit, sg.status, sg.used, (unsigned long long)sg.ntok,
-                        (unsigned long long)sg.tok_base, sg.next);
-                if (sg.head) fprintf(stderr, " head %u", sg.head);
-                fprintf(stderr, "\n");
-            }
-        }
-    }
+    if (p.parallel && getenv("SPNG_TRACE_PINFLATE"))
+        if (int32_t st = trace_inflate_plan(c, p, a)) return st;
     {
         Timed t(c, SPNG_K_INFLATE);
         HIP_TRY(launch_inflate(a.dev<InflateJob>(p.jobs_at), n, dr, c->stream));
@@ -1067,11 +1088,7 @@ static int32_t inflate_batch(spng_ctx *c, const spng_stream_desc *descs, const u
     poison_results_kernel<<<(count + 255) / 256, 256, 0, c->stream>>>(dr, count);
     HIP_TRY(hipGetLastError());
     if (int32_t st = launch_inflate_plan(c, plan, a, dr)) return st;
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, count * sizeof(spng_result), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
 }
 
 int32_t spng_inflate_batch(spng_ctx *c, const spng_stream_desc *descs, uint32_t count,
@@ -1116,11 +1133,7 @@ int32_t spng_unfilter_batch(spng_ctx *c, const spng_image_desc *descs, uint32_t 
     if (int32_t st = launch_plan(c, plan, a, slots, nullptr)) return st;
     finish_decode_kernel<<<(count + 255) / 256, 256, 0, c->stream>>>(dr, a.dev<uint64_t>(expected), count);
     HIP_TRY(hipGetLastError());
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, count * sizeof(spng_result), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
 }
 
 int32_t spng_unfilter_resume_batch(spng_ctx *c, const spng_image_desc *descs, void *const *d_work, const uint64_t *h_prev_len,
@@ -1263,11 +1276,7 @@ int32_t spng_decode_batch(spng_ctx *c, const spng_image_desc *descs, uint32_t co
     if (int32_t st = launch_plan(c, plan, a, slots, dr)) return st;
     finish_decode_kernel<<<(count + 255) / 256, 256, 0, c->stream>>>(dr, a.dev<uint64_t>(expected), count);
     HIP_TRY(hipGetLastError());
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, res_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_results, dr, res_bytes);
 }
 
 // ---- host-pointer convenience wrappers ---------------------------------------------------------
@@ -1353,8 +1362,7 @@ int32_t spng_adler32(spng_ctx *c, const void *data, uint64_t n, uint32_t *out)
             HIP_TRY(launch_adler_partial((const uint8_t *)dd.p, n, chunk, (uint64_t *)dp.p, blocks, c->stream));
         }
         std::vector<uint64_t> part((size_t)blocks * 2);
-        HIP_TRY(hipMemcpyAsync(part.data(), dp.p, (size_t)blocks * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int32_t st = read_back(c, part.data(), dp.p, (size_t)blocks * 16)) return st;
         for (uint32_t i = 0; i < blocks; ++i) {
             const uint64_t len = n - (uint64_t)i * chunk < chunk ? n - (uint64_t)i * chunk : chunk;
             s2 = (uint32_t)((s2 + (len % 65521) * s1 + part[2 * i + 1] % 65521) % 65521);
@@ -1414,11 +1422,7 @@ int32_t spng_filter_batch(spng_ctx *c, const spng_image_desc *descs, uint32_t co
     }
     init_results_kernel<<<(count + 255) / 256, 256, 0, c->stream>>>(dr, a.dev<uint64_t>(wslot), count);
     HIP_TRY(hipGetLastError());
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, count * sizeof(spng_result), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
 }
 
 int32_t spng_filter(spng_ctx *c, const void *storage,
@@ -1477,11 +1481,7 @@ int32_t spng_lex_batch(spng_ctx *c, const spng_file_desc *files, uint32_t count,
         HIP_TRY(launch_lex(a.dev<spng_file_desc>(fslot), count, dout, a.dev<uint8_t>(tslot), a.dev<uint64_t>(atslot), a.dev<uint8_t>(wslot),
                            max_listed, c->stream));
     }
-    if (h_infos) {
-        HIP_TRY(hipMemcpyAsync(h_infos, dout, count * sizeof(spng_lexed), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_infos, dout, count * sizeof(spng_lexed));
 }
 
 int32_t spng_write_idat_batch(spng_ctx *c, const spng_chunking_desc *descs, uint32_t count,
@@ -1507,11 +1507,7 @@ int32_t spng_write_idat_batch(spng_ctx *c, const spng_chunking_desc *descs, uint
     if (int32_t st = c->upload(0, upload)) return st;
     spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
     { Timed t(c, SPNG_K_LEX); HIP_TRY(launch_write_idat(a.dev<spng_chunking_desc>(dslot), count, (uint32_t)(most > 4096 ? 4096 : most), dr, c->stream)); }
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, count * sizeof(spng_result), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
 }
 
 int32_t spng_crc32(spng_ctx *c, const void *data, uint64_t n, uint32_t *out)
@@ -1526,8 +1522,7 @@ int32_t spng_crc32(spng_ctx *c, const void *data, uint64_t n, uint32_t *out)
         HIP_TRY(dd.alloc(n)); HIP_TRY(dp.alloc((size_t)pieces * 4));
         HIP_TRY(hipMemcpyAsync(dd.p, data, n, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(launch_crc_partial((const uint8_t *)dd.p, n, piece, (uint32_t *)dp.p, pieces, c->stream));
-        HIP_TRY(hipMemcpyAsync(part.data(), dp.p, (size_t)pieces * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (int32_t st = read_back(c, part.data(), dp.p, (size_t)pieces * 4)) return st;
     }
     *out = crc32_fold(part.data(), pieces, n, piece);
     return SPNG_DONE;
@@ -1675,15 +1670,35 @@ static int32_t deflate_slab(spng_ctx *c, uint64_t floor, const std::function<uin
     for (;;) {
         bool single = false;
         const uint64_t slab = plan(budget, single);
-        if (slab <= c->graph_cap) return SPNG_DONE;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_graph) HIP_TRY(hipFree(c->d_graph));
-        c->d_graph = nullptr; c->graph_cap = 0;
-        if (hipMalloc(&c->d_graph, slab) == hipSuccess) { c->graph_cap = slab; return SPNG_DONE; }
-        (void)hipGetLastError();
+        bool failed = false;
+        if (int32_t st = c->grow(c->d_graph, c->graph_cap, slab, 0, &failed)) return st;
+        if (!failed) return SPNG_DONE;
         if (single) return fail_text("deflate: no device memory for the search scratch of a single stream");
         budget /= 2;
     }
+}
+
+// The rounds of one group of deflate streams: the search of round r + 1 beside the parse of round r, on a stream of its own
+// (candidates are a function of the input alone; the parse is a wave or two per stream and leaves most of the chip idle): two
+// sets of records, by round parity.  searched[p] / parsed[p] (c->ev_dfl[p] / [2 + p]): the last search into / parse out of the
+// records of parity p.  search(parity) launches on c->stream2, parse(parity) on c->stream.
+static int32_t deflate_round_pipeline(spng_ctx *c, uint32_t rounds, const std::function<hipError_t(uint32_t)> &search,
+                                      const std::function<hipError_t(uint32_t)> &parse)
+{
+    if (int32_t st = second_stream(c)) return st;
+    if (!c->ev_dfl[0]) for (hipEvent_t &e : c->ev_dfl) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t par = r & 1;
+        if (r >= 2) HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_dfl[2 + par], 0));     // the parse of round r - 2 is done with these records
+        { Timed t(c, SPNG_K_DFL_SEARCH, c->stream2); HIP_TRY(search(par)); }
+        HIP_TRY(hipEventRecord(c->ev_dfl[par], c->stream2));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dfl[par], 0));
+        { Timed t(c, SPNG_K_DFL_PARSE); HIP_TRY(parse(par)); }
+        HIP_TRY(hipEventRecord(c->ev_dfl[2 + par], c->stream));
+    }
+    return SPNG_DONE;
 }
 
 // One pass of the two-kernel full search (deflate.hip, "round 4") over jobs[0, n): per stream 11 bytes of scratch per vertex of
@@ -1784,26 +1799,13 @@ static int32_t deflate_full_pass(spng_ctx *c, const DeflateJob *jobs, size_t n, 
         for (size_t i = l.first; i < l.last; ++i) rounds = rounds_of[i] > rounds ? rounds_of[i] : rounds;
         const D2Stream *ds = a.dev<D2Stream>(sslot) + l.first;
         HIP_TRY(launch_deflate2_begin(ds, cnt, c->stream));
-        // The search of round r + 1 beside the parse of round r, on a stream of its own (candidates are a function of the input
-        // alone; the parse is one wave per stream and leaves most of the chip idle): two sets of records and pools, by round parity.
-        // searched[p] / parsed[p]: the last search into / parse out of the records of parity p.
-        if (!c->stream2) {
-            HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-            for (hipEvent_t *e : {&c->ev_fork, &c->ev_mid, &c->ev_join}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-        if (!c->ev_dfl[0]) for (hipEvent_t &e : c->ev_dfl) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        for (uint32_t r = 0; r < rounds; ++r) {
-            const uint32_t par = r & 1;
-            if (r >= 2) HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_dfl[2 + par], 0));     // the parse of round r - 2 is done with these records
-            { Timed t(c, SPNG_K_DFL_SEARCH, c->stream2); HIP_TRY(launch_deflate2_search(ds, cnt, l.cps, l.chunk, (uint32_t *)pools[par],
-                                                                            (unsigned long long *)(pools[par] + l.pool), l.pool / 4, (uint32_t *)rings, par, c->stream2)); }
-            HIP_TRY(hipEventRecord(c->ev_dfl[par], c->stream2));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dfl[par], 0));
-            { Timed t(c, SPNG_K_DFL_PARSE); HIP_TRY(launch_deflate2_parse(ds, cnt, (uint32_t *)pools[par], dr, par, c->stream)); }
-            HIP_TRY(hipEventRecord(c->ev_dfl[2 + par], c->stream));
-        }
+        // (two pools too, by round parity)
+        auto search = [&](uint32_t par) {
+            return launch_deflate2_search(ds, cnt, l.cps, l.chunk, (uint32_t *)pools[par], (unsigned long long *)(pools[par] + l.pool), l.pool / 4,
+                                          (uint32_t *)rings, par, c->stream2);
+        };
+        auto parse = [&](uint32_t par) { return launch_deflate2_parse(ds, cnt, (uint32_t *)pools[par], dr, par, c->stream); };
+        if (int32_t st = deflate_round_pipeline(c, rounds, search, parse)) return st;
     }
     return SPNG_DONE;
 }
@@ -1820,9 +1822,7 @@ static int32_t deflate_full_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted,
     auto unfinished = [&](size_t n) -> int32_t {
         HIP_TRY(launch_deflate2_failed(a.dev<D2Stream>(sslot), (uint32_t)n, a.dev<uint32_t>(fslot), c->stream));
         failed.assign(n + 1, 0);
-        HIP_TRY(hipMemcpyAsync(failed.data(), a.dev<uint32_t>(fslot), (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SPNG_DONE;
+        return read_back(c, failed.data(), a.dev<uint32_t>(fslot), (n + 1) * 4);
     };
     if (int32_t st = deflate_full_pass(c, sorted.data() + first, nfull, false, dr, a, sslot, tslot)) return st;
     if (int32_t st = unfinished(nfull)) return st;
@@ -1926,11 +1926,6 @@ static int32_t deflate_fast_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted,
         }
     }
     if (int32_t st = c->upload(sslot, tslot + nfast * sizeof(D1State))) return st;
-    if (!c->stream2) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        for (hipEvent_t *e : {&c->ev_fork, &c->ev_mid, &c->ev_join}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
-    if (!c->ev_dfl[0]) for (hipEvent_t &e : c->ev_dfl) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (auto &gr : groups) {
         const uint32_t cnt = (uint32_t)(gr.last - gr.first);
         uint32_t cps = (256 + cnt - 1) / cnt;                 // (as the level >= 8 search: one round of workgroups where the streams are few)
@@ -1943,21 +1938,11 @@ static int32_t deflate_fast_rounds(spng_ctx *c, std::vector<DeflateJob> &sorted,
         }
         const D3Stream *ds = a.dev<D3Stream>(sslot) + (gr.first - first);
         HIP_TRY(launch_deflate3_begin(ds, cnt, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        for (uint32_t r = 0; r < rounds; ++r) {
-            const uint32_t par = r & 1;
-            if (r >= 2) HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_dfl[2 + par], 0));     // the parse of round r - 2 is done with these records
-            { Timed t(c, SPNG_K_DFL_SEARCH, c->stream2); HIP_TRY(launch_deflate3_search(ds, cnt, cps, chunk, par, c->stream2)); }
-            HIP_TRY(hipEventRecord(c->ev_dfl[par], c->stream2));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_dfl[par], 0));
-            {
-                Timed t(c, SPNG_K_DFL_PARSE);
-                if (gr.blocks) HIP_TRY(launch_deflate4_round(ds, cnt, maxb, dr, par, c->stream));
-                else HIP_TRY(launch_deflate3_parse(ds, cnt, dr, par, c->stream));
-            }
-            HIP_TRY(hipEventRecord(c->ev_dfl[2 + par], c->stream));
-        }
+        auto search = [&](uint32_t par) { return launch_deflate3_search(ds, cnt, cps, chunk, par, c->stream2); };
+        auto parse = [&](uint32_t par) {
+            return gr.blocks ? launch_deflate4_round(ds, cnt, maxb, dr, par, c->stream) : launch_deflate3_parse(ds, cnt, dr, par, c->stream);
+        };
+        if (int32_t st = deflate_round_pipeline(c, rounds, search, parse)) return st;
     }
     return SPNG_DONE;
 }
@@ -1988,8 +1973,9 @@ static int32_t deflate_launch(spng_ctx *c, std::vector<DeflateJob> &jobs, spng_r
     return SPNG_DONE;
 }
 
-int32_t spng_deflate_batch(spng_ctx *c, const spng_stream_desc *descs, const int32_t *levels, uint32_t count,
-                           spng_result *d_results, spng_result *h_results)
+// One-shot streams (d_states == NULL) and streams that arrive in pieces (spng_deflate_resume_batch: d_states, last, h_state).
+static int32_t deflate_batch(spng_ctx *c, const spng_stream_desc *descs, const int32_t *levels, void *const *d_states, const uint8_t *last,
+                             const uint64_t *h_state, uint32_t count, spng_result *d_results, spng_result *h_results)
 {
     if (!c || (!descs && count) || !levels) return SPNG_E_ARGUMENT;
     if (!count) return SPNG_DONE;
@@ -2000,51 +1986,19 @@ int32_t spng_deflate_batch(spng_ctx *c, const spng_stream_desc *descs, const int
     for (uint32_t i = 0; i < count; ++i) {
         // spng_stream_desc.reserved: window exponent 8 ... 15 (0 = 15, as PNG always uses)
         const int32_t e = descs[i].reserved ? descs[i].reserved : 15;
-        if ((!descs[i].d_src && descs[i].src_len) || !descs[i].d_dst || e < 8 || e > 15 || descs[i].format < SPNG_FORMAT_ZLIB ||
-            descs[i].format > SPNG_FORMAT_GZIP) return SPNG_E_ARGUMENT;
-        gzip = gzip || descs[i].format == SPNG_FORMAT_GZIP;
-        jobs[i] = DeflateJob{(const uint8_t *)descs[i].d_src, (uint8_t *)descs[i].d_dst, descs[i].src_len,
-                             descs[i].dst_cap, descs[i].format, levels[i], i,
-                             descs[i].format == SPNG_FORMAT_IOS ? 15u : (uint32_t)e, 0};
-    }
-    if (int32_t st = c->reserve(count * (sizeof(DeflateJob) + sizeof(spng_result) + sizeof(D2Stream) + sizeof(D2State) + sizeof(D3Stream) + sizeof(D1State) + 1024 + (gzip ? 4 * (size_t)gzip_pieces() : 0)) + 8192)) return st;
-    Arena a{c};
-    const size_t jslot = a.take(count * sizeof(DeflateJob));
-    const size_t res = a.take(count * sizeof(spng_result));
-    const size_t gzparts = gzip ? a.take((size_t)count * 4 * gzip_pieces()) : (size_t)-1;
-    spng_result *dr = d_results ? d_results : a.dev<spng_result>(res);
-    if (int32_t st = deflate_launch(c, jobs, dr, a, jslot, gzparts)) return st;
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, count * sizeof(spng_result), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
-}
-
-uint64_t spng_deflate_state_bytes(void) { return deflate_state_bytes(); }
-
-int32_t spng_deflate_resume_batch(spng_ctx *c, const spng_stream_desc *descs, const int32_t *levels, void *const *d_states, const uint8_t *last,
-                                  const uint64_t *h_state, uint32_t count, spng_result *d_results, spng_result *h_results)
-{
-    if (!c || (!descs && count) || !levels || !d_states || !last) return SPNG_E_ARGUMENT;
-    if (!count) return SPNG_DONE;
-    HIP_TRY(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> g(c->mu);
-    std::vector<DeflateJob> jobs(count);
-    bool gzip = false;
-    for (uint32_t i = 0; i < count; ++i) {
-        const int32_t e = descs[i].reserved ? descs[i].reserved : 15;
-        if ((!descs[i].d_src && descs[i].src_len) || !descs[i].d_dst || !d_states[i] || e < 8 || e > 15 || descs[i].format < SPNG_FORMAT_ZLIB ||
-            descs[i].format > SPNG_FORMAT_GZIP) return SPNG_E_ARGUMENT;
+        if ((!descs[i].d_src && descs[i].src_len) || !descs[i].d_dst || (d_states && !d_states[i]) || e < 8 || e > 15 ||
+            descs[i].format < SPNG_FORMAT_ZLIB || descs[i].format > SPNG_FORMAT_GZIP) return SPNG_E_ARGUMENT;
         gzip = gzip || descs[i].format == SPNG_FORMAT_GZIP;
         DeflateJob j{};
         j.src = (const uint8_t *)descs[i].d_src; j.dst = (uint8_t *)descs[i].d_dst; j.src_len = descs[i].src_len; j.dst_cap = descs[i].dst_cap;
         j.format = descs[i].format; j.level = levels[i]; j.image = i; j.exponent = descs[i].format == SPNG_FORMAT_IOS ? 15u : (uint32_t)e;
-        j.more = last[i] ? 0u : 1u; j.state = (D1State *)d_states[i];
-        if (h_state) { j.plan_pos = h_state[2 * i]; j.plan_limit = (uint32_t)h_state[2 * i + 1]; j.plan_aux = h_state[2 * i + 1]; }
-        // (a state is only ever what an earlier call handed out: the search position it names lies inside what the input allows --
-        // the match arrays and the round count of levels 0-7 are sized from it)
-        if (j.plan_pos > j.src_len || (levels[i] < 8 && j.plan_aux > deflate3_end(j.src_len, j.more != 0))) return SPNG_E_ARGUMENT;
+        if (d_states) {
+            j.more = last[i] ? 0u : 1u; j.state = (D1State *)d_states[i];
+            if (h_state) { j.plan_pos = h_state[2 * i]; j.plan_limit = (uint32_t)h_state[2 * i + 1]; j.plan_aux = h_state[2 * i + 1]; }
+            // (a state is only ever what an earlier call handed out: the search position it names lies inside what the input allows --
+            // the match arrays and the round count of levels 0-7 are sized from it)
+            if (j.plan_pos > j.src_len || (levels[i] < 8 && j.plan_aux > deflate3_end(j.src_len, j.more != 0))) return SPNG_E_ARGUMENT;
+        }
         jobs[i] = j;
     }
     if (int32_t st = c->reserve(count * (sizeof(DeflateJob) + sizeof(spng_result) + sizeof(D2Stream) + sizeof(D2State) + sizeof(D3Stream) + sizeof(D1State) + 1024 + (gzip ? 4 * (size_t)gzip_pieces() : 0)) + 8192)) return st;
@@ -2054,11 +2008,22 @@ int32_t spng_deflate_resume_batch(spng_ctx *c, const spng_stream_desc *descs, co
     const size_t gzparts = gzip ? a.take((size_t)count * 4 * gzip_pieces()) : (size_t)-1;
     spng_result *dr = d_results ? d_results : a.dev<spng_result>(res);
     if (int32_t st = deflate_launch(c, jobs, dr, a, jslot, gzparts)) return st;
-    if (h_results) {
-        HIP_TRY(hipMemcpyAsync(h_results, dr, count * sizeof(spng_result), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return SPNG_DONE;
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+int32_t spng_deflate_batch(spng_ctx *c, const spng_stream_desc *descs, const int32_t *levels, uint32_t count,
+                           spng_result *d_results, spng_result *h_results)
+{
+    return deflate_batch(c, descs, levels, nullptr, nullptr, nullptr, count, d_results, h_results);
+}
+
+uint64_t spng_deflate_state_bytes(void) { return deflate_state_bytes(); }
+
+int32_t spng_deflate_resume_batch(spng_ctx *c, const spng_stream_desc *descs, const int32_t *levels, void *const *d_states, const uint8_t *last,
+                                  const uint64_t *h_state, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!d_states || !last) return SPNG_E_ARGUMENT;
+    return deflate_batch(c, descs, levels, d_states, last, h_state, count, d_results, h_results);
 }
 
 int32_t spng_deflate(spng_ctx *c, const void *src, uint64_t n, int32_t format, int32_t level,
@@ -2140,11 +2105,9 @@ int32_t spng_trim(spng_ctx *c)
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
     if (c->stream_out) HIP_TRY(hipStreamSynchronize(c->stream_out));
-    void **bufs[] = {&c->d_graph, &c->d_log, &c->d_tok, &c->d_sym, &c->d_win, &c->d_multi};
-    size_t *caps[] = {&c->graph_cap, &c->log_cap, &c->tok_cap, &c->sym_cap, &c->win_cap, &c->multi_cap};
-    for (int i = 0; i < 6; ++i) {
-        if (*bufs[i]) HIP_TRY(hipFree(*bufs[i]));
-        *bufs[i] = nullptr; *caps[i] = 0;
+    for (auto b : c->batch_buffers()) {
+        if (*b.p) HIP_TRY(hipFree(*b.p));
+        *b.p = nullptr; *b.cap = 0;
     }
     c->pool_ratio = 0; c->block_bytes = 0; c->sym_failed = 0;  // (what the token pool had learned went with it)
     return SPNG_DONE;
@@ -2191,12 +2154,7 @@ int32_t spng_decode_batch_multi(spng_ctx *const *ctxs, uint32_t n_ctx, const spn
         {
             std::lock_guard<std::mutex> g(c->mu);
             const size_t need = (size_t)n * sizeof(spng_result);
-            if (need > c->multi_cap) {
-                if (hipError_t e = hipStreamSynchronize(c->stream); e != hipSuccess) { status = fail_hip(e, "hipStreamSynchronize"); break; }
-                if (c->d_multi) { (void)hipFree(c->d_multi); c->d_multi = nullptr; c->multi_cap = 0; }
-                if (hipError_t e = hipMalloc(&c->d_multi, need + need / 2); e != hipSuccess) { status = fail_hip(e, "hipMalloc"); break; }
-                c->multi_cap = need + need / 2;
-            }
+            if ((status = c->grow(c->d_multi, c->multi_cap, need, need / 2)) != SPNG_DONE) break;
             if (leaves) {
                 if (!c->stream_out) {
                     if (hipError_t e = hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking); e != hipSuccess) { status = fail_hip(e, "hipStreamCreateWithFlags"); break; }

@@ -125,12 +125,11 @@ def test_pipeline_batch_of_ragged_streams(gpu):
 
 
 @pytest.mark.parametrize("pool", [0, 1 << 20])
-def test_two_halves_on_two_streams(gpu, pool):
-    """SPNG_CFG_INFLATE_OVERLAP: the batch in two halves, each with its share of the token pool, the decode of the second
-    beside the resolve of the first on a second stream (opt-in: it is slower than one pass).  Same verdicts and bytes
-    as the oracle for every stream -- valid, truncated, corrupted, empty -- also when the pool is far too small and the
-    streams that found it empty take the retry pass behind the join; and again in the next call (events, counters and
-    the second stream are the context's)."""
+def test_mixed_batch_in_repeated_calls_with_dry_pool_retry(gpu, pool):
+    """A mixed batch of small segments, three calls on one context.  Same verdicts and bytes as the oracle for every stream
+    -- valid, truncated, corrupted, wrong Adler-32, empty, one byte -- with the automatic pool, and also when the pool is far
+    too small and the streams that found it empty take the retry pass; and again in the next calls (the page counters, the
+    events and what the last batch taught are the context's)."""
     s = gpu.load()
     rng = np.random.default_rng(6)
     datas = [scanlines(40 + i, int(4096 * rng.integers(1, 300))) for i in range(21)] + [b"", b"a", bytes(300000)]
@@ -140,7 +139,6 @@ def test_two_halves_on_two_streams(gpu, pool):
     bad = bytearray(zs[9]); bad[len(bad) // 3] ^= 0x42; zs[9] = bytes(bad)
     d_in = [s.to_device(z) for z in zs]
     caps = [len(d) + 16 for d in datas]
-    s.configure(spng.CFG_INFLATE_OVERLAP, spng.OVERLAP_ALWAYS)
     s.configure(spng.CFG_SEGMENT_BYTES, 8192)
     s.configure(spng.CFG_TOKEN_BYTES, pool)
     try:
@@ -157,9 +155,30 @@ def test_two_halves_on_two_streams(gpu, pool):
             if pool == 0:
                 assert sum(r.reserved == 1 for r in res) >= 20       # (the pipeline's own work, not the serial kernel's)
     finally:
-        s.configure(spng.CFG_INFLATE_OVERLAP, spng.OVERLAP_AUTO)
         s.configure(spng.CFG_SEGMENT_BYTES, 0)
         s.configure(spng.CFG_TOKEN_BYTES, 0)
+
+
+def test_reserved_configure_keys_are_refused(gpu):
+    """Keys 4 and 6 of spng_configure named modes that have been removed: both are refused with SPNG_E_ARGUMENT whatever the
+    value, and the refusals leave the context as it was -- the next inflate_batch on it matches the oracle."""
+    s = gpu.load()
+    for key in (4, 6):
+        for value in (0, 1):
+            with pytest.raises(spng.SpngError) as err:
+                s.configure(key, value)
+            assert err.value.status == spng.E_ARGUMENT, (key, value)
+    datas = [scanlines(90 + i, 4096 * (40 + 30 * i)) for i in range(4)] + [b""]
+    zs = [zlib.compress(d, 6) for d in datas]
+    zs[1] = zs[1][:len(zs[1]) // 2]
+    caps = [len(d) + 16 for d in datas]
+    outs, res = s.inflate_batch([s.to_device(z) for z in zs], caps)
+    for i, z in enumerate(zs):
+        st, out, used, aux = ph.orc_inflate(z, 0, cap=caps[i])
+        assert (res[i].status, res[i].written) == (st, len(out)), (i, res[i].status, st)
+        assert bytes(outs[i][:len(out)].cpu().numpy()) == out, i
+        if st == 0:
+            assert res[i].consumed == used
 
 
 def test_retry_pass_takes_the_streams_a_dry_pool_left(gpu):

@@ -8,7 +8,12 @@ the medians of its decode and resolve stages and of the host's wall time, the no
 cuts, the single-stream legs are measured once more under SPNG_BLOCK_CUT_NEVER as a cross-check; a library without them (an older
 build: the baseline) runs the same legs through the exports it has.
 
-    python bench_one_block.py [--repeats 7] [--warmup 2] [--legs fixed,dynamic,image1,image32]
+Pushed legs (pushed_fixed, pushed_dynamic): the same two streams through spng_inflate_resume_batch, as 64 KiB and then 8 equal pieces,
+the state handed from call to call.  Per leg: the sum over the pushes of the library's own HIP-event times (SPNG_K_PINFLATE +
+SPNG_K_INFLATE: the pipeline and the serial kernel that takes what the pipeline leaves), median over the repeats, the same per
+push, and spng_cut_stats per push.
+
+    python bench_one_block.py [--repeats 7] [--warmup 2] [--legs fixed,dynamic,image1,image32,pushed_fixed,pushed_dynamic]
 """
 import argparse
 import ctypes
@@ -105,6 +110,45 @@ def main():
             finally:
                 s.configure(spng.CFG_BLOCK_CUT_BYTES, 0)
 
+    def pushed_leg(name, data, z):
+        first, k = 65536, 8
+        step = (len(z) - first + k - 1) // k
+        ends = [first] + [min(len(z), first + (i + 1) * step) for i in range(k)]
+        d_z = s.to_device(z)
+        d_out = s.empty(len(data) + 64)
+        torch.cuda.synchronize()
+
+        def once():
+            state, per, stats, res = (0, 0, 0, 0), [], [], None
+            s.profile(True)
+            before = 0.0
+            for n in ends:
+                res, state = s.inflate_resume(d_z, n, d_out, spng.FORMAT_ZLIB, state)
+                assert res.status == (0 if n == len(z) else 1), (name, n, res.status)
+                now = s.profile_get(spng.K_PINFLATE)[0] + s.profile_get(spng.K_INFLATE)[0]
+                per.append(now - before)
+                before = now
+                if has_cuts:
+                    stats.append(list(s.cut_stats()))
+            s.profile(False)
+            assert res.written == len(data) and res.consumed == len(z), name
+            return per, stats
+
+        for _ in range(args.warmup):
+            once()
+        runs = [once() for _ in range(args.repeats)]
+        assert bytes(d_out[:len(data)].cpu().numpy()) == data, name
+        totals = [sum(per) for per, _ in runs]
+        med = statistics.median(totals)
+        out[name] = {"ms": round(med, 3), "ms_min": round(min(totals), 3), "ms_max": round(max(totals), 3), "repeats": len(runs),
+                     "MB_per_s": round(len(data) / 1e6 / (med * 1e-3), 1), "pushes": len(ends), "in_bytes": len(z), "out_bytes": len(data),
+                     "ms_per_push": [round(statistics.median(per[i] for per, _ in runs), 3) for i in range(len(ends))],
+                     "cut_stats_per_push": runs[-1][1]}
+
+    if "pushed_fixed" in legs:
+        pushed_leg("pushed_fixed_32MiB", *ob.one_fixed_block(11, 32 << 20))
+    if "pushed_dynamic" in legs:
+        pushed_leg("pushed_dynamic_64MiB", *ob.one_dynamic_block(7, 68 << 20))
     if "fixed" in legs:
         stream_leg("fixed_32MiB", *ob.one_fixed_block(11, 32 << 20))
     if "dynamic" in legs:

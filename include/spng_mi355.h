@@ -145,10 +145,12 @@ enum { SPNG_CFG_INFLATE_MODE = 0,   /* SPNG_INFLATE_AUTO: parallel pipeline, ser
                                               memory.  Streams that do not fit side by side go in groups */
        SPNG_CFG_MULTI_GROUPS = 8,          /* spng_decode_batch_multi: calls a context's shard is cut into when its rasters leave for another
                                               device (a group's copies run beside the next group's decode); 0 = 2, at most 2 */
-       SPNG_CFG_BLOCK_CUT_BYTES = 9,       /* parallel inflate, one-shot calls: a run of segments in which no block starts -- one huge block, or
+       SPNG_CFG_BLOCK_CUT_BYTES = 9,       /* parallel inflate: a run of segments in which no block starts -- one huge block, or
                                               blocks without a findable header (fixed codes) -- of at least so many compressed bytes (rounded up
                                               to whole segments) is cut: every segment of it decoded by a wave of its own from a guessed bit
-                                              and joined to the chain afterwards.  0 = 1 MiB; SPNG_BLOCK_CUT_NEVER = never */
+                                              and joined to the chain afterwards.  0 = 1 MiB; SPNG_BLOCK_CUT_NEVER = never.  One-shot calls, and
+                                              calls of spng_inflate_resume_batch whose state is not all zero and that bring at least so many
+                                              bytes behind their resume point (the same knob, the same threshold); results never depend on it */
        SPNG_CFG_COUNT = 10 };
 enum { SPNG_BLOCK_CUT_AUTO = 0, SPNG_BLOCK_CUT_NEVER = 1 };
 enum { SPNG_INFLATE_AUTO = 0, SPNG_INFLATE_SERIAL = 1 };
@@ -173,7 +175,9 @@ int32_t spng_profile_get(spng_ctx *ctx, int kernel, double *total_ms, uint64_t *
  * counterpart (measurement: bench.py's per-kernel design bytes).  Any pointer may be NULL. */
 int32_t spng_token_stats(spng_ctx *ctx, uint64_t *page_bytes, uint64_t *blocks, int32_t *ran_dry);
 /* Block cuts of the most recent parallel-inflate call (read back behind its kernels; any pointer may be NULL): cut segments tried,
- * cuts whose join to the chain was proven, streams that were decoded again without cuts because one of theirs was not. */
+ * cuts whose join to the chain was proven, streams that were decoded again without cuts because one of theirs was not.  Resumed
+ * calls report here like one-shot calls ((0, 0, 0) when no stream of the call passed the gate of SPNG_CFG_BLOCK_CUT_BYTES); a
+ * resumed call whose input ends inside the block it cut is not "decoded again": its tail goes to the serial kernel. */
 int32_t spng_cut_stats(spng_ctx *ctx, uint64_t *tried, uint64_t *joined, uint64_t *streams_redone);
 
 /* ---- decode: device batch entry points (asynchronous on the context's stream) -------------- */
@@ -197,7 +201,11 @@ int32_t spng_inflate_batch(spng_ctx *ctx, const spng_stream_desc *descs, uint32_
  * once more than 1 MiB of input lies inside ONE block, the next call goes on at the token the last one stopped in front of (the
  * serial kernel, its tables rebuilt from the block's header): a stream that is a single block pushed in k pieces costs O(n), not
  * O(n k).  (Whatever the blocks are: the pipeline's first segment starts at the resume point and takes stored and fixed blocks
- * like dynamic ones.)  Results as spng_inflate_batch, except `consumed` of a SPNG_NEED_MORE_INPUT result (above; gzip: a bit of the
+ * like dynamic ones.)  A call whose state is not all zero and that brings at least SPNG_CFG_BLOCK_CUT_BYTES (0: 1 MiB) behind its resume
+ * point -- the token of its state, else the block header -- is cut like a one-shot call: the pipeline starts at that very token with
+ * the tables of the block's header, decodes the block on many waves, and hands the tail the end of the input cuts off (at most
+ * two segments) to the serial kernel at the last proven join; smaller pushes keep the serial kernel.  A call with an all-zero
+ * state is a whole stream and is planned as it always was -- spng_inflate_batch is the entry that cuts a whole stream.  Results as spng_inflate_batch, except `consumed` of a SPNG_NEED_MORE_INPUT result (above; gzip: a bit of the
  * member's DEFLATE payload, like aux[0]); written / consumed of finished streams count from the start of the stream; the zlib
  * checksum -- the CRC-32 of a gzip member -- is verified over the whole output by the call that reports SPNG_DONE); formats
  * SPNG_FORMAT_ZLIB, SPNG_FORMAT_IOS and SPNG_FORMAT_GZIP (state = bits and bytes of the member's DEFLATE payload; the header is

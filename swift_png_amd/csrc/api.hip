@@ -610,8 +610,6 @@ struct InflatePlan {
 #ifndef SPNG_PARTS_MAX
 #define SPNG_PARTS_MAX 128        // parts a stream's chain is cut into at most (round 5: 64 -- one to four images left half the chip idle)
 #endif
-static constexpr uint64_t RESUME_SERIAL_BITS = 8ull << 20;      // 1 MiB of input inside one block: resume there, not at its header
-                                                                // (and, one-shot calls: cut there -- SPNG_CFG_BLOCK_CUT_BYTES)
 
 // What the last batch taught about token volume (its page count comes back behind its kernels: when the planning
 // figure would cut THIS batch into groups, waiting for that number is cheaper than not knowing it).
@@ -675,34 +673,52 @@ static int32_t cut_into_segments(spng_ctx *c, InflatePlan &p, uint64_t seg_bytes
         memset(&st, 0, sizeof st);
         st.src = j.src; st.dst = j.dst; st.src_len = j.src_len; st.dst_cap = j.dst_cap;
         st.format = j.format; st.image = j.image;
+        // Block cuts (pinflate2.hip).  A one-shot call: a stream long enough to hold a run of segments without a start.  A resumed call:
+        // a state that is not all zero with that much input behind its resume point -- the token it stands at, else the block header --;
+        // its segments are counted from there (seg_origin), and a state inside a block goes on at its token (tok_bit) instead of taking
+        // the serial kernel or the block's header again.  A call with an all-zero state is a whole stream, for which
+        // spng_inflate_batch is the entry: it keeps the plan it always had.
+        const int64_t cb = c->cfg[SPNG_CFG_BLOCK_CUT_BYTES];
+        const uint64_t cut_bytes = cb == 0 ? RESUME_SERIAL_BITS / 8 : (uint64_t)cb;
+        uint64_t origin = 0;
+        bool cut = p.internal && cb != SPNG_BLOCK_CUT_NEVER && j.src_len >= cut_bytes;
+        if (!p.internal && cb != SPNG_BLOCK_CUT_NEVER) {
+            const uint64_t *s4 = &p.state[4 * i];
+            const uint64_t at = (s4[2] ? s4[2] : s4[0]) / 8;
+            if ((s4[0] | s4[1] | s4[2] | s4[3]) && j.src_len >= at && j.src_len - at >= cut_bytes) {
+                cut = true; st.cut_resumed = 1;
+                origin = at & ~(uint64_t)255;
+            }
+        }
         if (!p.state.empty()) {
-            st.start_bit = p.state[4 * i]; st.out_pos = p.state[4 * i + 1];
+            st.start_bit = p.state[4 * i]; st.out_pos = p.state[4 * i + 1]; st.blk_out = st.out_pos;
+            if (st.cut_resumed && p.state[4 * i + 2]) { st.tok_bit = p.state[4 * i + 2]; st.out_pos = p.state[4 * i + 3]; }
             // The caller's state stands inside a block.  A block of ordinary size is simply decoded again from its header by the
             // pipeline (cheaper than the serial kernel for everything behind it); one that has already taken more than
             // RESUME_SERIAL_BITS of input would make every push cost what all pushes before it did -- a stream that is ONE block
             // pushed in k pieces O(n k) --: the serial kernel goes on at the token the last push stopped in front of.
-            if (!p.internal && p.state[4 * i + 2] && p.state[4 * i + 2] - p.state[4 * i] > RESUME_SERIAL_BITS) st.serial_only = 1;
+            // (Not with cuts: the pipeline goes on at that token itself.)
+            if (!p.internal && !st.cut_resumed && p.state[4 * i + 2] && p.state[4 * i + 2] - p.state[4 * i] > RESUME_SERIAL_BITS) st.serial_only = 1;
         }
         st.seg_first = (uint32_t)p.segs.size();
-        uint64_t k = (j.src_len + seg_bytes - 1) / seg_bytes;
+        st.seg_origin = origin;
+        const uint64_t span = j.src_len - origin;                  // (what the segments cover)
+        uint64_t k = (span + seg_bytes - 1) / seg_bytes;
         if (k < 1) k = 1;
         if (p.segs.size() + k > 0x7fffffffu) return SPNG_E_ARGUMENT;
         st.seg_count = (uint32_t)k; st.seg_bytes = seg_bytes;
-        // block cuts (pinflate2.hip): one-shot calls only, and only a stream long enough to hold such a run of segments without a start
-        {
-            const int64_t cb = c->cfg[SPNG_CFG_BLOCK_CUT_BYTES];
-            const uint64_t cut_bytes = cb == 0 ? RESUME_SERIAL_BITS / 8 : (uint64_t)cb;
-            if (p.internal && cb != SPNG_BLOCK_CUT_NEVER && !st.start_bit && !st.serial_only && j.src_len >= cut_bytes) {
-                const uint64_t cs = (cut_bytes + seg_bytes - 1) / seg_bytes;
-                st.cut_segs = (uint32_t)(cs > 0x7fffffffu ? 0x7fffffffu : cs < 1 ? 1 : cs);
-                p.cuts = true;
-            }
+        if (cut) {
+            // (whole segments: rounded up -- a resumed call down, so that what passed the gate above is not refused by the plan, which
+            // counts the run of such a call from its first segment's start, at or in front of the resume point)
+            const uint64_t cs = st.cut_resumed ? cut_bytes / seg_bytes : (cut_bytes + seg_bytes - 1) / seg_bytes;
+            st.cut_segs = (uint32_t)(cs > 0x7fffffffu ? 0x7fffffffu : cs < 1 ? 1 : cs);
+            p.cuts = true;
         }
         for (uint64_t q = 0; q < k; ++q) {
             PSeg sg;
             memset(&sg, 0, sizeof sg);
             sg.stream = (uint32_t)i; sg.index = (uint32_t)q;
-            const uint64_t len = q + 1 < k ? seg_bytes : j.src_len - q * seg_bytes;
+            const uint64_t len = q + 1 < k ? seg_bytes : span - q * seg_bytes;
             // page-table entries: 16 token bytes per compressed byte at most, and never more than two per output byte
             uint64_t most = 16 * len;
             if (most > 2 * (j.dst_cap + 64)) most = 2 * (j.dst_cap + 64);
@@ -711,7 +727,7 @@ static int32_t cut_into_segments(spng_ctx *c, InflatePlan &p, uint64_t seg_bytes
             sg.start_bit = ~0ull;
             p.segs.push_back(sg);
         }
-        uint64_t e = (uint64_t)(per_byte * (double)j.src_len);
+        uint64_t e = (uint64_t)(per_byte * (double)span);
         if (e > 2 * (j.dst_cap + 64)) e = 2 * (j.dst_cap + 64);
         p.est[i] = e + k * 65536 + 65536;                                          // (every segment ends inside a page)
         // (block cuts: a cut segment's first chunks -- tokens nobody reads --, the padding of its records and its join's bridge take room

@@ -150,7 +150,8 @@ struct PStream {
     uint64_t       tok_base, ntok;         // its tokens in the token buffer (of its pass)
     uint64_t       end_bit;                // first bit after the final block
     int32_t        ok;                     // 1: the segment chain holds from the first bit to a final block; 2 (resumable
-                                           // streams): up to the first block the input does not hold completely
+                                           // streams): up to the first block the input does not hold completely; 3 (resumed calls
+                                           // with cuts): up to a token inside a block, the input ends within two segments of it
     uint32_t       pass;
     // resumable streams (spng_inflate_resume_batch): where to start, and where to note how far the chain got
     uint64_t       start_bit, out_pos;
@@ -160,10 +161,19 @@ struct PStream {
     uint32_t       parts_max, parts;
     uint64_t       out_total;              // scan: bytes of the whole chain
     uint64_t       sym_off;                // its 16-bit symbols in the symbol scratch (in symbols)
-    uint32_t       cut_on, pad_;           // plan (device side): some of its segments are cut
+    uint32_t       cut_on, cut_resumed;    // plan (device side): some of its segments are cut.  cut_resumed (host): a call of
+                                           // spng_inflate_resume_batch with a state for which cuts may be tried ("resumed calls", pinflate2.hip)
+    // resumed calls with cuts: segment 0 starts seg_origin bytes into the input (a multiple of 256; 0 in every other stream);
+    // tok_bit != 0: the state stands INSIDE the block whose header is start_bit -- the first token still to decode, out_pos bytes
+    // in the output, blk_out of them in front of the block (the plan or scan clear tok_bit, on the device, when the call falls back
+    // to the block's header)
+    uint64_t       seg_origin, tok_bit, blk_out;
+    uint64_t       ho_hdr, ho_out;         // scan, ok == 3: the block the hand-over token (end_bit) lies in: its header, the bytes in front of it
 };
 enum { PSEG_FAIL = 0, PSEG_CONT = 1, PSEG_FINAL = 2, PSEG_PARTIAL = 3, PSEG_NOPAGE = 4,
        PSEG_CUT = 5 };                     // stopped INSIDE a block, in front of a cut segment (block cuts: pinflate2.hip)
+static constexpr uint64_t RESUME_SERIAL_BITS = 8ull << 20;      // 1 MiB of input inside one block: a resumed call goes on there, not at its header
+                                                                // (and the default of SPNG_CFG_BLOCK_CUT_BYTES)
 static constexpr uint32_t PCUT_RECS = 4;   // chunk ends a cut segment's wave records of its chain's head
 // One segment: the blocks that start in [index * seg_bytes, (index + 1) * seg_bytes).
 struct PSeg {
@@ -186,11 +196,15 @@ struct PSeg {
 struct PCut {
     uint32_t cut, anchor;                  // plan: decoded from a guessed bit with the tables of the block at segment `anchor`'s start
     uint32_t nrec, joined;                 // decode: records below; join (PSEG_CUT): this segment's chain provably runs into segment `next`'s ...
-    uint32_t next_head, pad;               // ... behind that one's first next_head halfwords, which stand for next_sub bytes
+    uint32_t next_head, tbl_here;          // ... behind that one's first next_head halfwords, which stand for next_sub bytes.  tbl_here (decode,
+                                           // PSEG_CUT): the block end_bit lies in began in this segment, tbl_bytes of its bytes in front of it
     uint64_t tbl, tbl_id;                  // decode, PSEG_CUT: the header of the block end_bit lies in, and which tables that makes (table_id)
     uint64_t head_tbl;                     // decode, cut segments: the tables its records were decoded with
     uint64_t add_tok, add_bytes;           // join: bridge tokens it appended behind ntok on the way there, their bytes
     uint64_t next_sub;
+    uint64_t tbl_bytes;
+    uint64_t next_bit;                     // join: the bit at which the two chains are one (a token start: a record of segment `next`)
+    uint64_t join_tbl, join_tbl_bytes;     // join: the bridge crossed into another block: its header (0: it did not), bridge bytes in front of it
     struct { uint64_t bit; uint32_t hw, bytes; } rec[PCUT_RECS];   // decode: a chunk end of its first block: the token start there,
                                                                    // halfwords (padded to 8) and bytes emitted in front of it
 };

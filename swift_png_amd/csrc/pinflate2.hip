@@ -45,7 +45,9 @@
 //
 // Streams that arrive in pieces (spng_inflate_resume_batch): the resume point is the first segment start; a
 // segment that meets a block it cannot take as it stands ends PARTIAL in front of it; resolve begins with
-// the window read back from the output, and the block boundary reached goes to the serial kernel.
+// the window read back from the output, and the block boundary reached goes to the serial kernel.  A resumed call with a state
+// and enough input behind it is cut like a one-shot call ("resumed calls" at the block cuts); one with an all-zero state is a whole
+// stream and keeps the plan above -- spng_inflate_batch is the entry that cuts a whole stream.
 #include "common.hpp"
 #include <type_traits>
 #include <cstddef>
@@ -700,8 +702,9 @@ __global__ __launch_bounds__(64) void pinf2_find_kernel(const PStream *__restric
             k3[x] = (uint8_t)(((128u >> a) & 127) + ((128u >> b) & 127) + ((128u >> c) & 127));      // (<= 192)
         }
         const uint64_t sb = uni64(st.seg_bytes) * 8;
-        const uint64_t lo_nom = (uint64_t)j * sb;
-        const uint64_t lo_bit = lo_nom > resume_bit ? lo_nom : ((resume_bit + 1 + 63) & ~(uint64_t)63);   // (window loads want whole bytes)
+        const uint64_t lo_nom = uni64(st.seg_origin) * 8 + (uint64_t)j * sb;
+        const uint64_t floor_bit = uni64(st.tok_bit) ? uni64(st.tok_bit) : resume_bit;      // (a call that goes on inside a block: no header in front of its token)
+        const uint64_t lo_bit = lo_nom > floor_bit ? lo_nom : ((floor_bit + 1 + 63) & ~(uint64_t)63);   // (window loads want whole bytes)
         const uint64_t hi_bit = lo_nom + sb < total ? lo_nom + sb : total;
         for (uint64_t wb = lo_bit; wb < hi_bit && found == NONE2; wb += 16384) {
             stage_bytes2(win, src, n, wb >> 3, 512, lane);
@@ -1056,7 +1059,7 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
 // ---- block cuts ---------------------------------------------------------------------------------------------
 // A segment in which find saw no start (an ORPHAN) lies inside a block -- or a run of blocks without a findable header -- that began
 // in an earlier segment, the nearest one with a start: its ANCHOR.  Where such a run is long (PStream.cut_segs: 1 MiB of input by
-// default; never in a stream that may be resumed) pinf2_cutplan_kernel marks its segments as CUT, and the instantiation
+// default) pinf2_cutplan_kernel marks its segments as CUT, and the instantiation
 // pinf2_cutdecode_kernel<2> gives each a wave of its own: it builds the tables of the anchor's block and decodes from a GUESSED
 // bit, its nominal start, as lanes 1-63 of a chunk do.  The tokens of its first chunk are never on the chain: the chunk serves to
 // synchronise (an end-of-block or an undefined code there: the guess slides on by a chunk).  Of its first PCUT_RECS chunks that end
@@ -1068,6 +1071,15 @@ __device__ __forceinline__ uint32_t decode_chunk(DLds &s, const g8 *src, uint64_
 // bridge tokens to the segment in front and tells j how many of its own to skip (PSeg.head).  Scan takes a cut segment on the chain
 // only with its join proven, and a stream whose chain met a cut but did not reach its final block by proven joins takes the retry
 // pass, which knows no cuts: what today's pipeline does with it.
+//
+// Resumed calls (spng_inflate_resume_batch with a state that is not all zero and at least the threshold of input behind its resume
+// point: PStream.cut_resumed).  The segments count from the resume point (seg_origin), so segment 0 is the anchor of the run behind
+// it.  A state INSIDE a block (tok_bit): segment 0's start is the block's header -- the tables -- and its first chunk begins at
+// the token; resolve reads the window back from the output as for any resumed call.  The input usually ends inside the block: the
+// last cut waves run off it and FAIL.  Scan then accepts the chain through its last proven join and, when the input ends within two
+// segments of the token reached there, ends the stream with ok == 3: stream_verdict writes {header of the block the token lies in,
+// bytes in front of it, token, bytes written} into the state and the serial kernel goes on there, as it does for a call it takes
+// alone.  Any other break counts as a stream redone and takes the way such a call went before (back_to_the_header).
 //
 // Which tables: a dynamic block's are its header's bit; all fixed blocks share theirs, but not what follows their end.
 static constexpr uint64_t TBL_FIXED = 1ull << 63, TBL_FINAL = 1ull << 62;
@@ -1135,7 +1147,11 @@ __device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restric
         }
     };
     const uint64_t segbits = CUT ? uni64(st.seg_bytes) * 8 : 0;
-    uint64_t guess = CUT ? (uint64_t)UNI(sg.index) * segbits : 0;      // a cut segment: where its chain starts
+    const uint64_t org = CUT ? uni64(st.seg_origin) * 8 : 0;     // (resumed calls: the segments count from the resume point)
+    uint64_t guess = CUT ? org + (uint64_t)UNI(sg.index) * segbits : 0;      // a cut segment: where its chain starts
+    // a resumed call that goes on INSIDE a block: segment 0 is an anchor whose header bit (the tables) and first token differ
+    const uint64_t tok0 = CUT && UNI(sg.index) == 0 ? uni64(st.tok_bit) : 0;
+    bool inside = tok0 != 0;
     advance(CUT && mid ? guess + 1 : start + 1);
     // the page table: my own entries and those of the segments behind me in which no start was found (nobody else
     // writes there; a stream whose stored or fixed blocks hide every later start needs them)
@@ -1155,6 +1171,7 @@ __device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restric
     uint32_t nrec = 0, slides = 0;
     bool fresh = true, stopped = false;
     uint64_t tbl = 0, tbl_id = 0, head_tbl = 0;
+    bool tbl_here = false;
     Cursor cur;
     cur.nhw = 0; cur.npages = 0; cur.pa = nullptr; cur.dry = false;
     uint64_t pos = start;
@@ -1188,7 +1205,7 @@ __device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restric
         if (!hok_ && lane == 0) fprintf(stderr, "header at bit %llu rejected\n", (unsigned long long)pos);
 #endif
         if (!hok_) break;
-        if (CUT && mid && h.type == 0) break;                    // (the plan saw a Huffman block there)
+        if (CUT && (mid || inside) && h.type == 0) break;        // (the plan saw a Huffman block there; inside stored bytes: the serial kernel's)
         if (h.type == 0) {
             // stored bytes are literal tokens
             const uint64_t from = h.payload / 8;
@@ -1211,13 +1228,13 @@ __device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restric
             const uint64_t chb = (uint64_t)sdw * 32 * 64;
             const uint64_t id = table_id(h, pos);
             if (mid) head_tbl = id;
-            uint64_t entry = mid ? guess : h.payload, cb = entry;
+            uint64_t entry = mid ? guess : inside ? tok0 : h.payload, cb = entry;
             uint32_t state = 0;
             for (;;) {
                 // the cut segment to stop in front of: the first whose stop bit -- its nominal start + a chunk -- lies behind this chunk's first
                 uint64_t stop_at = NONE2;
                 for (; tgt < seg_count && UNI(cuts[seg_first + tgt].cut); ++tgt) {
-                    const uint64_t v = (uint64_t)tgt * segbits + chb;
+                    const uint64_t v = org + (uint64_t)tgt * segbits + chb;
                     if (v > cb) { stop_at = v; break; }
                 }
                 const bool last = stop_at != NONE2 && cb + chb >= stop_at;
@@ -1252,10 +1269,10 @@ __device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restric
                 if (state) break;
                 cb += chb;
             }
-            if (stopped) { status = PSEG_CUT; tbl = pos; tbl_id = id; pos = entry; break; }
+            if (stopped) { status = PSEG_CUT; tbl = pos; tbl_id = id; tbl_here = !(mid || inside); pos = entry; break; }
             if (state != 1) break;
             pos = entry;
-            mid = false;
+            mid = false; inside = false;
         } else {
             // subsequence length: at most 128 tokens may start in one (their kinds are kept in two 64-bit masks), and
             // no token may jump a whole subsequence (it is at most 48 bits long)
@@ -1291,14 +1308,15 @@ __device__ __forceinline__ void decode_segment(DLds &s, const PStream *__restric
     // The pool ran dry (a batch unlike the one it was sized by): the stream takes the retry pass, with the pool to itself and
     // its like; dry again there, it stops in front of this block like any other block that cannot be taken.
     if (status == PSEG_FAIL && cur.dry && !retry) status = PSEG_NOPAGE;
-    else if (status == PSEG_FAIL && resumable && !(CUT && mid)) { status = PSEG_PARTIAL; nhw = hw_block; nbytes = bytes_block; }   // (pos is still the block's first bit)
-    // (a cut segment that fails inside the block it was started in has no block boundary to stop at: FAIL, and scan sends the stream to the retry pass)
+    else if (status == PSEG_FAIL && resumable && !(CUT && (mid || inside))) { status = PSEG_PARTIAL; nhw = hw_block; nbytes = bytes_block; }   // (pos is still the block's first bit)
+    // (a cut segment that fails inside the block it was started in has no block boundary to stop at: FAIL, and scan sends the stream to the
+    // retry pass -- or, a resumed call whose input ends there, hands the tail to the serial kernel at the last proven join)
     // (no padding: resolve reads whole 16-byte units, inside the last page, and masks what lies behind nhw)
     if (lane == 0) { sg.end_bit = pos; sg.ntok = nhw; sg.nbytes = nbytes; sg.status = status; sg.next = CUT && stopped ? tgt : nk; }
     // (the retry pass: a first pass with cuts may have told this segment to skip tokens -- scan writes `head` before it knows that the
     // stream is redone --; these are new tokens, all of them on the chain)
     if (retry && lane == 0) sg.head = 0;
-    if (CUT && lane == 0) { PCut &ct = cuts[seg0 + blockIdx.x]; ct.tbl = tbl; ct.tbl_id = tbl_id; ct.nrec = nrec; ct.head_tbl = head_tbl; }
+    if (CUT && lane == 0) { PCut &ct = cuts[seg0 + blockIdx.x]; ct.tbl = tbl; ct.tbl_id = tbl_id; ct.nrec = nrec; ct.head_tbl = head_tbl; ct.tbl_here = tbl_here ? 1u : 0u; ct.tbl_bytes = bytes_block; }
 #ifdef SPNG_D_PROF
     if (blockIdx.x == 1 && lane == 0)
         printf("decode: %lu blocks %lu chunks %lu halfwords %lu windows; lane-0 steps r0 %lu r1 %lu replay %lu; cycles: total %lu stage %lu setup %lu round0 %lu "
@@ -1323,18 +1341,39 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_cutdecode_kernel(const
     decode_segment<0, WHICH>(s, streams, segs, pt_slab, pool, seg0, cuts);
 }
 
+// A resumed call that was planned to go on at its token (PStream.tok_bit) and cannot -- nothing was cut, or the cuts did not stitch --
+// takes the way such a call went before there were cuts for it: from the block's header again, or, deep inside the block, the
+// serial kernel at the token (no segment keeps a start: the chain is empty).  false: the latter.  Wave-uniform; lane 0 writes.
+__device__ __forceinline__ bool back_to_the_header(PStream &st, PSeg *__restrict__ segs, int lane)
+{
+    const bool deep = uni64(st.tok_bit) - uni64(st.start_bit) > RESUME_SERIAL_BITS;
+    if (deep) {
+        const uint32_t first = UNI(st.seg_first), count = UNI(st.seg_count);
+        for (uint32_t i = (uint32_t)lane; i < count; i += 64) segs[first + i].start_bit = NONE2;
+    }
+    if (lane == 0) {
+        if (deep) st.serial_only = 1;
+        else { st.tok_bit = 0; st.out_pos = st.blk_out; }
+    }
+    __threadfence();
+    return !deep;
+}
+
 // Block cuts, the plan (one wave per stream, between find and decode): every segment without a start learns its anchor, and the
 // runs of such segments that are long enough and lie behind a Huffman block's header are marked as cut.  stats[0] += cuts tried.
+// A resumed call (segment 0 = the resume point, the segments counted from seg_origin) is planned like any other stream: its
+// first segment is the anchor of the run behind it.
 __global__ __launch_bounds__(64) void pinf2_cutplan_kernel(PStream *__restrict__ streams, PSeg *__restrict__ segs, PCut *__restrict__ cuts, uint32_t *__restrict__ stats)
 {
     __shared__ __attribute__((aligned(16))) DLds s;
     const int lane = threadIdx.x;
     PStream &st = streams[blockIdx.x];
     const uint32_t need = UNI(st.cut_segs);
-    if (!need || UNI(st.serial_only) || uni64(st.start_bit)) return;
+    if (!need || UNI(st.serial_only)) return;
     const uint32_t first = UNI(st.seg_first), count = UNI(st.seg_count);
     const g8 *src = (const g8 *)uni64((uint64_t)st.src);
-    const uint64_t n = uni64(st.src_len), sb = uni64(st.seg_bytes);
+    const uint64_t n = uni64(st.src_len), sb = uni64(st.seg_bytes), org = uni64(st.seg_origin);
+    const bool rcut = UNI(st.cut_resumed) != 0;
     // A start that find saw behind a run long enough to be cut is more often a look-alike inside the huge block than a block's header
     // (compressed data is full of bit patterns that parse): it is kept only if the bits in front of it are the end-of-block code of the
     // block the run lies in, as far as this kernel can tell -- that of the segment with a start in front of the run (a code of at
@@ -1396,9 +1435,11 @@ __global__ __launch_bounds__(64) void pinf2_cutplan_kernel(PStream *__restrict__
         if (i < count && !has) {
             const uint32_t a = cuts[first + i].anchor;
             if (a != ~0u) {
-                const uint64_t lo = (uint64_t)(a + 1) * sb, hi = (uint64_t)nf * sb < n ? (uint64_t)nf * sb : n;
+                const uint64_t lo = org + (uint64_t)(a + 1) * sb, hi = org + (uint64_t)nf * sb < n ? org + (uint64_t)nf * sb : n;
                 const uint64_t b = segs[first + a].start_bit;
-                if (hi > lo && hi - lo >= (uint64_t)need * sb && b + 3 <= n * 8) {
+                // (a resumed call: the input behind the resume point counts, the anchor's own segment included -- the host's gate)
+                const uint64_t from = a == 0 && rcut ? org : lo;
+                if (hi > lo && hi - from >= (uint64_t)need * sb && b + 3 <= n * 8) {
                     const uint32_t v = (uint32_t)src[b >> 3] | ((b >> 3) + 1 < n ? (uint32_t)src[(b >> 3) + 1] << 8 : 0u);
                     const uint32_t type = (v >> ((b & 7) + 1)) & 3;
                     cut = type == 1 || type == 2;
@@ -1411,6 +1452,7 @@ __global__ __launch_bounds__(64) void pinf2_cutplan_kernel(PStream *__restrict__
         if (base == 0) break;
     }
     if (lane == 0 && tried) { atomicAdd(stats, tried); st.cut_on = 1; }
+    if (!tried && uni64(st.tok_bit)) back_to_the_header(st, segs, lane);      // (nothing to cut: today's way for this call)
 }
 
 // Block cuts, the join (one wave per segment, between decode and scan; every wave but that of a segment that stopped in front of a
@@ -1446,6 +1488,7 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_cutjoin_kernel(const P
     uint64_t nbytes = 0;
     uint32_t c = 0, chunks = 0;
     bool mid = true, have = false, ok = false;
+    uint64_t jt = 0, jt_bytes = 0;                              // the bridge crossed into another block: its header, the bridge's bytes in front of it
     Hdr2 h;
     for (uint32_t steps = 0; steps < 4 * CUT_JOIN_CHUNKS; ++steps) {
         while (c < nrec && uni64(sg.rec[c].bit) < pos) ++c;
@@ -1457,7 +1500,7 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_cutjoin_kernel(const P
             const uint64_t at = mid ? uni64(pc.tbl) : pos;
             if (!UB(parse_header2(s, src, n, at, h, lane)) || h.type == 0) break;
             have = true;
-            if (!mid) { id = table_id(h, pos); pos = h.payload; mid = true; continue; }
+            if (!mid) { id = table_id(h, pos); jt = pos; jt_bytes = nbytes; pos = h.payload; mid = true; continue; }
         }
         const uint32_t sdw = chunk_dwords(h.minlen);
         const uint64_t chb = (uint64_t)sdw * 32 * 64, upto = uni64(sg.rec[c].bit);
@@ -1473,6 +1516,7 @@ __global__ __launch_bounds__(64, SPNG_D_WAVES) void pinf2_cutjoin_kernel(const P
     if (lane == 0) {
         pc.add_tok = cur.nhw - hw0; pc.add_bytes = nbytes;
         pc.next_head = UNI(sg.rec[c].hw); pc.next_sub = UNI(sg.rec[c].bytes); pc.joined = 1;
+        pc.next_bit = pos; pc.join_tbl = jt; pc.join_tbl_bytes = jt_bytes;
         atomicAdd(stats + 1, 1u);
     }
 }
@@ -1508,6 +1552,11 @@ __device__ __forceinline__ void scan_stream(PStream *__restrict__ streams, PSeg 
     uint32_t k = 0;
     bool met_cut = false, by_cut = false;                         // CUT: the chain met a cut; this segment was reached through one ...
     uint32_t skip_hw = 0; uint64_t skip_bytes = 0;             // ... and its first tokens are not on the chain
+    // CUT, a resumed call (rcut): the block the chain stands in -- its header, the output bytes in front of it -- and the token at
+    // which a chain that the end of the input broke is handed to the serial kernel
+    const bool rcut = CUT && UNI(st.cut_resumed) != 0;
+    uint64_t cur_hdr = CUT ? uni64(st.start_bit) : 0, cur_out = CUT ? uni64(st.blk_out) : 0, ho_bit = 0;
+    bool handed = false;
     for (uint32_t hops = 0; hops < count; ++hops) {
         PSeg *sg = segs + first + k;
         const uint64_t start = uni64(sg->start_bit), end = uni64(sg->end_bit);
@@ -1523,7 +1572,25 @@ __device__ __forceinline__ void scan_stream(PStream *__restrict__ streams, PSeg 
                 met_cut = true;
                 nx = UNI(sg->next);
                 const PCut &ct = cuts[first + k];
-                if (nx <= k || nx >= count || !UNI(cuts[first + nx].cut) || !UNI(ct.joined)) break;
+                const bool joined = nx > k && nx < count && UNI(cuts[first + nx].cut) && UNI(ct.joined);
+                if (rcut) {
+                    if (UNI(ct.tbl_here)) { cur_hdr = uni64(ct.tbl); cur_out = uni64(st.out_pos) + out + uni64(ct.tbl_bytes) - (by_cut ? skip_bytes : 0); }
+                    // the segment behind the cut ran off the input (or never got a record): this one is the chain's last, with its
+                    // bridge when there is one, and the token it reaches is where the serial kernel goes on
+                    if (!joined || (int32_t)UNI(segs[first + nx].status) == PSEG_FAIL) {
+                        ho_bit = end;
+                        if (joined) {
+                            if (uni64(ct.join_tbl)) { cur_hdr = uni64(ct.join_tbl); cur_out = uni64(st.out_pos) + out + nb + uni64(ct.join_tbl_bytes); }
+                            nt += uni64(ct.add_tok); nb += uni64(ct.add_bytes); ho_bit = uni64(ct.next_bit);
+                        }
+                        if (lane == 0) { sg->tok_base = tok; sg->out_base = out; sg->used = 1; sg->ntok = nt; sg->nbytes = nb; sg->head = hd; sg->status = PSEG_PARTIAL; }
+                        tok += nt - hd; out += nb;
+                        handed = true;
+                        break;
+                    }
+                    if (uni64(ct.join_tbl)) { cur_hdr = uni64(ct.join_tbl); cur_out = uni64(st.out_pos) + out + nb + uni64(ct.join_tbl_bytes); }
+                }
+                if (!joined) break;
                 nt += uni64(ct.add_tok); nb += uni64(ct.add_bytes);
                 skip_hw = UNI(ct.next_head); skip_bytes = uni64(ct.next_sub);
             }
@@ -1544,11 +1611,17 @@ __device__ __forceinline__ void scan_stream(PStream *__restrict__ streams, PSeg 
         if (uni64(segs[first + nx].start_bit) != end) break;
         k = nx;
     }
-    if (CUT && met_cut && !(ok && !partial)) {                     // (before the parts: `ok` decides whether there are any)
-        ok = false; partial = false; dry = true;
+    // (only where the input ends within two segments of the token: anything else that breaks the chain is not the end of the input)
+    if (CUT && handed && uni64(st.src_len) * 8 - ho_bit <= 2 * uni64(st.seg_bytes) * 8) { ok = true; partial = true; end_bit = ho_bit; }
+    else handed = false;
+    // (a resumed call may end in front of a block the input does not hold completely, as it does without cuts)
+    if (CUT && met_cut && !(ok && (!partial || rcut))) {           // (before the parts: `ok` decides whether there are any)
+        ok = false; partial = false; dry = true; handed = false;
         if (lane == 0) atomicAdd(stats + 2, 1u);
         COV(8);
     }
+    bool again = !retry && dry;
+    if constexpr (CUT) { if (again && uni64(st.tok_bit)) again = back_to_the_header(st, segs, lane); }
     // the parts: a new one begins with the first chain segment whose first byte is at or behind the next multiple of 1 / P of
     // the output (and behind the first 32 KiB, so that every marker names a byte that exists); a stream from its first byte only (no resumed one), and one
     // that fits its buffer.  (The table arrives zeroed.)
@@ -1586,8 +1659,8 @@ __device__ __forceinline__ void scan_stream(PStream *__restrict__ streams, PSeg 
         if (lane == 0) { pp[np - 1].seg_end = ~0u; pp[np - 1].out_len = out - begun; }
     }
     // pass: 1 = the chain broke where the token pool was empty: once more, with the pool to itself and its like (retry)
-    if (lane == 0) { st.ok = ok ? (partial ? 2 : 1) : 0; st.ntok = tok; st.end_bit = end_bit; st.pass = (!retry && dry) ? 1 : 0; st.tok_base = 0;
-                     st.out_total = out; st.parts = np; }
+    if (lane == 0) { st.ok = ok ? (handed ? 3 : partial ? 2 : 1) : 0; st.ntok = tok; st.end_bit = end_bit; st.pass = again ? 1 : 0; st.tok_base = 0;
+                     st.out_total = out; st.parts = np; st.ho_hdr = cur_hdr; st.ho_out = cur_out; }
 }
 
 template <uint32_t RETRY>
@@ -1671,10 +1744,12 @@ __device__ __forceinline__ void stream_verdict(const PStream &st, uint32_t S, ui
     uint64_t *state = st.state;
     // what was in front of this call (spng_inflate_resume_batch): the sum above then lacks those bytes
     const bool whole = st.start_bit == 0 && st.out_pos == 0;
-    if (st.ok == 2) {
-        // the chain stopped in front of a block the input does not hold completely (or that is not acceptable): the
-        // serial kernel goes on from there
-        state[0] = st.end_bit; state[1] = pos; state[2] = 0; state[3] = 0;     // (a block boundary: nothing taken of the block behind it)
+    if (st.ok == 2 || st.ok == 3) {
+        // 2: the chain stopped in front of a block the input does not hold completely (or that is not acceptable): the serial kernel
+        // goes on from there -- a block boundary: nothing taken of the block behind it.  3 (a resumed call with cuts whose input ends
+        // inside a block): it goes on at the token the last proven join reached, inside the block whose header scan noted.
+        const bool tok = st.ok == 3;
+        state[0] = tok ? st.ho_hdr : st.end_bit; state[1] = tok ? st.ho_out : pos; state[2] = tok ? st.end_bit : 0; state[3] = tok ? pos : 0;
     } else if (!whole) {
         // resumed and complete: the trailer must be there; the sum over ALL bytes is compared afterwards (gzip.hip)
         const uint64_t endb = (st.end_bit + 7) / 8, consumed = endb + (st.format == SPNG_FORMAT_ZLIB ? 4 : 0);

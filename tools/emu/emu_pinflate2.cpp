@@ -5,6 +5,10 @@
 //   emu_pinflate2 <stream file> <expected output file> <format 0|1> <segment bytes> [pool pages] [resume: start_bit out_pos]
 //   EMU_CUT_BYTES=n: block cuts for runs of segments without a start of at least n bytes (api.hip: SPNG_CFG_BLOCK_CUT_BYTES), with
 //   the retry pass behind them for a stream whose cuts do not stitch; prints "cuts tried=<n> joined=<n> redone=<n>"
+//   EMU_TOK_BIT=b EMU_TOK_OUT=w (with the resume arguments and EMU_CUT_BYTES): a resumed call with cuts, as api.hip plans it -- the
+//   state is {start_bit, out_pos, b, w} (b = 0: it stands at the block header), the first w bytes of the output are there, the
+//   segments count from the resume point; prints "handover bit=<b> bytes=<n> header=<bit> header_bytes=<n>" when the chain was
+//   handed to the serial kernel at a token (PStream.ok == 3)
 //   exit code 0: the pipeline produced SPNG_DONE and identical bytes;  3: the pipeline left the whole stream to the serial
 //   kernel;  4: it decoded a prefix (printed: the block boundary and byte count the serial kernel would start from) and that
 //   prefix is right;  5: it reported an error of its own (printed);  1: wrong bytes / wrong result
@@ -51,11 +55,21 @@ int main(int argc, char **argv)
     uint64_t state[4] = {0, 0, 0, 0};                          // (four words: the pipeline moves the first pair and clears the second)
     st.state = state;                                          // (api.hip: every stream has a state slot, {0, 0} unless resumed)
     const bool resumed = argc > 7;
+    const uint64_t cut_bytes = getenv("EMU_CUT_BYTES") ? strtoull(getenv("EMU_CUT_BYTES"), nullptr, 10) : 0;
     if (argc > 7) {
-        state[0] = st.start_bit = strtoull(argv[6], nullptr, 10); state[1] = st.out_pos = strtoull(argv[7], nullptr, 10);
+        state[0] = st.start_bit = strtoull(argv[6], nullptr, 10); state[1] = st.out_pos = st.blk_out = strtoull(argv[7], nullptr, 10);
+        if (cut_bytes && getenv("EMU_TOK_BIT")) {
+            // (api.hip, cut_into_segments: the gate and the plan of a resumed call with cuts)
+            state[2] = strtoull(getenv("EMU_TOK_BIT"), nullptr, 10); state[3] = getenv("EMU_TOK_OUT") ? strtoull(getenv("EMU_TOK_OUT"), nullptr, 10) : 0;
+            const uint64_t at = (state[2] ? state[2] : state[0]) / 8;
+            if (src.size() >= at && src.size() - at >= cut_bytes) {
+                st.cut_resumed = 1; st.seg_origin = at & ~(uint64_t)255;
+                if (state[2]) { st.tok_bit = state[2]; st.out_pos = state[3]; }
+            }
+        }
         memcpy(dst.data(), want.data(), st.out_pos);
     }
-    uint64_t k = (src.size() + seg_bytes - 1) / seg_bytes;
+    uint64_t k = (src.size() - st.seg_origin + seg_bytes - 1) / seg_bytes;
     if (k < 1) k = 1;
     st.seg_first = 0; st.seg_count = (uint32_t)k; st.seg_bytes = seg_bytes;
     std::vector<PSeg> segs(k);
@@ -80,12 +94,11 @@ int main(int argc, char **argv)
     emu::launch((unsigned)k, 64, [&] { pinf2_find_kernel<0>(&st, segs.data(), 0); });
     if (verbose) for (uint64_t q = 0; q < k; ++q) fprintf(stderr, "seg %llu: start %lld\n", (unsigned long long)q, (long long)segs[q].start_bit);
     // block cuts (api.hip: a batch with a stream they may be tried for)
-    const uint64_t cut_bytes = getenv("EMU_CUT_BYTES") ? strtoull(getenv("EMU_CUT_BYTES"), nullptr, 10) : 0;
     uint32_t cstats[4] = {0, 0, 0, 0};                         // cuts tried, joined, streams redone
     std::vector<PCut> cuts(k);                                 // (api.hip: a table of its own beside the segments, zeroed on the device)
     memset(cuts.data(), 0, k * sizeof(PCut));
-    if (cut_bytes && !resumed) {
-        st.cut_segs = (uint32_t)((cut_bytes + seg_bytes - 1) / seg_bytes);
+    if (cut_bytes && (!resumed || st.cut_resumed)) {
+        st.cut_segs = (uint32_t)(st.cut_resumed ? (cut_bytes / seg_bytes ? cut_bytes / seg_bytes : 1) : (cut_bytes + seg_bytes - 1) / seg_bytes);
         emu::launch(1, 64, [&] { pinf2_cutplan_kernel(&st, segs.data(), cuts.data(), cstats); });
         emu::launch((unsigned)k, 64, [&] { pinf2_cutdecode_kernel<1>(&st, segs.data(), pt.data(), pool, 0, cuts.data()); });
         emu::launch((unsigned)k, 64, [&] { pinf2_cutdecode_kernel<2>(&st, segs.data(), pt.data(), pool, 0, cuts.data()); });
@@ -185,7 +198,9 @@ int main(int argc, char **argv)
     if (resumed) {
         // report what the pipeline did
         printf("resume ok=%d done=%d state=%llu,%llu\n", st.ok, done, (unsigned long long)state[0], (unsigned long long)state[1]);
-        const uint64_t upto = st.ok == 2 ? state[1] : (done ? res.written : 0);
+        if (st.ok == 3) printf("handover bit=%llu bytes=%llu header=%llu header_bytes=%llu\n", (unsigned long long)state[2], (unsigned long long)state[3],
+                               (unsigned long long)state[0], (unsigned long long)state[1]);
+        const uint64_t upto = st.ok == 3 ? state[3] : st.ok == 2 ? state[1] : (done ? res.written : 0);
         if (memcmp(dst.data(), want.data(), upto) != 0) { printf("MISMATCH in the resumed prefix\n"); return 1; }
         return 0;
     }

@@ -427,10 +427,13 @@ __global__ __launch_bounds__(SPNG_UNF_NW * 64) void unfilter_kernel(const UnfJob
             if (nb < nbands) {
                 bool ok = ready(nb, nT);
                 // Blocking here is deadlock-free only if nothing the awaited tile depends on is a tile
-                // this wave has not published yet: (nb, nT) reaches back to tile nT + NW*K of this
-                // wave's band nb - NW.  Same band: that band is complete.  Next band (we are in the
-                // last tile of the current one): only when the chain stops short of this tile.
-                const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(NW * C::K) + 1 < ntiles);
+                // this wave has not published yet.  Same band: that band is complete.  Next band (we are
+                // in the last tile of the current one): every wave in between may itself be blocked here, in
+                // front of its staged tile with only the tiles before it published, so a hop reaches back
+                // K + 1 tiles and (nb, 0) needs tile NW * (K + 1) - 1 of this wave's current band: it must
+                // lie in front of the last one (tests/test_emu_unfilter.py "one long piece").  Shorter rows
+                // do not prefetch across the band; what that costs them has not been measured.
+                const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(NW * (C::K + 1)) + 1 < ntiles);
                 if (!ok && may_block) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     if (lane == 0 && count)

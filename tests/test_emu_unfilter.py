@@ -61,6 +61,16 @@ CASES = [
     ("gray8 sub", 70, 10, 1, 8, 64, [1]), ("gray8 average", 70, 10, 1, 8, 64, [0, 3]), ("gray8 paeth", 71, 10, 1, 8, 64, [1, 4]),
     ("gray8 one pixel", 1, 1, 1, 8, 64, [4]), ("gray8 five pixels", 5, 130, 1, 8, 64, _f(13, 130)), ("va8 paeth", 33, 20, 2, 8, 64, [2, 4]),
     ("gray16 mixed", 301, 70, 1, 16, 64, _f(14, 70)), ("gray8 wide", 3001, 140, 1, 8, 64, _f(15, 140)), ("va8 wide, pieces", 1100, 200, 2, 8, 32, _f(16, 61)),
+    # one long piece (no None / Sub row behind the first: more bands than the workgroup has waves) of rows whose tile count is
+    # just above what `may_block` of unfilter_kernel asked for: a wave that waited for the first tile of its NEXT band in front of
+    # its last tile, while the three waves between waited in front of their staged tiles, waited for good (found by the
+    # production-size table of tests/scanline_cases.py: "rgb16 300x1300 up")
+    ("rgb16 one long piece", 300, 330, 3, 16, 1000, [1] + [2] * 400), ("rgb8 one long piece", 300, 330, 3, 8, 1000, [1] + [4] * 400),
+    ("gray8 one long piece", 900, 330, 1, 8, 1000, [1] + [3] * 400), ("va8 one long piece", 450, 330, 2, 8, 1000, [1] + [2] * 400),
+    # and the edge of the bound that replaced it, `NW * (K + 1) + 1 < ntiles`: the last tile count that does not wait and the first that does
+    ("rgb16 13 tiles", 330, 330, 3, 16, 1000, [1] + [4] * 400), ("rgb16 14 tiles", 360, 330, 3, 16, 1000, [1] + [4] * 400),
+    ("rgb8 9 tiles", 460, 330, 3, 8, 1000, [1] + [3] * 400), ("rgb8 10 tiles", 520, 330, 3, 8, 1000, [1] + [2] * 400),
+    ("gray8 21 tiles", 1040, 330, 1, 8, 1000, [1] + [4] * 400), ("va8 22 tiles", 550, 330, 2, 8, 1000, [1] + [4] * 400),
 ]
 
 

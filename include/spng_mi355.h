@@ -66,6 +66,9 @@ enum {
     SPNG_E_REFERENCE_UNDEFINED = 67   /* malformed input on which the reference reads uninitialised
                                          memory (unused distance code); no defined answer to match */
 };
+/* A second departure on input the reference has no answer for: straightening a pixel whose colour exceeds its alpha (a > 0 and
+ * p > a, no premultiplied pixel) overflows T and traps in Swift (PNG.swift:101-117).  The device cannot trap: such a component is
+ * written as T.max, the status stays SPNG_DONE, and spng_alpha_batch counts the components in spng_result.aux[0]. */
 
 enum { SPNG_FORMAT_ZLIB = 0,          /* LZ77.Format.zlib  (PNG.Standard.common) */
        SPNG_FORMAT_IOS = 1,           /* LZ77.Format.ios   (raw DEFLATE, CgBI)   */
@@ -166,6 +169,7 @@ enum { SPNG_K_INFLATE = 0,          /* the serial inflate kernel (streams the pa
        SPNG_K_LEX = 12,             /* chunk lexing + CRC-32 / IDAT chunk emission */
        SPNG_K_PINF_FIND = 8, SPNG_K_PINF_DECODE = 9, SPNG_K_PINF_RESOLVE = 11,   /* its stages */
        SPNG_K_DFL_SEARCH = 13, SPNG_K_DFL_PARSE = 14,   /* levels >= 8: the two kernels of a round (inside SPNG_K_DEFLATE) */
+       SPNG_K_ALPHA = 15,           /* spng_alpha_batch */
        SPNG_K_COUNT = 16 };
 int32_t spng_profile(spng_ctx *ctx, int enable);                /* enable/disable + reset counters  */
 int32_t spng_profile_get(spng_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
@@ -307,11 +311,19 @@ typedef struct spng_unpack_desc {
     uint8_t     premultiply;                    /* 0: straight;  SPNG_PREMULTIPLY: .premultiplied (PNG.RGBA.swift:121-127,
                                                    PNG.VA.swift:57-60);  SPNG_PREMULTIPLY_AS_U8 (target 16 only):
                                                    .premultiplied(as: UInt8.self) (PNG.RGBA.swift:146-158), the form the
-                                                   reference's iOS goldens are compared in (Roundtripping.swift:206-215) */
+                                                   reference's iOS goldens are compared in (Roundtripping.swift:206-215);
+                                                   SPNG_STRAIGHTEN / SPNG_STRAIGHTEN_AS_U8 (target 16 only): .straightened /
+                                                   .straightened(as: UInt8.self) -- unpack(as:).map(\.straightened), the first step of
+                                                   Snippets/PNG/iPhoneOptimized.swift, in one pass.  A component the reference
+                                                   traps on is written as T.max silently here: spng_alpha_batch is the entry
+                                                   that counts them */
     uint8_t     reserved[6];
 } spng_unpack_desc;
 enum { SPNG_TARGET_RGBA = 0, SPNG_TARGET_VA = 1, SPNG_TARGET_SCALAR = 2 };
-enum { SPNG_PREMULTIPLY = 1, SPNG_PREMULTIPLY_AS_U8 = 2 };
+enum { SPNG_PREMULTIPLY = 1,          /* .premultiplied                  (PNG.RGBA.swift:121-127, PNG.VA.swift:57-60)    */
+       SPNG_PREMULTIPLY_AS_U8 = 2,    /* .premultiplied(as: UInt8.self)  (PNG.RGBA.swift:146-158), T = UInt16 only       */
+       SPNG_STRAIGHTEN = 3,           /* .straightened                   (PNG.RGBA.swift:167-173, PNG.VA.swift:98-101)   */
+       SPNG_STRAIGHTEN_AS_U8 = 4 };   /* .straightened(as: UInt8.self)   (PNG.RGBA.swift:192-206), T = UInt16 only       */
 /* replaces PNG.RGBA<T>.unpack(_:of:deindexer:) / PNG.VA<T>.unpack(_:of:deindexer:) with the default deindexers, T = UInt8 / UInt16
  * (Sources/PNG/ColorTargets/PNG.RGBA.swift:259-365, depth rescaling Sources/PNG/PNG.swift:255-312,
  * 495-524; PNG.VA.swift:184-290; premultiplication PNG.swift:55-66); what PNG.Image.unpack(as:) returns.  All descs
@@ -339,7 +351,12 @@ typedef struct spng_pack_desc {
     uint8_t     bgr;                            /* PNG.Format.bgr8 / bgra8 (CgBI)                    */
     uint8_t     source;                         /* 8 or 16: T = UInt8 / UInt16                        */
     uint8_t     layout;                         /* SPNG_TARGET_RGBA / _VA / _SCALAR                   */
-    uint8_t     reserved[6];
+    uint8_t     premultiply;                    /* 0: as they are;  SPNG_PREMULTIPLY;  SPNG_PREMULTIPLY_AS_U8 (source 16 only): the
+                                                   components are premultiplied before they are narrowed, indexed and swizzled --
+                                                   pack(pixels.map(\.premultiplied)), the last step of Snippets/PNG/iPhoneOptimized.swift,
+                                                   in one pass (an indexed format looks up the premultiplied colour).  Not with
+                                                   SPNG_TARGET_SCALAR */
+    uint8_t     reserved[5];
 } spng_pack_desc;
 /* replaces PNG.RGBA<T>.pack(_:as:indexer:) / PNG.VA<T>.pack(_:as:indexer:) / the scalar PNG.Image.pack<T> with the default
  * indexers, T = UInt8 / UInt16 -- what PNG.Image.init(packing:size:layout:) stores (Sources/PNG/ColorTargets/PNG.RGBA.swift:409-478,
@@ -352,6 +369,29 @@ int32_t spng_pack_batch(spng_ctx *ctx, const spng_pack_desc *descs, uint32_t cou
 /* host-pointer convenience (copies in / out, synchronous) */
 int32_t spng_pack_as(spng_ctx *ctx, const void *pixels, uint32_t w, uint32_t h, int depth, int channels,
                      int indexed, int bgr, int source, int layout, const void *palette, uint32_t palette_count, void *storage);
+
+/* ---- pixels: premultiplied and straight alpha ------------------------------------------------------ */
+/* One array of colour-target pixels to premultiply or straighten.  Both pointers are device pointers aligned to T. */
+typedef struct spng_alpha_desc {
+    const void *d_in;  void *d_out;             /* `count` pixels each; d_out == d_in is allowed (in place), any other overlap is not */
+    uint64_t    count;
+    uint8_t     bits;                           /* 8 or 16: T = UInt8 / UInt16; all descs of a call share it */
+    uint8_t     layout;                         /* SPNG_TARGET_RGBA: (r, g, b, a) or SPNG_TARGET_VA: (v, a) */
+    uint8_t     op;                             /* SPNG_PREMULTIPLY ... SPNG_STRAIGHTEN_AS_U8 (the _AS_U8 forms: bits 16 only) */
+    uint8_t     reserved[5];                    /* zero */
+} spng_alpha_desc;
+/* replaces PNG.RGBA<T>.premultiplied / .straightened and their (as: UInt8.self) forms, and the same of PNG.VA<T>, mapped over an
+ * array (Sources/PNG/ColorTargets/PNG.RGBA.swift:121-206, PNG.VA.swift:57-131; PNG.premultiply / PNG.straighten,
+ * Sources/PNG/PNG.swift:55-117), bit for bit, with M = T.max:
+ *   premultiply   (c * a + (M >> 1)) / M;            straighten   a == 0 ? p : (M * p + (a >> 1)) / a;       alpha as it is
+ *   the _AS_U8 forms: every component, alpha included, shifted right by 8, the operation at M = 255, every component times 257.
+ * Where the reference traps -- a > 0 and p > a, compared after the shift in the _AS_U8 form: the quotient does not fit T -- the
+ * component becomes T.max (255 * 257 in the _AS_U8 form).  Results: status SPNG_DONE, written = bytes written, aux[0] = the
+ * number of such components.  A count of 0, of a desc or of the call, is valid and writes nothing. */
+int32_t spng_alpha_batch(spng_ctx *ctx, const spng_alpha_desc *descs, uint32_t count,
+                         spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous): n pixels */
+int32_t spng_alpha(spng_ctx *ctx, const void *pixels, uint64_t n, int bits, int layout, int op, void *out, spng_result *result);
 
 /* ---- encode -------------------------------------------------------------------------------- */
 /* replaces PNG.Encoder.filter (PNG.Encoder.swift:132-204) + PNG.Image.collect

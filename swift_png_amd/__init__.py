@@ -37,10 +37,11 @@ K_UNPACK = 7
 K_PACK = 10
 IMAGE_OVERDRAW = 1
 TARGET_RGBA, TARGET_VA, TARGET_SCALAR = 0, 1, 2
-PREMULTIPLY, PREMULTIPLY_AS_U8 = 1, 2
+PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8 = 1, 2, 3, 4
 K_LEX = 12
 K_PINF_FIND, K_PINF_DECODE, K_PINF_RESOLVE = 8, 9, 11
 K_DFL_SEARCH, K_DFL_PARSE = 13, 14
+K_ALPHA = 15
 CFG_INFLATE_MODE, CFG_SEGMENT_BYTES, CFG_TOKEN_BYTES, CFG_UNFILTER_PIECE_ROWS, CFG_RESOLVE_PARTS = 0, 1, 2, 3, 5          # (4: reserved)
 CFG_DEFLATE_BYTES, CFG_MULTI_GROUPS = 7, 8          # (6: reserved)
 CFG_BLOCK_CUT_BYTES = 9                            # parallel inflate: shortest run of segments without a block start that is cut (bytes; 0: 1 MiB)
@@ -53,7 +54,7 @@ EXPORTS = [
     "spng_profile_get", "spng_token_stats", "spng_cut_stats", "spng_configure", "spng_inflate_batch", "spng_inflate_resume_batch", "spng_unfilter_batch",
     "spng_unfilter_resume_batch", "spng_decode_batch",
     "spng_inflate", "spng_unfilter", "spng_decode", "spng_adler32", "spng_filter_batch", "spng_filter",
-    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
+    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
 ]
 
@@ -111,7 +112,13 @@ class PackDesc(ctypes.Structure):
     _fields_ = [("d_pixels", ctypes.c_void_p), ("d_storage", ctypes.c_void_p), ("d_palette", ctypes.c_void_p),
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("palette_count", ctypes.c_uint32),
                 ("depth", ctypes.c_uint8), ("channels", ctypes.c_uint8), ("indexed", ctypes.c_uint8), ("bgr", ctypes.c_uint8),
-                ("source", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
+                ("source", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("premultiply", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 5)]
+
+
+class AlphaDesc(ctypes.Structure):
+    _fields_ = [("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_uint64), ("bits", ctypes.c_uint8),
+                ("layout", ctypes.c_uint8), ("op", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 5)]
 
 
 class ChunkingDesc(ctypes.Structure):
@@ -242,6 +249,8 @@ def load_library():
     lib.spng_pack_batch.argtypes = [vp, vp, u32]
     lib.spng_pack_as.argtypes = [vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_int, vp, u32, vp]
+    lib.spng_alpha_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_alpha.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, rp]
     lib.spng_deflate_bound.restype = u64
     lib.spng_deflate_bound.argtypes = [u64]
     lib.spng_deflate_batch.argtypes = [vp, ctypes.POINTER(StreamDesc), ctypes.POINTER(i32), u32, vp, rp]
@@ -560,19 +569,61 @@ class Session:
                                                  int(layout), int(premultiply), pal if palette else None, len(palette or b"") // 4, k, out))
         return bytes(out[:n])
 
-    def pack(self, pixels: bytes, w, h, depth, channels, indexed=False, bgr=False, source=16, palette=None, layout=0) -> bytes:
+    def pack(self, pixels: bytes, w, h, depth, channels, indexed=False, bgr=False, source=16, palette=None, layout=0,
+             premultiply=0) -> bytes:
         """PNG.Image(packing:size:layout:).storage for [PNG.RGBA<T>] (layout TARGET_RGBA), [PNG.VA<T>] (TARGET_VA) or [T]
         (TARGET_SCALAR), T = UInt8 / UInt16 (`source` bits), with the default indexer: pixels = bytes of r, g, b, a | v, a | v per
-        pixel (host order) -> storage bytes.  palette: bytes of (r, g, b, a) quadruplets."""
+        pixel (host order) -> storage bytes.  palette: bytes of (r, g, b, a) quadruplets.  premultiply: 0, PREMULTIPLY or
+        PREMULTIPLY_AS_U8 -- pack(pixels.map(\\.premultiplied)) in one pass (spng_pack_desc.premultiply)."""
         px = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
         if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
             raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
         n = self.lib.spng_storage_size(w, h, depth, channels)
+        if premultiply:
+            # (spng_pack_as has no such argument: the batch entry on device buffers)
+            d_px, d_sto = self.to_device(bytes(pixels)), self.empty(n)
+            d_pal = self.to_device(bytes(palette)) if palette else None
+            desc = (PackDesc * 1)(PackDesc(self._ptr(d_px), self._ptr(d_sto), self._ptr(d_pal), w, h, len(palette or b"") // 4, depth,
+                                           channels, int(bool(indexed)), int(bool(bgr)), source, int(layout), int(premultiply)))
+            _check(self.lib, self.lib.spng_pack_batch(self.ctx, desc, 1))
+            self.sync()
+            return bytes(d_sto[:n].cpu().numpy())
         out = (ctypes.c_uint8 * max(n, 1))()
         pal = (ctypes.c_uint8 * max(len(palette or b""), 1)).from_buffer_copy(bytes(palette or b"\0"))
         _check(self.lib, self.lib.spng_pack_as(self.ctx, px, w, h, depth, channels, int(bool(indexed)), int(bool(bgr)), source,
                                                int(layout), pal if palette else None, len(palette or b"") // 4, out))
         return bytes(out[:n])
+
+    def alpha_batch(self, arrays, bits, layout, op, outs=None):
+        """spng_alpha_batch on device tensors: every tensor of `arrays` holds whole RGBA<T> / VA<T> pixels (T of `bits` bits)
+        and is premultiplied or straightened (`op`: PREMULTIPLY ... STRAIGHTEN_AS_U8; one value, or one per array, like
+        `layout`) into the tensor of `outs` at its place -- in place where outs is None.  -> list[Result] (aux[0]: components
+        the reference would have trapped on, written as T.max)"""
+        n = len(arrays)
+        descs = (AlphaDesc * max(n, 1))()
+        for i, t in enumerate(arrays):
+            lay = layout[i] if isinstance(layout, (list, tuple)) else layout
+            o = outs[i] if outs is not None else t
+            nbytes = t.numel() * t.element_size()
+            per = (4, 2)[lay] * (bits // 8)
+            if nbytes % per or o.numel() * o.element_size() < nbytes:
+                raise ValueError("an array of whole pixels and an output of at least its size are needed")
+            descs[i] = AlphaDesc(self._ptr(t), self._ptr(o), nbytes // per, bits, lay, op[i] if isinstance(op, (list, tuple)) else op)
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_alpha_batch(self.ctx, descs, n, None, res))
+        return list(res)[:n]
+
+    def alpha(self, pixels: bytes, bits, layout, op):
+        """pixels.map(\\.premultiplied) / .map(\\.straightened) and their (as: UInt8.self) forms for [PNG.RGBA<T>] / [PNG.VA<T>]
+        as bytes (host order): -> (bytes, trapped components)"""
+        per = (4, 2)[layout] * (bits // 8)
+        if len(pixels) % per:
+            raise ValueError("whole pixels are needed")
+        src = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
+        out = (ctypes.c_uint8 * max(len(pixels), 1))()
+        res = Result()
+        _check(self.lib, self.lib.spng_alpha(self.ctx, src, len(pixels) // per, bits, int(layout), int(op), out, ctypes.byref(res)))
+        return bytes(out[:len(pixels)]), int(res.aux[0])
 
     def deflate(self, data: bytes, level: int, fmt=FORMAT_ZLIB, exponent: int = 15) -> bytes:
         """Whole-stream LZ77.Deflator (push(all, last: true) + concatenated pull()): -> stream bytes"""

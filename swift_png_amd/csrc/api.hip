@@ -1560,7 +1560,8 @@ int32_t spng_unpack_batch(spng_ctx *c, const spng_unpack_desc *descs, uint32_t c
         const spng_unpack_desc &d = descs[i];
         if (!valid_format(d.depth, d.channels) || !d.d_storage || !d.d_out || d.target != target ||
             (d.indexed && (d.channels != 1 || d.depth > 8 || (!d.d_palette && d.palette_count))) ||
-            d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_PREMULTIPLY_AS_U8 || (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && target != 16) ||
+            d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_STRAIGHTEN_AS_U8 ||
+            ((d.premultiply == SPNG_PREMULTIPLY_AS_U8 || d.premultiply == SPNG_STRAIGHTEN_AS_U8) && target != 16) ||
             (d.layout == SPNG_TARGET_SCALAR && d.premultiply))
             return SPNG_E_ARGUMENT;
         UnpackJob j;
@@ -1629,13 +1630,16 @@ int32_t spng_pack_batch(spng_ctx *c, const spng_pack_desc *descs, uint32_t count
         const spng_pack_desc &d = descs[i];
         if (!valid_format(d.depth, d.channels) || !d.d_storage || !d.d_pixels || d.source != source ||
             (d.indexed && (d.channels != 1 || d.depth > 8 || (!d.d_palette && d.palette_count) || d.palette_count > 256)) ||
-            d.layout > SPNG_TARGET_SCALAR || ((uintptr_t)d.d_pixels & (source / 8 - 1)))
+            d.layout > SPNG_TARGET_SCALAR || ((uintptr_t)d.d_pixels & (source / 8 - 1)) ||
+            d.premultiply > SPNG_PREMULTIPLY_AS_U8 || (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && source != 16) ||
+            (d.layout == SPNG_TARGET_SCALAR && d.premultiply))
             return SPNG_E_ARGUMENT;
         PackJob j;
         memset(&j, 0, sizeof j);
         j.pixels = d.d_pixels; j.storage = (uint8_t *)d.d_storage; j.palette = (const uint8_t *)d.d_palette;
         j.width = d.width; j.height = d.height; j.palette_count = d.palette_count;
         j.depth = d.depth; j.channels = d.channels; j.indexed = d.indexed; j.bgr = d.bgr; j.layout = d.layout;
+        j.premultiply = d.premultiply;
         a.host<PackJob>(jslot)[i] = j;
         const uint64_t px = (uint64_t)d.width * d.height;
         maxpix = px > maxpix ? px : maxpix;
@@ -1668,6 +1672,63 @@ int32_t spng_pack_as(spng_ctx *c, const void *pixels, uint32_t w, uint32_t h, in
     if (int32_t st = spng_pack_batch(c, &d, 1)) return st;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (s) HIP_TRY(hipMemcpy(storage, ds.p, s, hipMemcpyDeviceToHost));
+    return SPNG_DONE;
+}
+
+int32_t spng_alpha_batch(spng_ctx *c, const spng_alpha_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    const int bits = descs[0].bits;
+    if (bits != 8 && bits != 16) return SPNG_E_ARGUMENT;
+    if (int32_t st = c->reserve(count * (sizeof(AlphaJob) + sizeof(spng_result)) + 1024)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(AlphaJob)), rslot = a.take(count * sizeof(spng_result));
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    uint64_t most = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_alpha_desc &d = descs[i];
+        const uint64_t bytes = d.count * (d.layout == SPNG_TARGET_VA ? 2u : 4u) * (bits / 8);
+        const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out;
+        bool bad = d.bits != bits || d.layout > SPNG_TARGET_VA || d.op < SPNG_PREMULTIPLY || d.op > SPNG_STRAIGHTEN_AS_U8 ||
+                   ((d.op == SPNG_PREMULTIPLY_AS_U8 || d.op == SPNG_STRAIGHTEN_AS_U8) && bits != 16) ||
+                   d.count > (~0ull >> 4) || ((in | out) & (bits / 8 - 1)) || (d.count && (!in || !out)) ||
+                   (in != out && in < out + bytes && out < in + bytes);
+        for (uint8_t r : d.reserved) bad = bad || r;
+        if (bad) return SPNG_E_ARGUMENT;
+        AlphaJob j;
+        memset(&j, 0, sizeof j);
+        j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.result = dr + i; j.layout = d.layout; j.op = d.op;
+        a.host<AlphaJob>(jslot)[i] = j;
+        spng_result r{};
+        r.status = SPNG_DONE; r.written = bytes; r.consumed = bytes;
+        a.host<spng_result>(rslot)[i] = r;                      // (aux[0]: the kernel adds the trapped components)
+        most = bytes > most ? bytes : most;
+    }
+    if (d_results)
+        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
+    if (int32_t st = c->upload(0, a.off)) return st;
+    uint64_t bx = (most + 16383) / 16384;                       // (16 bytes per thread, 256 threads, a few rounds)
+    if (bx > 4096) bx = 4096;
+    { Timed t(c, SPNG_K_ALPHA); HIP_TRY(launch_alpha(a.dev<AlphaJob>(jslot), count, (uint32_t)bx, bits, c->stream)); }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+int32_t spng_alpha(spng_ctx *c, const void *pixels, uint64_t n, int bits, int layout, int op, void *out, spng_result *result)
+{
+    if (!c || (n && (!pixels || !out)) || !result || (bits != 8 && bits != 16) || layout < 0 || layout > SPNG_TARGET_VA ||
+        op < 0 || op > 255 || n > (~0ull >> 4)) return SPNG_E_ARGUMENT;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t bytes = n * (layout == SPNG_TARGET_VA ? 2u : 4u) * (bits / 8);
+    DevBuf dpx;
+    HIP_TRY(dpx.alloc(bytes));
+    if (bytes) HIP_TRY(hipMemcpyAsync(dpx.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    spng_alpha_desc d{};
+    d.d_in = dpx.p; d.d_out = dpx.p; d.count = n; d.bits = (uint8_t)bits; d.layout = (uint8_t)layout; d.op = (uint8_t)op;
+    if (int32_t st = spng_alpha_batch(c, &d, 1, nullptr, result)) return st;
+    if (bytes) HIP_TRY(hipMemcpy(out, dpx.p, bytes, hipMemcpyDeviceToHost));
     return SPNG_DONE;
 }
 

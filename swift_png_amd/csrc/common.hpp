@@ -116,7 +116,16 @@ struct PackJob {
     uint32_t       width, height;
     uint32_t       palette_count;
     uint8_t        depth, channels, indexed, bgr;
-    uint8_t        layout, pad[3];           // spng_pack_desc.layout
+    uint8_t        layout, premultiply, pad[2];   // spng_pack_desc.layout / .premultiply
+};
+
+// One array of colour-target pixels to premultiply or straighten (alpha.hip, alpha_kernel)
+struct AlphaJob {
+    const void    *in;
+    void          *out;           // == in: in place
+    uint64_t       count;         // pixels
+    spng_result   *result;        // filled in by the host; the kernel adds the trapped components to aux[0]
+    uint8_t        layout, op, pad[6];       // spng_alpha_desc.layout / .op
 };
 
 struct InflateJob {
@@ -358,6 +367,7 @@ hipError_t launch_deflate2_parse(const D2Stream *d_streams, uint32_t count, cons
 hipError_t launch_deflate2_failed(const D2Stream *d_streams, uint32_t count, uint32_t *d_failed, hipStream_t stream);
 hipError_t launch_unpack(const UnpackJob *d_jobs, uint32_t count, uint32_t blocks_x, int target, hipStream_t stream);
 hipError_t launch_pack(const PackJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
+hipError_t launch_alpha(const AlphaJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
 size_t lex_chunk_bytes();
 size_t lex_walk_bytes();
 hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed *d_out, void *d_table, const uint64_t *d_table_at,

@@ -10,9 +10,11 @@
 // r = g = b, alpha T.max when the format has none, 0 for a pixel that equals the tRNS chroma key (compared at the source
 // depth), palette entries dereferenced (r, g, b, a as UInt8, then widened), bgr / bgra (CgBI) swizzled to rgb.  A VA
 // target keeps (r, a) of that -- the grey value, or the red channel of a colour format.  Premultiplied targets
-// (.premultiplied, or .premultiplied(as: UInt8.self) for T = UInt16: what the reference's iOS goldens are compared in).
+// (.premultiplied, or .premultiplied(as: UInt8.self) for T = UInt16: what the reference's iOS goldens are compared in) and
+// straightened ones (.straightened / .straightened(as: UInt8.self), PNG.RGBA.swift:167-206: the first step of the reference's
+// iPhone-optimized tutorial, fused).
 // HBM-bound: reads S, writes the target.  Four pixels per thread; RGBA8 -> RGBA<UInt8> moves 16 bytes per lane each way.
-#include "common.hpp"
+#include "alpha.hpp"
 
 namespace spng {
 
@@ -83,7 +85,13 @@ __global__ __launch_bounds__(256) void unpack_kernel(const UnpackJob *__restrict
         if (job.premultiply) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if (job.premultiply == 2 && TB == 16) {
+                if (job.premultiply >= SPNG_STRAIGHTEN) {
+                    // .straightened / .straightened(as: UInt8.self): a component the reference traps on becomes T.max without
+                    // a word (spng_alpha_batch is the entry that counts them)
+                    uint32_t c[3] = {px[k][0], px[k][1], px[k][2]}, uncounted = 0;
+                    alpha_pixel_op<TB, 3>(job.premultiply, c, px[k][3], uncounted);
+                    px[k][0] = c[0]; px[k][1] = c[1]; px[k][2] = c[2];
+                } else if (job.premultiply == 2 && TB == 16) {
                     // .premultiplied(as: UInt8.self): in eight bits, scaled back by T.max / 255 (alpha too)
                     const uint32_t a8 = px[k][3] >> 8;
                     for (int z = 0; z < 3; ++z) px[k][z] = premul(px[k][z] >> 8, a8, 0xff) * 257u;
@@ -139,6 +147,9 @@ __global__ __launch_bounds__(256) void unpack_kernel(const UnpackJob *__restrict
 //                       equal to (r, g, b, a) | (v, v, v, a) | (v, v, v, 255), entry 0 when there is none.  The reference builds a
 //                       Dictionary(uniqueKeysWithValues:) and traps on a palette that holds a colour twice; here the lowest index
 //                       of a repeated colour wins (the mirror refuses such palettes like the reference).
+//   premultiplication   job.premultiply: the components are premultiplied (.premultiplied / .premultiplied(as: UInt8.self),
+//                       PNG.RGBA.swift:121-158) before anything else: pack(pixels.map(\.premultiplied)) in one pass.  The two
+//                       16-byte paths below move pixels without looking at them and are not taken then.
 // HBM-bound: reads the pixels, writes S.  Four pixels per thread; RGBA<UInt8> -> rgba8 moves 16 bytes per lane each way.
 static constexpr uint32_t PACK_SLOTS = 1024;                    // open addressing, <= 256 entries: load factor <= 1/4
 __device__ __forceinline__ uint32_t pack_hash(uint32_t c) { return (c * 0x9E3779B1u) >> 22; }
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackJob *__restrict__ j
         }
         __syncthreads();
     }
-    const bool fast = TB == 8 && depth == 8 && ch == 4 && !job.indexed && job.layout == 0 &&
+    const bool fast = TB == 8 && depth == 8 && ch == 4 && !job.indexed && job.layout == 0 && !job.premultiply &&
                       (((uintptr_t)job.storage | (uintptr_t)job.pixels) & 3) == 0;
     const bool words = ((uintptr_t)job.storage & 3) == 0;
     const T *in = (const T *)job.pixels;
@@ -192,7 +203,8 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackJob *__restrict__ j
         }
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};               // the storage bytes of up to four pixels (<= 32), in memory order
         uint32_t at = 0;
-        const bool rgb_fast = TB == 8 && depth == 8 && ch == 3 && !job.indexed && job.layout == 0 && ((uintptr_t)job.pixels & 3) == 0;
+        const bool rgb_fast = TB == 8 && depth == 8 && ch == 3 && !job.indexed && job.layout == 0 && !job.premultiply &&
+                              ((uintptr_t)job.pixels & 3) == 0;
         if (rgb_fast && m == 4) {
             // [RGBA<UInt8>] -> rgb8 / bgr8: four pixels = one 16-byte load, twelve bytes out (alpha dropped)
             v4u v = ((const PV4 *)((const uint32_t *)in + i0))->v;
@@ -210,6 +222,11 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackJob *__restrict__ j
             if (job.layout == 0) { const T *p = in + i * 4; r = p[0]; g = p[1]; b = p[2]; a = p[3]; }
             else if (job.layout == 1) { const T *p = in + i * 2; r = g = b = p[0]; a = p[1]; }
             else { r = g = b = in[i]; }
+            if (job.premultiply) {
+                uint32_t c[3] = {r, g, b}, none = 0;
+                alpha_pixel_op<TB, 3>(job.premultiply, c, a, none);
+                r = c[0]; g = c[1]; b = c[2];
+            }
             if (job.indexed) {
                 const uint32_t s8 = TB - 8;
                 const uint32_t c = (r >> s8) | (g >> s8) << 8 | (b >> s8) << 16 | (a >> s8) << 24;

@@ -9,7 +9,8 @@ inflated bytes so far, and the point (a block boundary) from which the next push
 from __future__ import annotations
 
 from . import (DONE, FORMAT_GZIP, FORMAT_IOS, FORMAT_ZLIB, NEED_MORE_INPUT, DecodingError, SpngError,
-               E_EXTRANEOUS_COMPRESSED_DATA, E_INCOMPLETE_DATASTREAM, E_OUTPUT_CAPACITY, IMAGE_OVERDRAW)
+               E_EXTRANEOUS_COMPRESSED_DATA, E_INCOMPLETE_DATASTREAM, E_OUTPUT_CAPACITY, IMAGE_OVERDRAW,
+               PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8, TARGET_RGBA, TARGET_VA)
 
 _DELAY_FORMATS = {1: (8, 1), 2: (8, 2), 3: (8, 3), 4: (8, 4), 6: (16, 3), 8: (16, 4)}
 
@@ -210,10 +211,52 @@ class Gzip:
         return out
 
 
+def _alpha(layout, pixels, bits, op, session):
+    """an array of RGBA<T> / VA<T> pixels (numpy array of T, or bytes in host order) through spng_alpha: -> (the same kind of
+    object, components the reference would have trapped on)"""
+    from . import load
+    s = session or load()
+    if isinstance(pixels, (bytes, bytearray, memoryview)):
+        return s.alpha(bytes(pixels), bits, layout, op)
+    import numpy as np
+    a = np.ascontiguousarray(pixels)
+    if a.dtype.itemsize * 8 != bits or a.dtype.kind != "u":
+        raise ValueError("the array's element type must be the unsigned integer of `bits` bits")
+    out, trapped = s.alpha(a.tobytes(), bits, layout, op)
+    return np.frombuffer(out, dtype=a.dtype).reshape(a.shape).copy(), trapped
+
+
+class _ColorTarget:
+    """premultiplied / straightened of a colour target mapped over an array of pixels, on the device"""
+    _layout = TARGET_RGBA
+
+    @classmethod
+    def premultiplied(cls, pixels, bits, as_u8=False, session=None):
+        """.premultiplied / .premultiplied(as: UInt8.self) (PNG.RGBA.swift:121-158, PNG.VA.swift:57-87)"""
+        return _alpha(cls._layout, pixels, bits, PREMULTIPLY_AS_U8 if as_u8 else PREMULTIPLY, session)[0]
+
+    @classmethod
+    def straightened(cls, pixels, bits, as_u8=False, session=None):
+        """.straightened / .straightened(as: UInt8.self) (PNG.RGBA.swift:167-206, PNG.VA.swift:98-131).  Where the reference
+        traps -- a colour above its alpha: the quotient does not fit T -- this raises ValueError."""
+        out, trapped = _alpha(cls._layout, pixels, bits, STRAIGHTEN_AS_U8 if as_u8 else STRAIGHTEN, session)
+        if trapped:
+            raise ValueError(f"{trapped} components exceed their alpha: not representable in T (the reference traps)")
+        return out
+
+
 class PNG:
     class Standard:
         common = FORMAT_ZLIB
         ios = FORMAT_IOS
+
+    class RGBA(_ColorTarget):
+        """PNG.RGBA<T> (Sources/PNG/ColorTargets/PNG.RGBA.swift): arrays of (r, g, b, a)"""
+        _layout = TARGET_RGBA
+
+    class VA(_ColorTarget):
+        """PNG.VA<T> (Sources/PNG/ColorTargets/PNG.VA.swift): arrays of (v, a)"""
+        _layout = TARGET_VA
 
     class Decoder:
         @staticmethod

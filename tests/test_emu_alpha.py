@@ -1,0 +1,39 @@
+"""alpha_kernel of csrc/alpha.hip (premultiplied <-> straight alpha: PNG.premultiply / PNG.straighten, Sources/PNG/PNG.swift:55-117,
+without an integer division) run on the CPU by the wave emulator of tools/emu (host compiler: the ROCm clang++) against the
+formulas restated with plain `/` in tools/emu/emu_alpha.cpp: exhaustively at 8 bits, every alpha at 16 bits, and the whole
+numerator range of the divide-by-T.max identity."""
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
+
+CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
+        pytest.skip("clang++ not available")
+    import prep_deflate
+    d = tmp_path_factory.mktemp("emu_alpha")
+    inc = d / "alpha_emu.inc"
+    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "alpha.hip")).read()))
+    out = d / "emu_alpha"
+    subprocess.run([CLANG, "-O2", "-std=c++17", "-DSPNG_EMU", f'-DEMU_ALPHA_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
+                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
+                    os.path.join(ROOT, "tools", "emu", "emu_alpha.cpp")], check=True, capture_output=True, timeout=600)
+    return out
+
+
+@pytest.mark.parametrize("mode", ["grid8", "sweep16", "divmax"])
+def test_emulated_alpha_kernel_matches_plain_division(emu, mode):
+    """grid8: all 65536 (c, a) pairs, four operations (the (as: UInt8.self) forms on 16-bit input), both layouts, aligned and not,
+    in and out of place, with the trap count.  sweep16: every 16-bit alpha with the components around it and random ones.
+    divmax: x / (2^k - 1) == (x + 1 + (x >> k)) >> k for every numerator c * a + (M >> 1) can be, k = 8 and 16."""
+    r = subprocess.run([str(emu), mode], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (mode, r.stdout[-600:], r.stderr[-600:])

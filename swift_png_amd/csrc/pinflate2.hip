@@ -127,10 +127,13 @@ struct DPool { uint8_t *base; uint32_t *next; uint32_t pages, pad; };   // next[
 // Emulator builds can count how often the rare paths of the decode rounds ran (tests/test_emu_pinflate.py asserts that its cases
 // reach every one of them): COV(k) is nothing in the product.
 #if defined(SPNG_EMU) && defined(SPNG_EMU_COV)
-static long g_cov[12];     // 0 reference on a subsequence's last bit, 1 reference on a word's last bit, 2 chunks with marks for references,
+static long g_cov[13];     // 0 reference on a subsequence's last bit, 1 reference on a word's last bit, 2 chunks with marks for references,
                            // 3 chunks with kind masks, 4 pairs cut at a subsequence's end, 5 round-1 landings on a reference's second mark
                            // block cuts: 6 a guess slid on after a bogus end of block or an undefined code, 7 a join decoded more than one
                            // chunk, 8 a stream sent to the retry pass
+                           // resolve: 9 a tile ended by the cap on its back-references (MAXM), 10 a byte beyond its run's first period,
+                           // 11 a marker made for a byte in front of the part, 12 an offset that the period reduction left at or beyond
+                           // its distance (never: a quotient one too small still finds the right byte, one level deeper in the chain)
 #define COV(k) __atomic_fetch_add(&g_cov[k], 1, __ATOMIC_RELAXED)
 #else
 #define COV(k) ((void)0)
@@ -1892,7 +1895,7 @@ __global__ __launch_bounds__(RT2, SPNG_R_WAVES) void pinf2_resolve_kernel(const 
             const bool front = curb <= TILE2 && curm <= MAXM2;
             const bool fits = curb + bytes <= TILE2 && curm + refs <= MAXM2 &&
                               !(tid == (int)RT2 - 1 && (hh[HPT2 - 1] & 0xC000) == 0x8000);
-            if (front && !fits) { s.cut[0] = curb; s.cut[1] = (uint32_t)tid * HPT2; }
+            if (front && !fits) { s.cut[0] = curb; s.cut[1] = (uint32_t)tid * HPT2; if (curb + bytes <= TILE2 && curm + refs > MAXM2) COV(9); }
             if (fits) {
 #pragma unroll
                 for (int j = 0; j < (int)HPT2; ++j) {
@@ -1974,7 +1977,9 @@ __global__ __launch_bounds__(RT2, SPNG_R_WAVES) void pinf2_resolve_kernel(const 
                         // away from an integer at least) and the product a 24-bit multiply.  (Round 5 also tried the reciprocals from
                         // a table, kept in four-word records -- 5 full-rate instructions per byte here instead of 14 issue slots: the
                         // kernel took as long as before; the expand phase is not bound by its instruction count.  r05_tuning.md)
+                        if (inside && kk2 >= d) COV(10);
                         if (inside && kk2 >= d) kk2 -= mul24(d, (uint32_t)(((float)kk2 + 0.5f) * __builtin_amdgcn_rcpf((float)d)));
+                        if (inside && kk2 >= d) COV(12);
                         siv[kk] = inside ? startb - d + kk2 : 0x7fffffffu;                     // >= 0x80000000: before the tile
                         farv[kk] = s.ring[(rbase + siv[kk]) & (WINDOW2 - 1)];
                     }
@@ -1990,6 +1995,7 @@ __global__ __launch_bounds__(RT2, SPNG_R_WAVES) void pinf2_resolve_kernel(const 
                                 // in front of the tile: the symbol in the ring, or -- in front of the part -- a marker
                                 const uint32_t rel = (uint32_t)(pos - part_pos) + si;             // (from the part's first byte)
                                 v = (int32_t)si >= 0 ? si : (!EARLY || (int32_t)rel >= 0) ? farv[kk] : 0x8000u | (rel + WINDOW2);
+                                if (EARLY && (int32_t)si < 0 && (int32_t)rel < 0) COV(11);
                             } else {
                                 if (EARLY && (int32_t)si < 0 && (uint32_t)pos < 0u - si) bad = true;
                                 v = (int32_t)si < 0 ? DONE | farv[kk] : si;

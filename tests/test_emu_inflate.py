@@ -23,10 +23,14 @@ CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
+    return build_emu(tmp_path_factory.mktemp("emu_inflate"))
+
+
+def build_emu(d):
+    """the serial kernel's emulator, built in directory d (also for tests/test_deflate_cases.py)"""
     if not (os.path.exists(CLANG) or shutil.which(CLANG)):
         pytest.skip("clang++ not available")
     import prep_deflate
-    d = tmp_path_factory.mktemp("emu_inflate")
     csrc = os.path.join(ROOT, "swift_png_amd", "csrc")
     inc, hh = prep_deflate.prepare_inflate(open(os.path.join(csrc, "inflate.hip")).read(), open(os.path.join(csrc, "huffman.hpp")).read(),
                                            str(d / "huffman_emu.hpp"), os.path.join(csrc, "common.hpp"))

@@ -15,15 +15,19 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def emu(tmp_path_factory):
+def build_emu(out, *defines):
+    """tools/emu/emu_pinflate2.cpp -> the program `out` (also for tests/test_deflate_cases.py)"""
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
-    out = tmp_path_factory.mktemp("emu") / "emu_pinflate2"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-DSPNG_EMU", "-I" + os.path.join(ROOT, "tools", "emu"), "-x", "c++", "-fpermissive",
+    subprocess.run(["g++", "-O1", "-std=c++17", "-DSPNG_EMU", *defines, "-I" + os.path.join(ROOT, "tools", "emu"), "-x", "c++", "-fpermissive",
                     "-Wno-attributes", "-w", "-o", str(out), os.path.join(ROOT, "tools", "emu", "emu_pinflate2.cpp")],
                    check=True, capture_output=True, timeout=600)
     return out
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    return build_emu(tmp_path_factory.mktemp("emu") / "emu_pinflate2")
 
 
 def scanlines(seed, n):

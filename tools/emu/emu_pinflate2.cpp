@@ -28,6 +28,8 @@ static std::vector<uint8_t> slurp(const char *path)
 #ifdef SPNG_EMU_COV
 static void cov_print()
 {
+    // (resolve's counters first: tests/test_emu_pinflate.py reads the last line that begins with COV)
+    fprintf(stderr, "RESOLVE_COV %ld %ld %ld %ld\n", spng::g_cov[9], spng::g_cov[10], spng::g_cov[11], spng::g_cov[12]);
     fprintf(stderr, "COV"); for (int i = 0; i < 6; ++i) fprintf(stderr, " %ld", spng::g_cov[i]); fprintf(stderr, "\n");
     if (getenv("EMU_CUT_BYTES")) fprintf(stderr, "COVCUT %ld %ld %ld\n", spng::g_cov[6], spng::g_cov[7], spng::g_cov[8]);
 }

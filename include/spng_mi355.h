@@ -170,7 +170,9 @@ enum { SPNG_K_INFLATE = 0,          /* the serial inflate kernel (streams the pa
        SPNG_K_PINF_FIND = 8, SPNG_K_PINF_DECODE = 9, SPNG_K_PINF_RESOLVE = 11,   /* its stages */
        SPNG_K_DFL_SEARCH = 13, SPNG_K_DFL_PARSE = 14,   /* levels >= 8: the two kernels of a round (inside SPNG_K_DEFLATE) */
        SPNG_K_ALPHA = 15,           /* spng_alpha_batch */
-       SPNG_K_COUNT = 16 };
+       SPNG_K_CENSUS = 16,          /* spng_census_batch: the counting kernel and the sort behind it */
+       SPNG_K_PACK_INDEXED = 17,    /* spng_pack_indexed_batch */
+       SPNG_K_COUNT = 18 };
 int32_t spng_profile(spng_ctx *ctx, int enable);                /* enable/disable + reset counters  */
 int32_t spng_profile_get(spng_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 /* Token volume of the most recent parallel-inflate call whose figures have come back (they travel behind its kernels; this call
@@ -392,6 +394,68 @@ int32_t spng_alpha_batch(spng_ctx *ctx, const spng_alpha_desc *descs, uint32_t c
                          spng_result *d_results, spng_result *h_results);
 /* host-pointer convenience (copies in / out, synchronous): n pixels */
 int32_t spng_alpha(spng_ctx *ctx, const void *pixels, uint64_t n, int bits, int layout, int op, void *out, spng_result *result);
+
+/* ---- pixels: indexed colour with any pure indexer ---------------------------------------------------- */
+/* The reference takes an indexer closure wherever pixels are packed into an indexed format:
+ *   PNG.RGBA<T>.pack(_:as:indexer:)  ((UInt8, UInt8, UInt8, UInt8)) -> Int   Sources/PNG/ColorTargets/PNG.RGBA.swift:409-423
+ *   PNG.VA<T>.pack(_:as:indexer:)    ((UInt8, UInt8)) -> Int                 PNG.VA.swift:334-350
+ *   PNG.Image.pack<T>(_:as:indexer:) (UInt8) -> Int                          Sources/PNG/PNG.Image.swift:767-782
+ *   PNG.Image.init(packing:size:layout:metadata:indexer:)                    PNG.Image.swift:935-996
+ *   PNG.deconvolve(_:_:dereference:), which hands the closure its argument   Sources/PNG/PNG.swift:747-854
+ * Every argument is a UInt8 aggregate, so a pure closure is a table.  The KEY of a pixel is that aggregate as 32 bits: the
+ * components after the optional premultiplication, reduced to UInt8 as PNG.deconvolve does (PNG.swift:829-852: as they are for
+ * T = UInt8, >> 8 for T = UInt16),
+ *     RGBA: r | g << 8 | b << 16 | a << 24        VA: v | a << 8        scalar: v
+ * spng_census_batch reports the distinct keys of a pixel array (and how often each occurs: the frequencies of PNG.Histogram and
+ * of sPLT entries); the host evaluates the indexer once per key; spng_pack_indexed_batch stores the index of every pixel.  The
+ * storage can go straight to spng_encode_batch: the pixels never leave the device. */
+typedef struct spng_census_desc {
+    const void *d_pixels;                       /* `count` pixels, aligned to T */
+    uint64_t    count;
+    void       *d_keys;                         /* cap x uint32 */
+    void       *d_counts;                       /* cap x uint64, or NULL */
+    uint32_t    cap;                            /* 1 ... 65536 */
+    uint8_t     bits;                           /* 8 or 16: T = UInt8 / UInt16; all descs of a call share it */
+    uint8_t     layout;                         /* SPNG_TARGET_RGBA / _VA / _SCALAR */
+    uint8_t     premultiply;                    /* 0, SPNG_PREMULTIPLY or SPNG_PREMULTIPLY_AS_U8 (bits 16 only), as in spng_pack_desc:
+                                                   the keys of pixels.map(\.premultiplied).  Not with SPNG_TARGET_SCALAR */
+    uint8_t     reserved[1];                    /* zero */
+} spng_census_desc;
+/* At most `cap` distinct keys: status SPNG_DONE, written = their number n, consumed = count; d_keys[0 .. n) hold them in ascending
+ * order, d_counts[i] how many pixels have key i (the counts sum to `count`); both arrays are left untouched behind n.  More than
+ * `cap`: status SPNG_E_OUTPUT_CAPACITY, written = 0, the contents of both arrays unspecified (the kernel stops reading the
+ * pixels once it knows).  A count of 0 is valid: SPNG_DONE, written = 0.  The output is a function of the pixels alone -- never of
+ * the batch an array travels in, the launch or the run.  Scratch of the context: 16 bytes per slot of a table of 2 x cap slots
+ * (rounded up to a power of two) and 8 per key for the sort, per array of the call; spng_trim gives it back. */
+int32_t spng_census_batch(spng_ctx *ctx, const spng_census_desc *descs, uint32_t count,
+                          spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous): n pixels; keys: cap x uint32; counts: cap x uint64 or NULL */
+int32_t spng_census(spng_ctx *ctx, const void *pixels, uint64_t n, int bits, int layout, int premultiply, uint32_t cap,
+                    uint32_t *keys, uint64_t *counts, spng_result *result);
+
+typedef struct spng_pack_indexed_desc {
+    const void *d_pixels;                       /* width * height pixels, aligned to T */
+    void       *d_storage;                      /* one byte per pixel, any alignment: PNG.Image.storage of an indexed8 image, as the
+                                                   indexed path of spng_pack_batch writes it */
+    const void *d_keys;                         /* map_count x uint32, ASCENDING AND DISTINCT: the form the census writes */
+    const void *d_indices;                      /* map_count bytes: the indexer's result for each key */
+    uint32_t    width, height;
+    uint32_t    map_count;                      /* 0 ... 65536 */
+    uint8_t     source;                         /* 8 or 16: T = UInt8 / UInt16; all descs of a call share it */
+    uint8_t     layout, premultiply;            /* as in spng_census_desc */
+    uint8_t     miss;                           /* stored for a pixel whose key is not in d_keys */
+    uint8_t     reserved[8];                    /* zero */
+} spng_pack_indexed_desc;
+/* Every pixel stores d_indices[j] where d_keys[j] equals its key, and `miss` where none does.  Results: status SPNG_DONE,
+ * written = pixels, aux[0] = pixels that missed.  Keys that are not ascending and distinct are the caller's responsibility here
+ * (device memory is not looked at by the host; the lookup may then miss keys that are present, nothing worse); the host-pointer
+ * form below sees them and returns SPNG_E_ARGUMENT. */
+int32_t spng_pack_indexed_batch(spng_ctx *ctx, const spng_pack_indexed_desc *descs, uint32_t count,
+                                spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous) */
+int32_t spng_pack_indexed(spng_ctx *ctx, const void *pixels, uint32_t w, uint32_t h, int source, int layout, int premultiply,
+                          const uint32_t *keys, const uint8_t *indices, uint32_t map_count, int miss, void *storage,
+                          spng_result *result);
 
 /* ---- encode -------------------------------------------------------------------------------- */
 /* replaces PNG.Encoder.filter (PNG.Encoder.swift:132-204) + PNG.Image.collect

@@ -42,6 +42,11 @@ K_LEX = 12
 K_PINF_FIND, K_PINF_DECODE, K_PINF_RESOLVE = 8, 9, 11
 K_DFL_SEARCH, K_DFL_PARSE = 13, 14
 K_ALPHA = 15
+K_CENSUS, K_PACK_INDEXED = 16, 17
+# thresholds of csrc/indexing.hip (the tests take the sizes at which the kernels change paths from here)
+CENSUS_LDS_SLOTS, CENSUS_LDS_LIMIT = 2048, 512     # a workgroup's table; keys in it above which it is merged into the image's
+CENSUS_FINISH_LDS_KEYS = 4096                      # up to so many keys are sorted in LDS, more in the context's scratch
+PACK_INDEXED_LDS_KEYS = 512                        # maps of up to so many keys sit in an LDS hash table, larger ones are searched
 CFG_INFLATE_MODE, CFG_SEGMENT_BYTES, CFG_TOKEN_BYTES, CFG_UNFILTER_PIECE_ROWS, CFG_RESOLVE_PARTS = 0, 1, 2, 3, 5          # (4: reserved)
 CFG_DEFLATE_BYTES, CFG_MULTI_GROUPS = 7, 8          # (6: reserved)
 CFG_BLOCK_CUT_BYTES = 9                            # parallel inflate: shortest run of segments without a block start that is cut (bytes; 0: 1 MiB)
@@ -54,7 +59,7 @@ EXPORTS = [
     "spng_profile_get", "spng_token_stats", "spng_cut_stats", "spng_configure", "spng_inflate_batch", "spng_inflate_resume_batch", "spng_unfilter_batch",
     "spng_unfilter_resume_batch", "spng_decode_batch",
     "spng_inflate", "spng_unfilter", "spng_decode", "spng_adler32", "spng_filter_batch", "spng_filter",
-    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
+    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
 ]
 
@@ -119,6 +124,19 @@ class PackDesc(ctypes.Structure):
 class AlphaDesc(ctypes.Structure):
     _fields_ = [("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_uint64), ("bits", ctypes.c_uint8),
                 ("layout", ctypes.c_uint8), ("op", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 5)]
+
+
+class CensusDesc(ctypes.Structure):
+    _fields_ = [("d_pixels", ctypes.c_void_p), ("count", ctypes.c_uint64), ("d_keys", ctypes.c_void_p), ("d_counts", ctypes.c_void_p),
+                ("cap", ctypes.c_uint32), ("bits", ctypes.c_uint8), ("layout", ctypes.c_uint8), ("premultiply", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 1)]
+
+
+class PackIndexedDesc(ctypes.Structure):
+    _fields_ = [("d_pixels", ctypes.c_void_p), ("d_storage", ctypes.c_void_p), ("d_keys", ctypes.c_void_p),
+                ("d_indices", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("map_count", ctypes.c_uint32), ("source", ctypes.c_uint8), ("layout", ctypes.c_uint8),
+                ("premultiply", ctypes.c_uint8), ("miss", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 8)]
 
 
 class ChunkingDesc(ctypes.Structure):
@@ -251,6 +269,10 @@ def load_library():
                                  ctypes.c_int, vp, u32, vp]
     lib.spng_alpha_batch.argtypes = [vp, vp, u32, vp, rp]
     lib.spng_alpha.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, rp]
+    lib.spng_census_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_census.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32, vp, vp, rp]
+    lib.spng_pack_indexed_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_pack_indexed.argtypes = [vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, u32, ctypes.c_int, vp, rp]
     lib.spng_deflate_bound.restype = u64
     lib.spng_deflate_bound.argtypes = [u64]
     lib.spng_deflate_batch.argtypes = [vp, ctypes.POINTER(StreamDesc), ctypes.POINTER(i32), u32, vp, rp]
@@ -316,6 +338,52 @@ def _check(lib, st):
     if st != DONE:
         msg = lib.spng_last_error_string().decode() if st == E_DEVICE else lib.spng_status_string(st).decode()
         raise SpngError(st) if st != E_DEVICE else RuntimeError(f"libspng_mi355: {msg}")
+
+
+# ---- indexers and deindexers as tables -------------------------------------------------------------
+def palette_entries(palette):
+    """bytes of (r, g, b, a) quadruplets -> the list of tuples an indexer / deindexer of the reference is created with"""
+    p = bytes(palette or b"")
+    return [tuple(p[i:i + 4]) for i in range(0, len(p) - len(p) % 4, 4)]
+
+
+def key_aggregate(key: int, layout: int):
+    """the UInt8 aggregate the reference hands to an indexer for a pixel whose key is `key`: (r, g, b, a), (v, a) or v"""
+    if layout == TARGET_RGBA:
+        return (key & 255, key >> 8 & 255, key >> 16 & 255, key >> 24 & 255)
+    if layout == TARGET_VA:
+        return (key & 255, key >> 8 & 255)
+    return key & 255
+
+
+def tabulate_indexer(index, keys, layout) -> bytes:
+    """index: the closure an indexer made for a palette; keys: the pixel keys to evaluate it on -> one index byte per key.  An index
+    outside 0 ... 255 raises, where Swift's UInt8(_:) traps (PNG.RGBA.swift:421)."""
+    out = bytearray(len(keys))
+    for j, k in enumerate(keys):
+        i = int(index(key_aggregate(int(k), layout)))
+        if not 0 <= i <= 255:
+            raise OverflowError(f"indexer returned {i} for {key_aggregate(int(k), layout)}: not representable in UInt8")
+        out[j] = i
+    return bytes(out)
+
+
+def tabulate_deindexer(dereference, layout=TARGET_RGBA) -> bytes:
+    """dereference: the closure a deindexer made for a palette ((Int) -> (r, g, b, a) | (v, a) | v) -> the 256 x (r, g, b, a)
+    table spng_unpack_desc.d_palette takes: a VA target reads the r and a slots, a scalar target the r slot."""
+    out = bytearray(1024)
+    for i in range(256):
+        v = dereference(i)
+        if layout == TARGET_RGBA:
+            q = tuple(v)
+        elif layout == TARGET_VA:
+            q = (v[0], v[0], v[0], v[1])
+        else:
+            q = (v, v, v, 255)
+        if len(q) != 4 or not all(0 <= int(x) <= 255 for x in q):
+            raise OverflowError(f"deindexer returned {v!r} for {i}: UInt8 components are needed")
+        out[4 * i:4 * i + 4] = bytes(int(x) for x in q)
+    return bytes(out)
 
 
 class Session:
@@ -556,10 +624,16 @@ class Session:
         return out.value
 
     def unpack(self, storage: bytes, w, h, depth, channels, indexed=False, bgr=False, target=16, palette=None, key=None,
-               layout=0, premultiply=0):
+               layout=0, premultiply=0, deindexer=None):
         """PNG.Image.unpack(as: PNG.RGBA<UInt8 / UInt16>.self) (layout = TARGET_VA: PNG.VA<T>): -> bytes of r, g, b, a
         (v, a) per pixel (host order).  palette: bytes of (r, g, b, a) quadruplets (PLTE with the tRNS alphas folded in);
-        key: tRNS chroma key; premultiply: 0, PREMULTIPLY (.premultiplied) or PREMULTIPLY_AS_U8 (.premultiplied(as: UInt8.self))."""
+        key: tRNS chroma key; premultiply: 0, PREMULTIPLY (.premultiplied) or PREMULTIPLY_AS_U8 (.premultiplied(as: UInt8.self)).
+        deindexer (indexed formats): shaped like the reference's (unpack(as:deindexer:), PNG.Image.swift:836-933): deindexer(palette)
+        returns a function of the index; it is tabulated over 0 ... 255 into the palette the kernel dereferences."""
+        if deindexer is not None:
+            if not indexed:
+                raise ValueError("a deindexer needs an indexed format")
+            palette = tabulate_deindexer(deindexer(palette_entries(palette)), layout)
         n = w * h * (4, 2, 1)[layout] * (target // 8)
         src = (ctypes.c_uint8 * max(len(storage), 1)).from_buffer_copy(bytes(storage) or b"\0")
         out = (ctypes.c_uint8 * max(n, 1))()
@@ -570,11 +644,29 @@ class Session:
         return bytes(out[:n])
 
     def pack(self, pixels: bytes, w, h, depth, channels, indexed=False, bgr=False, source=16, palette=None, layout=0,
-             premultiply=0) -> bytes:
+             premultiply=0, indexer=None) -> bytes:
         """PNG.Image(packing:size:layout:).storage for [PNG.RGBA<T>] (layout TARGET_RGBA), [PNG.VA<T>] (TARGET_VA) or [T]
         (TARGET_SCALAR), T = UInt8 / UInt16 (`source` bits), with the default indexer: pixels = bytes of r, g, b, a | v, a | v per
         pixel (host order) -> storage bytes.  palette: bytes of (r, g, b, a) quadruplets.  premultiply: 0, PREMULTIPLY or
-        PREMULTIPLY_AS_U8 -- pack(pixels.map(\\.premultiplied)) in one pass (spng_pack_desc.premultiply)."""
+        PREMULTIPLY_AS_U8 -- pack(pixels.map(\\.premultiplied)) in one pass (spng_pack_desc.premultiply).
+        indexer (indexed8 only): shaped like the reference's (init(packing:size:layout:metadata:indexer:), PNG.Image.swift:935-996):
+        indexer(palette) returns a function of the UInt8 aggregate -- (r, g, b, a), (v, a) or v -- that returns the index.  Scalar
+        and VA layouts tabulate it over all 256 / 65536 aggregates; the RGBA layout asks the device for the distinct colours of the
+        pixels (census, at most 65536: SpngError(E_OUTPUT_CAPACITY) above) and calls it once per colour."""
+        if indexer is not None:
+            if not indexed or depth != 8:
+                raise ValueError("an indexer needs the indexed8 format")
+            if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
+                raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
+            index = indexer(palette_entries(palette))
+            if layout == TARGET_RGBA:
+                keys, _ = self.census(pixels, source, layout, cap=65536, premultiply=premultiply)
+            else:
+                keys = range(256 if layout == TARGET_SCALAR else 65536)
+            keys = list(keys)
+            storage, _ = self.pack_indexed(pixels, w, h, source, layout, keys, tabulate_indexer(index, keys, layout),
+                                           premultiply=premultiply)
+            return storage
         px = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
         if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
             raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
@@ -593,6 +685,87 @@ class Session:
         _check(self.lib, self.lib.spng_pack_as(self.ctx, px, w, h, depth, channels, int(bool(indexed)), int(bool(bgr)), source,
                                                int(layout), pal if palette else None, len(palette or b"") // 4, out))
         return bytes(out[:n])
+
+    def census_batch(self, arrays, bits, layout, cap=256, premultiply=0, counts=True, outs=None):
+        """spng_census_batch on device tensors: every tensor of `arrays` holds whole RGBA<T> / VA<T> / T pixels (T of `bits`
+        bits; layout, cap and premultiply: one value, or one per array).  -> (list of (keys, counts) device tensors -- int32 /
+        int64 bit patterns of the uint32 keys and uint64 counts, `cap` long, valid up to Result.written; or the (keys, counts) pairs of
+        `outs`, of at least 4 * cap / 8 * cap bytes --, list[Result]).  Like every batch entry it runs on the context's stream: tensors
+        that torch kernels are still writing have to be waited for first."""
+        n = len(arrays)
+        t = self.torch
+        pick = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
+        descs = (CensusDesc * max(n, 1))()
+        given, outs = outs, []
+        for i, a in enumerate(arrays):
+            lay, cp = pick(layout, i), pick(cap, i)
+            nbytes, per = a.numel() * a.element_size(), (4, 2, 1)[lay] * (bits // 8)
+            if nbytes % per:
+                raise ValueError("an array of whole pixels is needed")
+            if given is not None:
+                k, c = given[i]
+                if k.numel() * k.element_size() < 4 * cp or (c is not None and c.numel() * c.element_size() < 8 * cp):
+                    raise ValueError("outputs of cap keys and cap counts are needed")
+            else:
+                k = t.empty(max(cp, 1), dtype=t.int32, device=self.tdev)
+                c = t.empty(max(cp, 1), dtype=t.int64, device=self.tdev) if counts else None
+            outs.append((k, c))
+            descs[i] = CensusDesc(self._ptr(a), nbytes // per, self._ptr(k), self._ptr(c), cp, bits, lay, pick(premultiply, i))
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_census_batch(self.ctx, descs, n, None, res))
+        return outs, list(res)[:n]
+
+    def census(self, pixels: bytes, bits, layout, cap=256, premultiply=0):
+        """The distinct UInt8 aggregates ("keys": r | g << 8 | b << 16 | a << 24, v | a << 8 or v) of [PNG.RGBA<T>] / [PNG.VA<T>] /
+        [T] as bytes (host order), ascending, and how many pixels have each: -> (list of keys, list of counts).  More than `cap`
+        (at most 65536) distinct keys raise SpngError(E_OUTPUT_CAPACITY)."""
+        per = (4, 2, 1)[layout] * (bits // 8)
+        if len(pixels) % per:
+            raise ValueError("whole pixels are needed")
+        src = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
+        keys, counts = (ctypes.c_uint32 * max(cap, 1))(), (ctypes.c_uint64 * max(cap, 1))()
+        res = Result()
+        _check(self.lib, self.lib.spng_census(self.ctx, src, len(pixels) // per, bits, int(layout), int(premultiply), cap, keys, counts,
+                                              ctypes.byref(res)))
+        raise_for(res.status)
+        return list(keys[:res.written]), list(counts[:res.written])
+
+    def pack_indexed_batch(self, arrays, sizes, source, layout, keys, indices, miss=0, premultiply=0, storages=None):
+        """spng_pack_indexed_batch on device tensors: arrays[i] holds sizes[i] = (w, h) pixels; keys[i] (uint32, ascending and
+        distinct, int32 bit patterns) and indices[i] (uint8) are its map, equally long.  -> (list of storage tensors, list[Result]
+        with aux[0] = pixels that missed)"""
+        n = len(arrays)
+        pick = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
+        descs = (PackIndexedDesc * max(n, 1))()
+        outs = []
+        for i, a in enumerate(arrays):
+            w, h = sizes[i]
+            o = storages[i] if storages is not None else self.empty(w * h)
+            outs.append(o)
+            k, ix = keys[i], indices[i]
+            mc = ix.numel() if ix is not None else 0
+            descs[i] = PackIndexedDesc(self._ptr(a), self._ptr(o), self._ptr(k) if mc else None, self._ptr(ix) if mc else None, w, h, mc,
+                                       source, pick(layout, i), pick(premultiply, i), pick(miss, i))
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_pack_indexed_batch(self.ctx, descs, n, None, res))
+        return outs, list(res)[:n]
+
+    def pack_indexed(self, pixels: bytes, w, h, source, layout, keys, indices, miss=0, premultiply=0):
+        """One index byte per pixel: indices[j] where keys[j] (ascending, distinct) is the pixel's key, `miss` where none is.
+        -> (storage bytes, pixels that missed)"""
+        if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
+            raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
+        if len(keys) != len(indices):
+            raise ValueError("one index per key is needed")
+        px = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
+        k = (ctypes.c_uint32 * max(len(keys), 1))(*keys)
+        ix = (ctypes.c_uint8 * max(len(indices), 1))(*bytes(indices))
+        out = (ctypes.c_uint8 * max(w * h, 1))()
+        res = Result()
+        _check(self.lib, self.lib.spng_pack_indexed(self.ctx, px, w, h, source, int(layout), int(premultiply), k, ix, len(keys),
+                                                    int(miss), out, ctypes.byref(res)))
+        raise_for(res.status)
+        return bytes(out[:w * h]), int(res.aux[0])
 
     def alpha_batch(self, arrays, bits, layout, op, outs=None):
         """spng_alpha_batch on device tensors: every tensor of `arrays` holds whole RGBA<T> / VA<T> pixels (T of `bits` bits)

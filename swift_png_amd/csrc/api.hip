@@ -87,6 +87,7 @@ struct spng_ctx {
     void *d_sym = nullptr;  size_t sym_cap = 0;      // several workgroups per stream: 16-bit symbols, windows (bytes)
     uint64_t sym_failed = 0;                        // a symbol scratch of this size could not be had (forgotten by spng_trim)
     void *d_win = nullptr;  size_t win_cap = 0;
+    void *d_census = nullptr; size_t census_cap = 0; // spng_census_batch: the images' hash tables and sort buffers
     // token pool of the pipeline (pinflate2.hip): halfwords a compressed byte turned into in the last batch (learned,
     // so that the next batch of the same kind takes one pass), and the pinned word the page counter is read back into
     double   pool_ratio = 0;
@@ -115,9 +116,10 @@ struct spng_ctx {
 
     // the buffers a batch sizes (spng_trim gives them back to the device; d_ws, the job tables', stays)
     struct Buf { void **p; size_t *cap; };
-    std::array<Buf, 6> batch_buffers()
+    std::array<Buf, 7> batch_buffers()
     {
-        return {{{&d_graph, &graph_cap}, {&d_log, &log_cap}, {&d_tok, &tok_cap}, {&d_sym, &sym_cap}, {&d_win, &win_cap}, {&d_multi, &multi_cap}}};
+        return {{{&d_graph, &graph_cap}, {&d_log, &log_cap}, {&d_tok, &tok_cap}, {&d_sym, &sym_cap}, {&d_win, &win_cap}, {&d_multi, &multi_cap},
+                 {&d_census, &census_cap}}};
     }
     // Makes a device buffer of the context hold `need` bytes.  Only when it has to grow: waits for the stream (kernels in
     // flight may still read the old one), frees it and allocates need + slack.  A failed allocation is an error -- or, `failed`
@@ -1729,6 +1731,147 @@ int32_t spng_alpha(spng_ctx *c, const void *pixels, uint64_t n, int bits, int la
     d.d_in = dpx.p; d.d_out = dpx.p; d.count = n; d.bits = (uint8_t)bits; d.layout = (uint8_t)layout; d.op = (uint8_t)op;
     if (int32_t st = spng_alpha_batch(c, &d, 1, nullptr, result)) return st;
     if (bytes) HIP_TRY(hipMemcpy(out, dpx.p, bytes, hipMemcpyDeviceToHost));
+    return SPNG_DONE;
+}
+
+int32_t spng_census_batch(spng_ctx *c, const spng_census_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    const int bits = descs[0].bits;
+    if (bits != 8 && bits != 16) return SPNG_E_ARGUMENT;
+    // the scratch: {ctrl, tags, counts} of every array first -- one block to zero --, the sort buffers behind it
+    uint64_t zeroed = 0, sorts = 0, most = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_census_desc &d = descs[i];
+        bool bad = d.bits != bits || d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_PREMULTIPLY_AS_U8 ||
+                   (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && bits != 16) || (d.layout == SPNG_TARGET_SCALAR && d.premultiply) ||
+                   d.cap < 1 || d.cap > 65536 || !d.d_keys || ((uintptr_t)d.d_keys & 3) || ((uintptr_t)d.d_counts & 7) ||
+                   (d.count && !d.d_pixels) || ((uintptr_t)d.d_pixels & (bits / 8 - 1)) || d.count > (~0ull >> 4) || d.reserved[0];
+        if (bad) return SPNG_E_ARGUMENT;
+        zeroed += 256 + 16ull * census_slots(d.cap);
+        sorts += 8ull * census_sort_elems(d.cap);
+        most = d.count > most ? d.count : most;
+    }
+    if (int32_t st = c->grow(c->d_census, c->census_cap, zeroed + sorts, 0)) return st;
+    if (int32_t st = c->reserve(count * (sizeof(CensusJob) + sizeof(spng_result)) + 1024)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(CensusJob)), rslot = a.take(count * sizeof(spng_result));
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    char *z = (char *)c->d_census, *srt = z + zeroed;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_census_desc &d = descs[i];
+        CensusJob j;
+        memset(&j, 0, sizeof j);
+        j.pixels = d.d_pixels; j.count = d.count; j.keys = (uint32_t *)d.d_keys; j.out_counts = (uint64_t *)d.d_counts;
+        j.cap = d.cap; j.slots = census_slots(d.cap);
+        for (j.slot_bits = 0; (1u << j.slot_bits) < j.slots; ++j.slot_bits) {}
+        j.ctrl = (uint32_t *)z; j.tags = (unsigned long long *)(z + 256); j.counts = j.tags + j.slots;
+        z += 256 + 16ull * j.slots;
+        j.sort = (unsigned long long *)srt; srt += 8ull * census_sort_elems(d.cap);
+        j.result = dr + i; j.layout = d.layout; j.premultiply = d.premultiply;
+        a.host<CensusJob>(jslot)[i] = j;
+    }
+    HIP_TRY(hipMemsetAsync(c->d_census, 0, zeroed, c->stream));
+    if (int32_t st = c->upload(0, a.off)) return st;
+    // about 4096 workgroups over the call (twice what is resident), at least 16 per array: a workgroup that counts many pixels
+    // merges its table into the image's seldom
+    uint64_t bx = 4096 / count < 16 ? 16 : 4096 / count;
+    const uint64_t full = (most + 1023) / 1024;                 // (four pixels per thread, 256 threads)
+    if (bx > full) bx = full;
+    { Timed t(c, SPNG_K_CENSUS); HIP_TRY(launch_census(a.dev<CensusJob>(jslot), count, (uint32_t)bx, bits, c->stream)); }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+int32_t spng_census(spng_ctx *c, const void *pixels, uint64_t n, int bits, int layout, int premultiply, uint32_t cap,
+                    uint32_t *keys, uint64_t *counts, spng_result *result)
+{
+    if (!c || (n && !pixels) || !keys || !result || (bits != 8 && bits != 16) || layout < 0 || layout > SPNG_TARGET_SCALAR ||
+        premultiply < 0 || premultiply > 255 || cap < 1 || cap > 65536 || n > (~0ull >> 4)) return SPNG_E_ARGUMENT;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t bytes = n * (layout == SPNG_TARGET_VA ? 2u : layout == SPNG_TARGET_SCALAR ? 1u : 4u) * (bits / 8);
+    DevBuf dpx, dk, dc;
+    HIP_TRY(dpx.alloc(bytes)); HIP_TRY(dk.alloc((size_t)cap * 4)); HIP_TRY(dc.alloc((size_t)cap * 8));
+    if (bytes) HIP_TRY(hipMemcpyAsync(dpx.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    spng_census_desc d{};
+    d.d_pixels = dpx.p; d.count = n; d.d_keys = dk.p; d.d_counts = counts ? dc.p : nullptr; d.cap = cap;
+    d.bits = (uint8_t)bits; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply;
+    if (int32_t st = spng_census_batch(c, &d, 1, nullptr, result)) return st;
+    if (result->status == SPNG_DONE && result->written) {
+        HIP_TRY(hipMemcpy(keys, dk.p, result->written * 4, hipMemcpyDeviceToHost));
+        if (counts) HIP_TRY(hipMemcpy(counts, dc.p, result->written * 8, hipMemcpyDeviceToHost));
+    }
+    return SPNG_DONE;
+}
+
+int32_t spng_pack_indexed_batch(spng_ctx *c, const spng_pack_indexed_desc *descs, uint32_t count, spng_result *d_results,
+                                spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    const int source = descs[0].source;
+    if (source != 8 && source != 16) return SPNG_E_ARGUMENT;
+    if (int32_t st = c->reserve(count * (sizeof(PackIndexedJob) + sizeof(spng_result)) + 1024)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(PackIndexedJob)), rslot = a.take(count * sizeof(spng_result));
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    uint64_t maxpix = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_pack_indexed_desc &d = descs[i];
+        const uint64_t px = (uint64_t)d.width * d.height;
+        bool bad = d.source != source || d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_PREMULTIPLY_AS_U8 ||
+                   (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && source != 16) || (d.layout == SPNG_TARGET_SCALAR && d.premultiply) ||
+                   d.map_count > 65536 || (d.map_count && (!d.d_keys || !d.d_indices)) || ((uintptr_t)d.d_keys & 3) ||
+                   (px && (!d.d_pixels || !d.d_storage)) || ((uintptr_t)d.d_pixels & (source / 8 - 1));
+        for (uint8_t r : d.reserved) bad = bad || r;
+        if (bad) return SPNG_E_ARGUMENT;
+        PackIndexedJob j;
+        memset(&j, 0, sizeof j);
+        j.pixels = d.d_pixels; j.storage = (uint8_t *)d.d_storage; j.keys = (const uint32_t *)d.d_keys; j.indices = (const uint8_t *)d.d_indices;
+        j.result = dr + i; j.width = d.width; j.height = d.height; j.map_count = d.map_count;
+        j.layout = d.layout; j.premultiply = d.premultiply; j.miss = d.miss;
+        a.host<PackIndexedJob>(jslot)[i] = j;
+        spng_result r{};
+        r.status = SPNG_DONE; r.written = px; r.consumed = px;
+        a.host<spng_result>(rslot)[i] = r;                      // (aux[0]: the kernel adds the pixels that missed)
+        maxpix = px > maxpix ? px : maxpix;
+    }
+    if (d_results)
+        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
+    if (int32_t st = c->upload(0, a.off)) return st;
+    uint64_t bx = (maxpix + 4095) / 4096;                      // (four pixels per thread, 256 threads, a few rounds)
+    if (bx > 4096) bx = 4096;
+    { Timed t(c, SPNG_K_PACK_INDEXED); HIP_TRY(launch_pack_indexed(a.dev<PackIndexedJob>(jslot), count, (uint32_t)bx, source, c->stream)); }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+int32_t spng_pack_indexed(spng_ctx *c, const void *pixels, uint32_t w, uint32_t h, int source, int layout, int premultiply,
+                          const uint32_t *keys, const uint8_t *indices, uint32_t map_count, int miss, void *storage, spng_result *result)
+{
+    const uint64_t px = (uint64_t)w * h;
+    if (!c || !result || (px && (!pixels || !storage)) || (source != 8 && source != 16) || layout < 0 || layout > SPNG_TARGET_SCALAR ||
+        premultiply < 0 || premultiply > 255 || miss < 0 || miss > 255 || map_count > 65536 || (map_count && (!keys || !indices)))
+        return SPNG_E_ARGUMENT;
+    for (uint32_t i = 1; i < map_count; ++i) if (keys[i] <= keys[i - 1]) return SPNG_E_ARGUMENT;   // ascending and distinct
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t bytes = px * (layout == SPNG_TARGET_VA ? 2u : layout == SPNG_TARGET_SCALAR ? 1u : 4u) * (source / 8);
+    DevBuf dpx, ds, dk, di;
+    HIP_TRY(dpx.alloc(bytes)); HIP_TRY(ds.alloc(px)); HIP_TRY(dk.alloc((size_t)map_count * 4)); HIP_TRY(di.alloc(map_count));
+    if (bytes) HIP_TRY(hipMemcpyAsync(dpx.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    if (map_count) {
+        HIP_TRY(hipMemcpyAsync(dk.p, keys, (size_t)map_count * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(di.p, indices, map_count, hipMemcpyHostToDevice, c->stream));
+    }
+    spng_pack_indexed_desc d{};
+    d.d_pixels = dpx.p; d.d_storage = ds.p; d.d_keys = map_count ? dk.p : nullptr; d.d_indices = map_count ? di.p : nullptr;
+    d.width = w; d.height = h; d.map_count = map_count;
+    d.source = (uint8_t)source; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply; d.miss = (uint8_t)miss;
+    if (int32_t st = spng_pack_indexed_batch(c, &d, 1, nullptr, result)) return st;
+    if (px) HIP_TRY(hipMemcpy(storage, ds.p, px, hipMemcpyDeviceToHost));
     return SPNG_DONE;
 }
 

@@ -128,6 +128,33 @@ struct AlphaJob {
     uint8_t        layout, op, pad[6];       // spng_alpha_desc.layout / .op
 };
 
+// One array of colour-target pixels whose distinct keys are counted (indexing.hip, census_kernel + census_finish_kernel)
+struct CensusJob {
+    const void    *pixels;
+    uint64_t       count;         // pixels
+    uint32_t      *keys;          // out: the distinct keys, ascending
+    uint64_t      *out_counts;    // out: their frequencies, or null
+    unsigned long long *tags;     // context scratch, zeroed in front of the call: the image's hash table (slots tags, slots counts),
+    unsigned long long *counts;
+    uint32_t      *ctrl;          // ... {distinct keys claimed, overflow flag},
+    unsigned long long *sort;     // ... and pow2(cap) elements for the sort (not zeroed)
+    spng_result   *result;        // written by census_finish_kernel
+    uint32_t       cap, slots, slot_bits;
+    uint8_t        layout, premultiply, pad[2];
+};
+
+// One image to pack through a map from keys to indices (indexing.hip, pack_indexed_kernel)
+struct PackIndexedJob {
+    const void    *pixels;
+    uint8_t       *storage;       // one byte per pixel
+    const uint32_t *keys;         // map_count keys, ascending and distinct
+    const uint8_t *indices;
+    spng_result   *result;        // filled in by the host; the kernel adds the pixels that missed to aux[0]
+    uint32_t       width, height;
+    uint32_t       map_count;
+    uint8_t        layout, premultiply, miss, pad;
+};
+
 struct InflateJob {
     const uint8_t *src;
     uint8_t       *dst;
@@ -368,6 +395,10 @@ hipError_t launch_deflate2_failed(const D2Stream *d_streams, uint32_t count, uin
 hipError_t launch_unpack(const UnpackJob *d_jobs, uint32_t count, uint32_t blocks_x, int target, hipStream_t stream);
 hipError_t launch_pack(const PackJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
 hipError_t launch_alpha(const AlphaJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
+uint32_t census_slots(uint32_t cap);                       // slots of an image's table
+uint32_t census_sort_elems(uint32_t cap);
+hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
+hipError_t launch_pack_indexed(const PackIndexedJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
 size_t lex_chunk_bytes();
 size_t lex_walk_bytes();
 hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed *d_out, void *d_table, const uint64_t *d_table_at,

@@ -1,0 +1,58 @@
+"""Code-generation guard for the kernels of csrc/indexing.hip (no GPU needed: hipcc cross-compiles gfx950): no scratch, no spills, and
+the workgroup size each is launched with.  Registers and LDS bytes are printed (pytest -s) for profiles/r10_indexing.md; no figure
+that nobody has measured on the device is asserted."""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+KEYS = ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+        "max_flat_workgroup_size")
+# kernel -> (instantiations, threads per workgroup at its launch in launch_census / launch_pack_indexed)
+LAUNCHED = {"census_kernel": (2, 256), "census_finish_kernel": (1, 1024), "pack_indexed_kernel": (2, 256)}
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
+        pytest.skip("hipcc not available")
+    with tempfile.TemporaryDirectory() as tmp:
+        src = os.path.join(ROOT, "swift_png_amd", "csrc", "indexing.hip")
+        out = os.path.join(tmp, "indexing.s")
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
+                       check=True, capture_output=True, timeout=900)
+        asm = open(out).read()
+    table = {}
+    for blk in re.split(r"\n  - ", asm[asm.index("amdhsa.kernels:"):])[1:]:
+        def get(key, blk=blk):
+            m = re.search(r"\." + key + r":\s+(\S+)", blk)
+            return m.group(1) if m else "0"
+        if "_kernel" in get("name"):
+            table[get("name")] = {k: int(get(k)) for k in KEYS}
+    return table
+
+
+def test_every_kernel_is_known_and_free_of_scratch(kernels):
+    seen = {name: 0 for name in LAUNCHED}
+    for mangled, v in kernels.items():
+        name = next((n for n in sorted(LAUNCHED, key=len, reverse=True) if n in mangled), None)
+        assert name is not None, f"{mangled}: a kernel this test does not know"
+        seen[name] += 1
+        print(f"{mangled}: {v['vgpr_count']} VGPRs, {v['sgpr_count']} SGPRs, {v['group_segment_fixed_size']} bytes of LDS")
+        assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0, mangled
+        assert v["max_flat_workgroup_size"] == LAUNCHED[name][1], mangled
+    assert seen == {name: n for name, (n, _) in LAUNCHED.items()}
+
+
+def test_launches_use_the_declared_workgroup_sizes():
+    src = open(os.path.join(ROOT, "swift_png_amd", "csrc", "indexing.hip")).read()
+    launches = re.findall(r"\b(\w+_kernel)(?:<\w+>)?<<<\s*\w+,\s*(\d+),", src)
+    assert len(launches) == 5
+    for name, threads in launches:
+        assert int(threads) == LAUNCHED[name][1], name
+        assert re.search(r"__launch_bounds__\(%d\) void %s\(" % (LAUNCHED[name][1], name), src), name

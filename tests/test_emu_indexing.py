@@ -1,0 +1,41 @@
+"""census_kernel, census_finish_kernel and pack_indexed_kernel of csrc/indexing.hip (the distinct UInt8 aggregates of a pixel array
+and the pack through a key -> index map: the indexer closures of PNG.RGBA.swift:409-423, PNG.VA.swift:334-350 and
+PNG.Image.swift:767-782 as tables) run on the CPU by the wave emulator of tools/emu (host compiler: the ROCm clang++) against
+std::map in tools/emu/emu_indexing.cpp."""
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
+
+CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
+        pytest.skip("clang++ not available")
+    import prep_deflate
+    d = tmp_path_factory.mktemp("emu_indexing")
+    inc = d / "indexing_emu.inc"
+    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "indexing.hip")).read()))
+    out = d / "emu_indexing"
+    subprocess.run([CLANG, "-O2", "-std=c++17", "-DSPNG_EMU", f'-DEMU_INDEXING_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
+                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
+                    os.path.join(ROOT, "tools", "emu", "emu_indexing.cpp")], check=True, capture_output=True, timeout=600)
+    return out
+
+
+@pytest.mark.parametrize("mode", ["census", "pack"])
+def test_emulated_indexing_kernels_match_a_map(emu, mode):
+    """census: T = UInt8 / UInt16, three layouts; 0 ... 2051 pixels on one and three workgroups; a flat array; exactly cap and
+    cap + 1 keys; the keys 0 and 0xFFFFFFFF; {k << s}; more distinct keys in one workgroup than its LDS table may hold, twice
+    (the merge), on both sides of the sort's LDS limit; overflow seen early and late; both premultiplications; no counts; nothing
+    written behind the result.  pack: the same sizes at storage offsets 0 ... 3, maps of 0 ... 65536 keys around the LDS
+    threshold, misses counted, the keys 0 and 0xFFFFFFFF present and absent, the identity indexer, both premultiplications."""
+    r = subprocess.run([str(emu), mode], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (mode, r.stdout[-600:], r.stderr[-600:])

@@ -337,6 +337,13 @@ inline unsigned atomicOr(unsigned *p, unsigned v) { unsigned o = *p; *p = o | v;
 inline void __threadfence() {}
 inline unsigned atomicAdd(unsigned *p, unsigned v) { unsigned o = *p; *p = o + v; return o; }
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { unsigned long long o = *p; *p = o + v; return o; }
+inline unsigned atomicCAS(unsigned *p, unsigned expected, unsigned v) { unsigned o = *p; if (o == expected) *p = v; return o; }
+inline unsigned long long atomicCAS(unsigned long long *p, unsigned long long expected, unsigned long long v)
+{
+    unsigned long long o = *p;
+    if (o == expected) *p = v;
+    return o;
+}
 inline unsigned atomicMax(unsigned *p, unsigned v) { unsigned o = *p; if (v > o) *p = v; return o; }
 inline unsigned atomicMin(unsigned *p, unsigned v) { unsigned o = *p; if (v < o) *p = v; return o; }
 #ifndef __clang__

@@ -172,7 +172,8 @@ enum { SPNG_K_INFLATE = 0,          /* the serial inflate kernel (streams the pa
        SPNG_K_ALPHA = 15,           /* spng_alpha_batch */
        SPNG_K_CENSUS = 16,          /* spng_census_batch: the counting kernel and the sort behind it */
        SPNG_K_PACK_INDEXED = 17,    /* spng_pack_indexed_batch */
-       SPNG_K_COUNT = 18 };
+       SPNG_K_HSVA = 18,            /* spng_hsva_batch */
+       SPNG_K_COUNT = 19 };
 int32_t spng_profile(spng_ctx *ctx, int enable);                /* enable/disable + reset counters  */
 int32_t spng_profile_get(spng_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 /* Token volume of the most recent parallel-inflate call whose figures have come back (they travel behind its kernels; this call
@@ -394,6 +395,47 @@ int32_t spng_alpha_batch(spng_ctx *ctx, const spng_alpha_desc *descs, uint32_t c
                          spng_result *d_results, spng_result *h_results);
 /* host-pointer convenience (copies in / out, synchronous): n pixels */
 int32_t spng_alpha(spng_ctx *ctx, const void *pixels, uint64_t n, int bits, int layout, int op, void *out, spng_result *result);
+
+/* ---- pixels: a custom colour target (the HSVA tutorial) --------------------------------------------- */
+/* The reference's third colour-target tutorial (Snippets/PNG/CustomColor.swift) defines its own target,
+ *     struct HSVA { var h:UInt32, s:UInt16, v:UInt8, a:UInt8 }           -- in memory {uint32 h; uint16 s; uint8 v; uint8 a}:
+ * 8 bytes, aligned to 4, host byte order --, unpacks an image into it, edits the fields and packs the result.  Its three
+ * conversions, mapped over an array, bit for bit (all arithmetic in UInt32; (min, mid, max) the sorted r, g, b; d = max - min):
+ *   SPNG_HSVA_FROM_RGBA8   HSVA.init(r:g:b:a:), CustomColor.swift:19-49.  sector from (r < g, g < b, r < b) as the switch orders
+ *                          them ((false, false, _) is sector 0).  d > 0: f = ((mid - min) << 16) / d + 1, h = 65537 sector +
+ *                          (sector even ? f : 65537 - f), s = ((d << 16) - 1) / max; d == 0: h = s = 0.  v = max, a as it is.
+ *   SPNG_HSVA_TO_RGBA8     HSVA.rgba, CustomColor.swift:51-78.  s == 0 or v == 0: (v, v, v, a).  Otherwise (sector, r') = h divmod
+ *                          65537, f = sector even ? r' : 65537 - r', d = ((s v) >> 16) + 1, x = v, y = x - d, z = ((f d) >> 16) + y,
+ *                          and (r, g, b) = (x, z, y), (z, x, y), (y, x, z), (y, z, x), (z, y, x), (x, y, z) for sector 0 ... 5.
+ *   SPNG_HSVA_TO_VA8       (v, a): what HSVA.pack stores for the grey formats (kernel: \.v, CustomColor.swift:232-251) -- not .rgba.r.
+ * TO_RGBA8(FROM_RGBA8(c)) == c for every colour.  Where the reference traps -- only fatalError("unreachable"): sector >= 6 with
+ * s > 0 and v > 0 -- the pixel becomes (v, v, v, a) and is counted in spng_result.aux[0], as spng_alpha_batch counts its own.
+ *
+ * Two steps make HSVA.unpack (CustomColor.swift:86-210): for every PNG.Format it equals FROM_RGBA8 applied to
+ * RGBA<UInt8>.unpack (spng_unpack_batch, target 8, SPNG_TARGET_RGBA; Sources/PNG/ColorTargets/PNG.RGBA.swift:259-365) -- the colour
+ * formats hand init(r:g:b:a:) the very components RGBA<UInt8> holds; the grey formats store (h: 0, s: 0, v, a), which is what
+ * (v, v, v, a) converts to (no comparison holds: sector 0, d = 0); chroma keys and palettes (deindexers included) are resolved by
+ * the existing unpack.  HSVA.pack (CustomColor.swift:213-299) by the format packed into:
+ *   grey (v1 ... v16, va8, va16)      TO_VA8,   then spng_pack_batch with source 8, SPNG_TARGET_VA
+ *   colour (rgb*, bgr8, rgba*, bgra8) TO_RGBA8, then spng_pack_batch with source 8, SPNG_TARGET_RGBA
+ *   indexed                           TO_RGBA8, then the indexed path of spng_pack_batch, or spng_census_batch +
+ *                                     spng_pack_indexed_batch for a custom indexer
+ * The price of not fusing the conversion into the unpack and pack kernels is one more pass over 4 bytes per pixel. */
+enum { SPNG_HSVA_FROM_RGBA8 = 1, SPNG_HSVA_TO_RGBA8 = 2, SPNG_HSVA_TO_VA8 = 3 };
+typedef struct spng_hsva_desc {
+    const void *d_in;  void *d_out;             /* device pointers to `count` pixels each.  The HSVA side is aligned to 4; the
+                                                   RGBA8 / VA8 side may have any alignment (16 on both sides is the fast path) */
+    uint64_t    count;
+    uint8_t     op;                             /* SPNG_HSVA_FROM_RGBA8 ... SPNG_HSVA_TO_VA8; every desc has its own */
+    uint8_t     reserved[7];                    /* zero */
+} spng_hsva_desc;
+/* Results: status SPNG_DONE, written = bytes written, consumed = bytes read, aux[0] = pixels the reference would have trapped on.
+ * A count of 0, of a desc or of the call, is valid and writes nothing.  SPNG_E_ARGUMENT: a non-zero reserved byte, an unknown op,
+ * d_out == d_in (the element sizes differ, so nothing runs in place) or any other overlap, an HSVA pointer not aligned to 4. */
+int32_t spng_hsva_batch(spng_ctx *ctx, const spng_hsva_desc *descs, uint32_t count,
+                        spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous): n pixels */
+int32_t spng_hsva(spng_ctx *ctx, const void *pixels, uint64_t n, int op, void *out, spng_result *result);
 
 /* ---- pixels: indexed colour with any pure indexer ---------------------------------------------------- */
 /* The reference takes an indexer closure wherever pixels are packed into an indexed format:

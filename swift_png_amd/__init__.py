@@ -43,6 +43,9 @@ K_PINF_FIND, K_PINF_DECODE, K_PINF_RESOLVE = 8, 9, 11
 K_DFL_SEARCH, K_DFL_PARSE = 13, 14
 K_ALPHA = 15
 K_CENSUS, K_PACK_INDEXED = 16, 17
+K_HSVA = 18
+HSVA_FROM_RGBA8, HSVA_TO_RGBA8, HSVA_TO_VA8 = 1, 2, 3
+_HSVA_BYTES = {1: (4, 8), 2: (8, 4), 3: (8, 2)}             # op: bytes of a pixel in, out
 # thresholds of csrc/indexing.hip (the tests take the sizes at which the kernels change paths from here)
 CENSUS_LDS_SLOTS, CENSUS_LDS_LIMIT = 2048, 512     # a workgroup's table; keys in it above which it is merged into the image's
 CENSUS_FINISH_LDS_KEYS = 4096                      # up to so many keys are sorted in LDS, more in the context's scratch
@@ -59,7 +62,7 @@ EXPORTS = [
     "spng_profile_get", "spng_token_stats", "spng_cut_stats", "spng_configure", "spng_inflate_batch", "spng_inflate_resume_batch", "spng_unfilter_batch",
     "spng_unfilter_resume_batch", "spng_decode_batch",
     "spng_inflate", "spng_unfilter", "spng_decode", "spng_adler32", "spng_filter_batch", "spng_filter",
-    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
+    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
 ]
 
@@ -124,6 +127,11 @@ class PackDesc(ctypes.Structure):
 class AlphaDesc(ctypes.Structure):
     _fields_ = [("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_uint64), ("bits", ctypes.c_uint8),
                 ("layout", ctypes.c_uint8), ("op", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 5)]
+
+
+class HsvaDesc(ctypes.Structure):
+    _fields_ = [("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_uint64), ("op", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 7)]
 
 
 class CensusDesc(ctypes.Structure):
@@ -269,6 +277,8 @@ def load_library():
                                  ctypes.c_int, vp, u32, vp]
     lib.spng_alpha_batch.argtypes = [vp, vp, u32, vp, rp]
     lib.spng_alpha.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, rp]
+    lib.spng_hsva_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_hsva.argtypes = [vp, vp, u64, ctypes.c_int, vp, rp]
     lib.spng_census_batch.argtypes = [vp, vp, u32, vp, rp]
     lib.spng_census.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32, vp, vp, rp]
     lib.spng_pack_indexed_batch.argtypes = [vp, vp, u32, vp, rp]
@@ -797,6 +807,48 @@ class Session:
         res = Result()
         _check(self.lib, self.lib.spng_alpha(self.ctx, src, len(pixels) // per, bits, int(layout), int(op), out, ctypes.byref(res)))
         return bytes(out[:len(pixels)]), int(res.aux[0])
+
+    def hsva_batch(self, arrays, ops, outs=None):
+        """spng_hsva_batch on device tensors: every tensor of `arrays` holds whole pixels -- RGBA<UInt8> for HSVA_FROM_RGBA8, HSVA
+        ({uint32 h; uint16 s; uint8 v; uint8 a}, 8 bytes, aligned to 4) for HSVA_TO_RGBA8 and HSVA_TO_VA8 -- and is converted into
+        the tensor of `outs` at its place (never in place: the element sizes differ), or into a new uint8 tensor where outs is
+        None.  ops: one value, or one per array.  -> (list of output tensors, list[Result] with aux[0] = pixels the reference would
+        have trapped on, written as (v, v, v, a))"""
+        n = len(arrays)
+        descs = (HsvaDesc * max(n, 1))()
+        given, outs = outs, []
+        for i, t in enumerate(arrays):
+            op = ops[i] if isinstance(ops, (list, tuple)) else ops
+            if op not in _HSVA_BYTES:
+                raise ValueError("op must be HSVA_FROM_RGBA8, HSVA_TO_RGBA8 or HSVA_TO_VA8")
+            per_in, per_out = _HSVA_BYTES[op]
+            nbytes = t.numel() * t.element_size()
+            if nbytes % per_in:
+                raise ValueError("an array of whole pixels is needed")
+            count = nbytes // per_in
+            o = given[i] if given is not None else self.torch.empty(count * per_out, dtype=self.torch.uint8, device=self.tdev)
+            if o.numel() * o.element_size() < count * per_out:
+                raise ValueError("an output of at least the converted size is needed")
+            outs.append(o)
+            descs[i] = HsvaDesc(self._ptr(t), self._ptr(o), count, op)
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_hsva_batch(self.ctx, descs, n, None, res))
+        return outs, list(res)[:n]
+
+    def hsva(self, pixels: bytes, op):
+        """[PNG.RGBA<UInt8>].map(HSVA.init(r:g:b:a:)) (HSVA_FROM_RGBA8), [HSVA].map(\\.rgba) (HSVA_TO_RGBA8) or the (v, a) pairs of
+        [HSVA] (HSVA_TO_VA8) as bytes (host order): -> (bytes, trapped pixels)"""
+        if op not in _HSVA_BYTES:
+            raise ValueError("op must be HSVA_FROM_RGBA8, HSVA_TO_RGBA8 or HSVA_TO_VA8")
+        per_in, per_out = _HSVA_BYTES[op]
+        if len(pixels) % per_in:
+            raise ValueError("whole pixels are needed")
+        n = len(pixels) // per_in
+        src = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
+        out = (ctypes.c_uint8 * max(n * per_out, 1))()
+        res = Result()
+        _check(self.lib, self.lib.spng_hsva(self.ctx, src, n, int(op), out, ctypes.byref(res)))
+        return bytes(out[:n * per_out]), int(res.aux[0])
 
     def deflate(self, data: bytes, level: int, fmt=FORMAT_ZLIB, exponent: int = 15) -> bytes:
         """Whole-stream LZ77.Deflator (push(all, last: true) + concatenated pull()): -> stream bytes"""

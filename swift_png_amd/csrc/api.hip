@@ -1734,6 +1734,62 @@ int32_t spng_alpha(spng_ctx *c, const void *pixels, uint64_t n, int bits, int la
     return SPNG_DONE;
 }
 
+int32_t spng_hsva_batch(spng_ctx *c, const spng_hsva_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    if (int32_t st = c->reserve(count * (sizeof(HsvaJob) + sizeof(spng_result)) + 1024)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(HsvaJob)), rslot = a.take(count * sizeof(spng_result));
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    uint64_t most = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_hsva_desc &d = descs[i];
+        if (d.op < SPNG_HSVA_FROM_RGBA8 || d.op > SPNG_HSVA_TO_VA8 || d.count > (~0ull >> 4)) return SPNG_E_ARGUMENT;
+        const uint64_t ibytes = d.count * (d.op == SPNG_HSVA_FROM_RGBA8 ? 4u : 8u),
+                       obytes = d.count * (d.op == SPNG_HSVA_FROM_RGBA8 ? 8u : d.op == SPNG_HSVA_TO_RGBA8 ? 4u : 2u);
+        const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out, hsva = d.op == SPNG_HSVA_FROM_RGBA8 ? out : in;
+        // the element sizes differ: nothing runs in place, and no other overlap is allowed either
+        bool bad = (hsva & 3) || (d.count && (!in || !out)) || (in && in == out) || (in < out + obytes && out < in + ibytes);
+        for (uint8_t r : d.reserved) bad = bad || r;
+        if (bad) return SPNG_E_ARGUMENT;
+        HsvaJob j;
+        memset(&j, 0, sizeof j);
+        j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.result = dr + i; j.op = d.op;
+        a.host<HsvaJob>(jslot)[i] = j;
+        spng_result r{};
+        r.status = SPNG_DONE; r.written = obytes; r.consumed = ibytes;
+        a.host<spng_result>(rslot)[i] = r;                      // (aux[0]: the kernel adds the trapped pixels)
+        most = d.count > most ? d.count : most;
+    }
+    if (d_results)
+        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
+    if (int32_t st = c->upload(0, a.off)) return st;
+    uint64_t bx = (most + 4095) / 4096;                         // (four pixels per thread, 256 threads, a few rounds)
+    if (bx > 4096) bx = 4096;
+    { Timed t(c, SPNG_K_HSVA); HIP_TRY(launch_hsva(a.dev<HsvaJob>(jslot), count, (uint32_t)bx, c->stream)); }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+int32_t spng_hsva(spng_ctx *c, const void *pixels, uint64_t n, int op, void *out, spng_result *result)
+{
+    if (!c || (n && (!pixels || !out)) || !result || op < SPNG_HSVA_FROM_RGBA8 || op > SPNG_HSVA_TO_VA8 || n > (~0ull >> 4))
+        return SPNG_E_ARGUMENT;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t ibytes = n * (op == SPNG_HSVA_FROM_RGBA8 ? 4u : 8u),
+                   obytes = n * (op == SPNG_HSVA_FROM_RGBA8 ? 8u : op == SPNG_HSVA_TO_RGBA8 ? 4u : 2u);
+    DevBuf din, dout;
+    HIP_TRY(din.alloc(ibytes)); HIP_TRY(dout.alloc(obytes));
+    if (ibytes) HIP_TRY(hipMemcpyAsync(din.p, pixels, ibytes, hipMemcpyHostToDevice, c->stream));
+    spng_hsva_desc d{};
+    d.d_in = din.p; d.d_out = dout.p; d.count = n; d.op = (uint8_t)op;
+    if (int32_t st = spng_hsva_batch(c, &d, 1, nullptr, result)) return st;
+    if (obytes) HIP_TRY(hipMemcpy(out, dout.p, obytes, hipMemcpyDeviceToHost));
+    return SPNG_DONE;
+}
+
 int32_t spng_census_batch(spng_ctx *c, const spng_census_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
 {
     if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;

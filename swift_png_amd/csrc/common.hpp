@@ -128,6 +128,15 @@ struct AlphaJob {
     uint8_t        layout, op, pad[6];       // spng_alpha_desc.layout / .op
 };
 
+// One array of pixels converted to or from the tutorial's HSVA colour target (hsva.hip, hsva_kernel)
+struct HsvaJob {
+    const void    *in;
+    void          *out;
+    uint64_t       count;         // pixels
+    spng_result   *result;        // filled in by the host; the kernel adds the trapped pixels to aux[0]
+    uint8_t        op, pad[7];    // spng_hsva_desc.op
+};
+
 // One array of colour-target pixels whose distinct keys are counted (indexing.hip, census_kernel + census_finish_kernel)
 struct CensusJob {
     const void    *pixels;
@@ -395,6 +404,7 @@ hipError_t launch_deflate2_failed(const D2Stream *d_streams, uint32_t count, uin
 hipError_t launch_unpack(const UnpackJob *d_jobs, uint32_t count, uint32_t blocks_x, int target, hipStream_t stream);
 hipError_t launch_pack(const PackJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
 hipError_t launch_alpha(const AlphaJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
+hipError_t launch_hsva(const HsvaJob *d_jobs, uint32_t count, uint32_t blocks_x, hipStream_t stream);
 uint32_t census_slots(uint32_t cap);                       // slots of an image's table
 uint32_t census_sort_elems(uint32_t cap);
 hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);

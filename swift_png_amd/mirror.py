@@ -10,7 +10,8 @@ from __future__ import annotations
 
 from . import (DONE, FORMAT_GZIP, FORMAT_IOS, FORMAT_ZLIB, NEED_MORE_INPUT, DecodingError, SpngError,
                E_EXTRANEOUS_COMPRESSED_DATA, E_INCOMPLETE_DATASTREAM, E_OUTPUT_CAPACITY, IMAGE_OVERDRAW,
-               PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8, TARGET_RGBA, TARGET_VA)
+               HSVA_FROM_RGBA8, HSVA_TO_RGBA8, HSVA_TO_VA8, PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8, TARGET_RGBA,
+               TARGET_VA)
 
 _DELAY_FORMATS = {1: (8, 1), 2: (8, 2), 3: (8, 3), 4: (8, 4), 6: (16, 3), 8: (16, 4)}
 
@@ -245,7 +246,79 @@ class _ColorTarget:
         return out
 
 
+def _hsva(pixels, op, session):
+    """an array of pixels (bytes in host order, or a numpy array: (n, 4) uint8 going in, records of PNG.HSVA.dtype() coming out)
+    through spng_hsva: -> (the converted array, bytes for bytes, pixels the reference would have trapped on)"""
+    from . import load
+    s = session or load()
+    if isinstance(pixels, (bytes, bytearray, memoryview)):
+        return s.hsva(bytes(pixels), op)
+    import numpy as np
+    a = np.ascontiguousarray(pixels)
+    if a.dtype != (np.dtype(np.uint8) if op == HSVA_FROM_RGBA8 else PNG.HSVA.dtype()):
+        raise ValueError("uint8 components going in, records of PNG.HSVA.dtype() coming out")
+    out, trapped = s.hsva(a.tobytes(), op)
+    if op == HSVA_FROM_RGBA8:
+        return np.frombuffer(out, dtype=PNG.HSVA.dtype()).copy(), trapped
+    return np.frombuffer(out, dtype=np.uint8).reshape(-1, 4 if op == HSVA_TO_RGBA8 else 2).copy(), trapped
+
+
 class PNG:
+    class HSVA:
+        """The custom colour target of the reference's tutorial (Snippets/PNG/CustomColor.swift: struct HSVA { h: UInt32, s: UInt16,
+        v: UInt8, a: UInt8 }, PNG.Color conformance :82-301) on the device: arrays of 8-byte records, host byte order."""
+
+        @staticmethod
+        def dtype():
+            import numpy as np
+            return np.dtype([("h", "<u4"), ("s", "<u2"), ("v", "u1"), ("a", "u1")])
+
+        @staticmethod
+        def from_rgba(pixels, session=None):
+            """[PNG.RGBA<UInt8>].map{ HSVA.init(r: $0.r, g: $0.g, b: $0.b, a: $0.a) } (CustomColor.swift:19-49)"""
+            return _hsva(pixels, HSVA_FROM_RGBA8, session)[0]
+
+        @staticmethod
+        def rgba(pixels, session=None):
+            """[HSVA].map(\\.rgba) (CustomColor.swift:51-78).  Where the reference traps -- fatalError("unreachable"): h of 6 * 65537
+            or more in a pixel with s > 0 and v > 0 -- this raises ValueError."""
+            out, trapped = _hsva(pixels, HSVA_TO_RGBA8, session)
+            if trapped:
+                raise ValueError(f"{trapped} pixels have a hue of 6 * 65537 or more: unreachable (the reference traps)")
+            return out
+
+        @staticmethod
+        def va(pixels, session=None):
+            """the (v, a) of every pixel: what HSVA.pack stores for the grey formats (CustomColor.swift:232-251)"""
+            return _hsva(pixels, HSVA_TO_VA8, session)[0]
+
+        @staticmethod
+        def unpack(storage: bytes, w, h, depth, channels, indexed=False, bgr=False, palette=None, key=None, deindexer=None,
+                   session=None) -> bytes:
+            """PNG.Image.unpack(as: HSVA.self) (HSVA.unpack, CustomColor.swift:86-210): Session.unpack's arguments without the
+            target's own (target, layout, premultiply).  Two steps on the device: RGBA<UInt8>.unpack, then HSVA.init(r:g:b:a:) -- for
+            every format what the tutorial's switch computes (include/spng_mi355.h).  -> bytes of HSVA records"""
+            from . import load
+            s = session or load()
+            rgba = s.unpack(storage, w, h, depth, channels, indexed=indexed, bgr=bgr, target=8, palette=palette, key=key,
+                            layout=TARGET_RGBA, deindexer=deindexer)
+            return s.hsva(rgba, HSVA_FROM_RGBA8)[0]
+
+        @staticmethod
+        def pack(pixels: bytes, w, h, depth, channels, indexed=False, bgr=False, palette=None, indexer=None, session=None) -> bytes:
+            """PNG.Image(packing: [HSVA], size:layout:).storage (HSVA.pack, CustomColor.swift:213-299): Session.pack's arguments
+            without the source's own (source, layout, premultiply).  Grey formats store (v, a) (kernel: \\.v): HSVA_TO_VA8, then the
+            VA<UInt8> pack; colour and indexed formats store .rgba: HSVA_TO_RGBA8, then the RGBA<UInt8> pack with the default or
+            the given indexer.  ValueError where .rgba traps."""
+            from . import load
+            s = session or load()
+            if len(pixels) != 8 * w * h:
+                raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
+            if not indexed and channels <= 2:
+                return s.pack(s.hsva(bytes(pixels), HSVA_TO_VA8)[0], w, h, depth, channels, source=8, layout=TARGET_VA)
+            return s.pack(PNG.HSVA.rgba(bytes(pixels), session=s), w, h, depth, channels, indexed=indexed, bgr=bgr, source=8,
+                          palette=palette, layout=TARGET_RGBA, indexer=indexer)
+
     class Standard:
         common = FORMAT_ZLIB
         ios = FORMAT_IOS

@@ -350,6 +350,23 @@ def _check(lib, st):
         raise SpngError(st) if st != E_DEVICE else RuntimeError(f"libspng_mi355: {msg}")
 
 
+def _cbuf(data):
+    """`data` (None: nothing) as a ctypes byte array for a host-pointer entry: one zero byte where it is empty, for ctypes cannot point at
+    an array of length 0"""
+    data = b"" if data is None else bytes(data)
+    return (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+
+
+def pick(v, i):
+    """an argument of a batch call that holds one value, or one per array: the value for array i"""
+    return v[i] if isinstance(v, (list, tuple)) else v
+
+
+def pixel_bytes(layout, bits) -> int:
+    """bytes of one RGBA<T> / VA<T> / T pixel, T of `bits` bits"""
+    return (4, 2, 1)[layout] * (bits // 8)
+
+
 # ---- indexers and deindexers as tables -------------------------------------------------------------
 def palette_entries(palette):
     """bytes of (r, g, b, a) quadruplets -> the list of tuples an indexer / deindexer of the reference is created with"""
@@ -486,8 +503,7 @@ class Session:
         outs = [self.empty(c) for c in caps]
         descs = (StreamDesc * n)()
         for i, (s, o, c) in enumerate(zip(streams, outs, caps)):
-            f = fmt[i] if isinstance(fmt, (list, tuple)) else fmt
-            descs[i] = StreamDesc(self._ptr(s), s.numel(), self._ptr(o), int(c), f, 0)
+            descs[i] = StreamDesc(self._ptr(s), s.numel(), self._ptr(o), int(c), pick(fmt, i), 0)
         res = (Result * n)()
         _check(self.lib, self.lib.spng_inflate_batch(self.ctx, descs, n, None, res))
         return outs, list(res)
@@ -565,10 +581,9 @@ class Session:
     def inflate(self, data: bytes, fmt=FORMAT_ZLIB, cap=None):
         """Whole-stream LZ77.Inflator: -> (status, bytes, consumed, aux)"""
         cap = int(cap if cap is not None else max(1 << 16, 1100 * len(data)))
-        src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
         dst = (ctypes.c_uint8 * max(cap, 1))()
         res = Result()
-        _check(self.lib, self.lib.spng_inflate(self.ctx, src, len(data), fmt, dst, cap, ctypes.byref(res)))
+        _check(self.lib, self.lib.spng_inflate(self.ctx, _cbuf(data), len(data), fmt, dst, cap, ctypes.byref(res)))
         return res.status, bytes(dst[:res.written]), res.consumed, (res.aux[0], res.aux[1])
 
     def decode(self, idat: bytes, w, h, depth, channels, interlaced, fmt=FORMAT_ZLIB, storage=None):
@@ -577,9 +592,8 @@ class Session:
         buf = (ctypes.c_uint8 * max(s, 1))()
         if storage is not None:
             ctypes.memmove(buf, bytes(storage), s)
-        src = (ctypes.c_uint8 * max(len(idat), 1)).from_buffer_copy(bytes(idat) or b"\0")
         res = Result()
-        _check(self.lib, self.lib.spng_decode(self.ctx, src, len(idat), fmt, w, h, depth, channels,
+        _check(self.lib, self.lib.spng_decode(self.ctx, _cbuf(idat), len(idat), fmt, w, h, depth, channels,
                                               int(bool(interlaced)), buf, ctypes.byref(res)))
         return res.status, bytes(buf[:s]), (res.aux[0], res.aux[1])
 
@@ -588,18 +602,16 @@ class Session:
         buf = (ctypes.c_uint8 * max(s, 1))()
         if storage is not None:
             ctypes.memmove(buf, bytes(storage), s)
-        src = (ctypes.c_uint8 * max(len(rows), 1)).from_buffer_copy(bytes(rows) or b"\0")
         res = Result()
-        _check(self.lib, self.lib.spng_unfilter(self.ctx, src, len(rows), w, h, depth, channels,
+        _check(self.lib, self.lib.spng_unfilter(self.ctx, _cbuf(rows), len(rows), w, h, depth, channels,
                                                 int(bool(interlaced)), buf, ctypes.byref(res)))
         return res.status, bytes(buf[:s])
 
     def filter(self, storage: bytes, w, h, depth, channels, interlaced) -> bytes:
         u = inflated_size(w, h, depth, channels, interlaced)
-        src = (ctypes.c_uint8 * max(len(storage), 1)).from_buffer_copy(bytes(storage) or b"\0")
         dst = (ctypes.c_uint8 * max(u, 1))()
         res = Result()
-        _check(self.lib, self.lib.spng_filter(self.ctx, src, w, h, depth, channels, int(bool(interlaced)), dst,
+        _check(self.lib, self.lib.spng_filter(self.ctx, _cbuf(storage), w, h, depth, channels, int(bool(interlaced)), dst,
                                               ctypes.byref(res)))
         return bytes(dst[:u])
 
@@ -628,9 +640,8 @@ class Session:
         return bytes(dst[:res[0].written].cpu().numpy())
 
     def crc32(self, data: bytes) -> int:
-        src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
         out = ctypes.c_uint32(0)
-        _check(self.lib, self.lib.spng_crc32(self.ctx, src, len(data), ctypes.byref(out)))
+        _check(self.lib, self.lib.spng_crc32(self.ctx, _cbuf(data), len(data), ctypes.byref(out)))
         return out.value
 
     def unpack(self, storage: bytes, w, h, depth, channels, indexed=False, bgr=False, target=16, palette=None, key=None,
@@ -644,13 +655,11 @@ class Session:
             if not indexed:
                 raise ValueError("a deindexer needs an indexed format")
             palette = tabulate_deindexer(deindexer(palette_entries(palette)), layout)
-        n = w * h * (4, 2, 1)[layout] * (target // 8)
-        src = (ctypes.c_uint8 * max(len(storage), 1)).from_buffer_copy(bytes(storage) or b"\0")
+        n = w * h * pixel_bytes(layout, target)
         out = (ctypes.c_uint8 * max(n, 1))()
-        pal = (ctypes.c_uint8 * max(len(palette or b""), 1)).from_buffer_copy(bytes(palette or b"\0"))
         k = (ctypes.c_uint16 * 3)(*(list(key) + [0, 0, 0])[:3]) if key is not None else None
-        _check(self.lib, self.lib.spng_unpack_as(self.ctx, src, w, h, depth, channels, int(bool(indexed)), int(bool(bgr)), target,
-                                                 int(layout), int(premultiply), pal if palette else None, len(palette or b"") // 4, k, out))
+        _check(self.lib, self.lib.spng_unpack_as(self.ctx, _cbuf(storage), w, h, depth, channels, int(bool(indexed)), int(bool(bgr)), target,
+                                                 int(layout), int(premultiply), _cbuf(palette) if palette else None, len(palette or b"") // 4, k, out))
         return bytes(out[:n])
 
     def pack(self, pixels: bytes, w, h, depth, channels, indexed=False, bgr=False, source=16, palette=None, layout=0,
@@ -666,7 +675,7 @@ class Session:
         if indexer is not None:
             if not indexed or depth != 8:
                 raise ValueError("an indexer needs the indexed8 format")
-            if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
+            if len(pixels) != w * h * pixel_bytes(layout, source):
                 raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
             index = indexer(palette_entries(palette))
             if layout == TARGET_RGBA:
@@ -677,8 +686,7 @@ class Session:
             storage, _ = self.pack_indexed(pixels, w, h, source, layout, keys, tabulate_indexer(index, keys, layout),
                                            premultiply=premultiply)
             return storage
-        px = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
-        if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
+        if len(pixels) != w * h * pixel_bytes(layout, source):
             raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
         n = self.lib.spng_storage_size(w, h, depth, channels)
         if premultiply:
@@ -691,9 +699,8 @@ class Session:
             self.sync()
             return bytes(d_sto[:n].cpu().numpy())
         out = (ctypes.c_uint8 * max(n, 1))()
-        pal = (ctypes.c_uint8 * max(len(palette or b""), 1)).from_buffer_copy(bytes(palette or b"\0"))
-        _check(self.lib, self.lib.spng_pack_as(self.ctx, px, w, h, depth, channels, int(bool(indexed)), int(bool(bgr)), source,
-                                               int(layout), pal if palette else None, len(palette or b"") // 4, out))
+        _check(self.lib, self.lib.spng_pack_as(self.ctx, _cbuf(pixels), w, h, depth, channels, int(bool(indexed)), int(bool(bgr)), source,
+                                               int(layout), _cbuf(palette) if palette else None, len(palette or b"") // 4, out))
         return bytes(out[:n])
 
     def census_batch(self, arrays, bits, layout, cap=256, premultiply=0, counts=True, outs=None):
@@ -704,12 +711,11 @@ class Session:
         that torch kernels are still writing have to be waited for first."""
         n = len(arrays)
         t = self.torch
-        pick = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
         descs = (CensusDesc * max(n, 1))()
         given, outs = outs, []
         for i, a in enumerate(arrays):
             lay, cp = pick(layout, i), pick(cap, i)
-            nbytes, per = a.numel() * a.element_size(), (4, 2, 1)[lay] * (bits // 8)
+            nbytes, per = a.numel() * a.element_size(), pixel_bytes(lay, bits)
             if nbytes % per:
                 raise ValueError("an array of whole pixels is needed")
             if given is not None:
@@ -729,13 +735,12 @@ class Session:
         """The distinct UInt8 aggregates ("keys": r | g << 8 | b << 16 | a << 24, v | a << 8 or v) of [PNG.RGBA<T>] / [PNG.VA<T>] /
         [T] as bytes (host order), ascending, and how many pixels have each: -> (list of keys, list of counts).  More than `cap`
         (at most 65536) distinct keys raise SpngError(E_OUTPUT_CAPACITY)."""
-        per = (4, 2, 1)[layout] * (bits // 8)
+        per = pixel_bytes(layout, bits)
         if len(pixels) % per:
             raise ValueError("whole pixels are needed")
-        src = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
         keys, counts = (ctypes.c_uint32 * max(cap, 1))(), (ctypes.c_uint64 * max(cap, 1))()
         res = Result()
-        _check(self.lib, self.lib.spng_census(self.ctx, src, len(pixels) // per, bits, int(layout), int(premultiply), cap, keys, counts,
+        _check(self.lib, self.lib.spng_census(self.ctx, _cbuf(pixels), len(pixels) // per, bits, int(layout), int(premultiply), cap, keys, counts,
                                               ctypes.byref(res)))
         raise_for(res.status)
         return list(keys[:res.written]), list(counts[:res.written])
@@ -745,7 +750,6 @@ class Session:
         distinct, int32 bit patterns) and indices[i] (uint8) are its map, equally long.  -> (list of storage tensors, list[Result]
         with aux[0] = pixels that missed)"""
         n = len(arrays)
-        pick = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
         descs = (PackIndexedDesc * max(n, 1))()
         outs = []
         for i, a in enumerate(arrays):
@@ -763,16 +767,15 @@ class Session:
     def pack_indexed(self, pixels: bytes, w, h, source, layout, keys, indices, miss=0, premultiply=0):
         """One index byte per pixel: indices[j] where keys[j] (ascending, distinct) is the pixel's key, `miss` where none is.
         -> (storage bytes, pixels that missed)"""
-        if len(pixels) != w * h * (4, 2, 1)[layout] * (source // 8):
+        if len(pixels) != w * h * pixel_bytes(layout, source):
             raise ValueError("pixel array `count` must be equal to `size.x * size.y`")
         if len(keys) != len(indices):
             raise ValueError("one index per key is needed")
-        px = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
         k = (ctypes.c_uint32 * max(len(keys), 1))(*keys)
         ix = (ctypes.c_uint8 * max(len(indices), 1))(*bytes(indices))
         out = (ctypes.c_uint8 * max(w * h, 1))()
         res = Result()
-        _check(self.lib, self.lib.spng_pack_indexed(self.ctx, px, w, h, source, int(layout), int(premultiply), k, ix, len(keys),
+        _check(self.lib, self.lib.spng_pack_indexed(self.ctx, _cbuf(pixels), w, h, source, int(layout), int(premultiply), k, ix, len(keys),
                                                     int(miss), out, ctypes.byref(res)))
         raise_for(res.status)
         return bytes(out[:w * h]), int(res.aux[0])
@@ -785,13 +788,13 @@ class Session:
         n = len(arrays)
         descs = (AlphaDesc * max(n, 1))()
         for i, t in enumerate(arrays):
-            lay = layout[i] if isinstance(layout, (list, tuple)) else layout
+            lay = pick(layout, i)
             o = outs[i] if outs is not None else t
             nbytes = t.numel() * t.element_size()
             per = (4, 2)[lay] * (bits // 8)
             if nbytes % per or o.numel() * o.element_size() < nbytes:
                 raise ValueError("an array of whole pixels and an output of at least its size are needed")
-            descs[i] = AlphaDesc(self._ptr(t), self._ptr(o), nbytes // per, bits, lay, op[i] if isinstance(op, (list, tuple)) else op)
+            descs[i] = AlphaDesc(self._ptr(t), self._ptr(o), nbytes // per, bits, lay, pick(op, i))
         res = (Result * max(n, 1))()
         _check(self.lib, self.lib.spng_alpha_batch(self.ctx, descs, n, None, res))
         return list(res)[:n]
@@ -802,10 +805,9 @@ class Session:
         per = (4, 2)[layout] * (bits // 8)
         if len(pixels) % per:
             raise ValueError("whole pixels are needed")
-        src = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
         out = (ctypes.c_uint8 * max(len(pixels), 1))()
         res = Result()
-        _check(self.lib, self.lib.spng_alpha(self.ctx, src, len(pixels) // per, bits, int(layout), int(op), out, ctypes.byref(res)))
+        _check(self.lib, self.lib.spng_alpha(self.ctx, _cbuf(pixels), len(pixels) // per, bits, int(layout), int(op), out, ctypes.byref(res)))
         return bytes(out[:len(pixels)]), int(res.aux[0])
 
     def hsva_batch(self, arrays, ops, outs=None):
@@ -818,7 +820,7 @@ class Session:
         descs = (HsvaDesc * max(n, 1))()
         given, outs = outs, []
         for i, t in enumerate(arrays):
-            op = ops[i] if isinstance(ops, (list, tuple)) else ops
+            op = pick(ops, i)
             if op not in _HSVA_BYTES:
                 raise ValueError("op must be HSVA_FROM_RGBA8, HSVA_TO_RGBA8 or HSVA_TO_VA8")
             per_in, per_out = _HSVA_BYTES[op]
@@ -844,19 +846,17 @@ class Session:
         if len(pixels) % per_in:
             raise ValueError("whole pixels are needed")
         n = len(pixels) // per_in
-        src = (ctypes.c_uint8 * max(len(pixels), 1)).from_buffer_copy(bytes(pixels) or b"\0")
         out = (ctypes.c_uint8 * max(n * per_out, 1))()
         res = Result()
-        _check(self.lib, self.lib.spng_hsva(self.ctx, src, n, int(op), out, ctypes.byref(res)))
+        _check(self.lib, self.lib.spng_hsva(self.ctx, _cbuf(pixels), n, int(op), out, ctypes.byref(res)))
         return bytes(out[:n * per_out]), int(res.aux[0])
 
     def deflate(self, data: bytes, level: int, fmt=FORMAT_ZLIB, exponent: int = 15) -> bytes:
         """Whole-stream LZ77.Deflator (push(all, last: true) + concatenated pull()): -> stream bytes"""
         cap = self.lib.spng_deflate_bound(len(data))
-        src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
         dst = (ctypes.c_uint8 * cap)()
         res = Result()
-        _check(self.lib, self.lib.spng_deflate_window(self.ctx, src, len(data), fmt, level, exponent, dst, cap,
+        _check(self.lib, self.lib.spng_deflate_window(self.ctx, _cbuf(data), len(data), fmt, level, exponent, dst, cap,
                                                       ctypes.byref(res)))
         if res.status != DONE:
             raise SpngError(res.status)
@@ -890,9 +890,8 @@ class Session:
         return outs, list(res)
 
     def adler32(self, data: bytes) -> int:
-        src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
         out = ctypes.c_uint32(0)
-        _check(self.lib, self.lib.spng_adler32(self.ctx, src, len(data), ctypes.byref(out)))
+        _check(self.lib, self.lib.spng_adler32(self.ctx, _cbuf(data), len(data), ctypes.byref(out)))
         return out.value
 
 

@@ -129,12 +129,7 @@ __global__ __launch_bounds__(256) void alpha_kernel(const AlphaJob *__restrict__
             }
         }
     }
-    // one atomic per wave, and only from waves that met such a component
-    if (__ballot(trapped != 0) != 0) {
-#pragma unroll
-        for (int m = 32; m; m >>= 1) trapped += (uint32_t)__shfl_xor((int)trapped, m);
-        if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&job.result->aux[0], (unsigned long long)trapped);
-    }
+    add_wave_count(job.result, trapped);
 }
 
 hipError_t launch_alpha(const AlphaJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream)

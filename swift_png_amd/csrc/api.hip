@@ -211,6 +211,68 @@ struct Arena {
     size_t take(size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; }
 };
 
+// ---- colour targets ------------------------------------------------------------------------------
+// What a batch entry and its host-pointer form both need to know about a desc.
+
+static uint32_t pixel_bytes(int layout, int bits)              // one RGBA<T> / VA<T> / T pixel, T of `bits` bits
+{
+    return (layout == SPNG_TARGET_VA ? 2u : layout == SPNG_TARGET_SCALAR ? 1u : 4u) * (bits / 8);
+}
+static uint32_t hsva_in_bytes(int op) { return op == SPNG_HSVA_FROM_RGBA8 ? 4u : 8u; }
+static uint32_t hsva_out_bytes(int op) { return op == SPNG_HSVA_FROM_RGBA8 ? 8u : op == SPNG_HSVA_TO_RGBA8 ? 4u : 2u; }
+
+// A desc's `premultiply` (spng_alpha_desc.op too): 0 ... highest, the (as: UInt8.self) forms for T = UInt16 only, none for scalars.
+static bool valid_premultiply(int value, int bits, int layout, int highest)
+{
+    return value <= highest && !((value == SPNG_PREMULTIPLY_AS_U8 || value == SPNG_STRAIGHTEN_AS_U8) && bits != 16) &&
+           !(layout == SPNG_TARGET_SCALAR && value);
+}
+
+template <size_t N> static bool all_zero(const uint8_t (&reserved)[N]) { return std::all_of(reserved, reserved + N, [](uint8_t r) { return !r; }); }
+
+// [a, a + an) and [b, b + bn) share a byte.  (Equal ranges do: an entry that works in place allows a == b itself.)
+static bool overlap(uintptr_t a, uint64_t an, uintptr_t b, uint64_t bn) { return a < b + bn && b < a + an; }
+
+// Workgroups for the longest array of a call: `per_block` of its elements each (256 threads, a few rounds), 4096 at most.
+static uint32_t blocks_for(uint64_t most, uint32_t per_block) { return (uint32_t)std::min<uint64_t>((most + per_block - 1) / per_block, 4096); }
+
+// The call of an entry whose results the host fills in (alpha, hsva, pack_indexed): one Job and one result per desc, written into
+// the arena and uploaded; the results go to d_results by a copy of their own when the caller gave one.
+//   fill(desc, job, result, extent) -> bool: checks one desc and fills its zeroed job, its result (status SPNG_DONE so far) and
+//     the extent its launch is sized by; false refuses the call (SPNG_E_ARGUMENT) with nothing enqueued.
+//   launch(d_jobs, count, most) -> hipError_t: the entry's kernels; most: the largest extent (1 at least).
+template <class Job, class Desc, class Fill, class Launch>
+static int32_t result_batch(spng_ctx *c, const Desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results,
+                            Fill fill, Launch launch)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    if (int32_t st = c->reserve(count * (sizeof(Job) + sizeof(spng_result)) + 1024)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(Job)), rslot = a.take(count * sizeof(spng_result));
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    uint64_t most = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        Job j;
+        memset(&j, 0, sizeof j);
+        j.result = dr + i;
+        spng_result r{};
+        r.status = SPNG_DONE;
+        uint64_t extent = 0;
+        if (!fill(descs[i], j, r, extent)) return SPNG_E_ARGUMENT;
+        a.host<Job>(jslot)[i] = j;
+        a.host<spng_result>(rslot)[i] = r;
+        most = extent > most ? extent : most;
+    }
+    if (d_results)
+        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
+    if (int32_t st = c->upload(0, a.off)) return st;
+    HIP_TRY(launch(a.dev<Job>(jslot), count, most));
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
 extern "C" {
 
 int32_t spng_version(void) { return SPNG_VERSION; }
@@ -1303,6 +1365,10 @@ struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+    // alloc, and the n bytes at `host` copied in behind what the stream holds (n == 0: no copy)
+    hipError_t alloc_from(const void *host, size_t n, hipStream_t stream)
+    { const hipError_t e = alloc(n); return e != hipSuccess || !n ? e : hipMemcpyAsync(p, host, n, hipMemcpyHostToDevice, stream); }
+    hipError_t copy_to(void *host, size_t n) const { return n ? hipMemcpy(host, p, n, hipMemcpyDeviceToHost) : hipSuccess; }
 };
 
 int32_t spng_inflate(spng_ctx *c, const void *src, uint64_t n, int32_t format,
@@ -1452,13 +1518,12 @@ int32_t spng_filter(spng_ctx *c, const void *storage,
     const uint64_t u = spng_inflated_size(w, h, depth, channels, interlaced);
     const uint64_t s = spng_storage_size(w, h, depth, channels);
     DevBuf dr, dst;
-    HIP_TRY(dr.alloc(u)); HIP_TRY(dst.alloc(s));
-    HIP_TRY(hipMemcpyAsync(dst.p, storage, s, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(dr.alloc(u)); HIP_TRY(dst.alloc_from(storage, s, c->stream));
     spng_image_desc d{};
     d.d_rows = dr.p; d.rows_cap = u; d.d_storage = dst.p; d.width = w; d.height = h;
     d.depth = (uint8_t)depth; d.channels = (uint8_t)channels; d.interlaced = (uint8_t)(interlaced != 0);
     if (int32_t st = spng_filter_batch(c, &d, 1, nullptr, result)) return st;
-    HIP_TRY(hipMemcpy(rows, dr.p, u, hipMemcpyDeviceToHost));
+    HIP_TRY(dr.copy_to(rows, u));
     return SPNG_DONE;
 }
 
@@ -1562,9 +1627,7 @@ int32_t spng_unpack_batch(spng_ctx *c, const spng_unpack_desc *descs, uint32_t c
         const spng_unpack_desc &d = descs[i];
         if (!valid_format(d.depth, d.channels) || !d.d_storage || !d.d_out || d.target != target ||
             (d.indexed && (d.channels != 1 || d.depth > 8 || (!d.d_palette && d.palette_count))) ||
-            d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_STRAIGHTEN_AS_U8 ||
-            ((d.premultiply == SPNG_PREMULTIPLY_AS_U8 || d.premultiply == SPNG_STRAIGHTEN_AS_U8) && target != 16) ||
-            (d.layout == SPNG_TARGET_SCALAR && d.premultiply))
+            d.layout > SPNG_TARGET_SCALAR || !valid_premultiply(d.premultiply, target, d.layout, SPNG_STRAIGHTEN_AS_U8))
             return SPNG_E_ARGUMENT;
         UnpackJob j;
         memset(&j, 0, sizeof j);
@@ -1578,10 +1641,8 @@ int32_t spng_unpack_batch(spng_ctx *c, const spng_unpack_desc *descs, uint32_t c
         maxpix = px > maxpix ? px : maxpix;
     }
     if (int32_t st = c->upload(0, a.off)) return st;
-    uint64_t bx = (maxpix + 4095) / 4096;                      // (four pixels per thread, 256 threads, a few rounds)
-    if (bx > 4096) bx = 4096;
     Timed t(c, SPNG_K_UNPACK);
-    HIP_TRY(launch_unpack(a.dev<UnpackJob>(jslot), count, (uint32_t)bx, target, c->stream));
+    HIP_TRY(launch_unpack(a.dev<UnpackJob>(jslot), count, blocks_for(maxpix, 4096), target, c->stream));   // (four pixels per thread)
     return SPNG_DONE;
 }
 
@@ -1591,12 +1652,10 @@ int32_t spng_unpack_as(spng_ctx *c, const void *storage, uint32_t w, uint32_t h,
 {
     if (!c || !storage || !out || !valid_format(depth, channels) || (target != 8 && target != 16)) return SPNG_E_ARGUMENT;
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t s = spng_storage_size(w, h, depth, channels),
-                   o = (uint64_t)w * h * (layout == SPNG_TARGET_VA ? 2 : layout == SPNG_TARGET_SCALAR ? 1 : 4) * (target / 8);
+    const uint64_t o = (uint64_t)w * h * pixel_bytes(layout, target);
     DevBuf ds, dout, dp;
-    HIP_TRY(ds.alloc(s)); HIP_TRY(dout.alloc(o)); HIP_TRY(dp.alloc((size_t)palette_count * 4));
-    HIP_TRY(hipMemcpyAsync(ds.p, storage, s, hipMemcpyHostToDevice, c->stream));
-    if (palette_count) HIP_TRY(hipMemcpyAsync(dp.p, palette, (size_t)palette_count * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ds.alloc_from(storage, spng_storage_size(w, h, depth, channels), c->stream)); HIP_TRY(dout.alloc(o));
+    HIP_TRY(dp.alloc_from(palette, (size_t)palette_count * 4, c->stream));
     spng_unpack_desc d{};
     d.d_storage = ds.p; d.d_out = dout.p; d.d_palette = palette_count ? dp.p : nullptr;
     d.width = w; d.height = h; d.palette_count = palette_count;
@@ -1605,7 +1664,7 @@ int32_t spng_unpack_as(spng_ctx *c, const void *storage, uint32_t w, uint32_t h,
     d.target = (uint8_t)target; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply;
     if (int32_t st = spng_unpack_batch(c, &d, 1)) return st;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (o) HIP_TRY(hipMemcpy(out, dout.p, o, hipMemcpyDeviceToHost));
+    HIP_TRY(dout.copy_to(out, o));
     return SPNG_DONE;
 }
 
@@ -1633,8 +1692,7 @@ int32_t spng_pack_batch(spng_ctx *c, const spng_pack_desc *descs, uint32_t count
         if (!valid_format(d.depth, d.channels) || !d.d_storage || !d.d_pixels || d.source != source ||
             (d.indexed && (d.channels != 1 || d.depth > 8 || (!d.d_palette && d.palette_count) || d.palette_count > 256)) ||
             d.layout > SPNG_TARGET_SCALAR || ((uintptr_t)d.d_pixels & (source / 8 - 1)) ||
-            d.premultiply > SPNG_PREMULTIPLY_AS_U8 || (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && source != 16) ||
-            (d.layout == SPNG_TARGET_SCALAR && d.premultiply))
+            !valid_premultiply(d.premultiply, source, d.layout, SPNG_PREMULTIPLY_AS_U8))
             return SPNG_E_ARGUMENT;
         PackJob j;
         memset(&j, 0, sizeof j);
@@ -1647,10 +1705,8 @@ int32_t spng_pack_batch(spng_ctx *c, const spng_pack_desc *descs, uint32_t count
         maxpix = px > maxpix ? px : maxpix;
     }
     if (int32_t st = c->upload(0, a.off)) return st;
-    uint64_t bx = (maxpix + 4095) / 4096;                      // (four pixels per thread, 256 threads, a few rounds)
-    if (bx > 4096) bx = 4096;
     Timed t(c, SPNG_K_PACK);
-    HIP_TRY(launch_pack(a.dev<PackJob>(jslot), count, (uint32_t)bx, source, c->stream));
+    HIP_TRY(launch_pack(a.dev<PackJob>(jslot), count, blocks_for(maxpix, 4096), source, c->stream));       // (four pixels per thread)
     return SPNG_DONE;
 }
 
@@ -1660,12 +1716,10 @@ int32_t spng_pack_as(spng_ctx *c, const void *pixels, uint32_t w, uint32_t h, in
     if (!c || !storage || !pixels || !valid_format(depth, channels) || (source != 8 && source != 16) || layout < 0 ||
         layout > SPNG_TARGET_SCALAR) return SPNG_E_ARGUMENT;
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t s = spng_storage_size(w, h, depth, channels),
-                   o = (uint64_t)w * h * (layout == SPNG_TARGET_VA ? 2 : layout == SPNG_TARGET_SCALAR ? 1 : 4) * (source / 8);
+    const uint64_t s = spng_storage_size(w, h, depth, channels);
     DevBuf ds, dpx, dp;
-    HIP_TRY(ds.alloc(s)); HIP_TRY(dpx.alloc(o)); HIP_TRY(dp.alloc((size_t)palette_count * 4));
-    HIP_TRY(hipMemcpyAsync(dpx.p, pixels, o, hipMemcpyHostToDevice, c->stream));
-    if (palette_count) HIP_TRY(hipMemcpyAsync(dp.p, palette, (size_t)palette_count * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ds.alloc(s)); HIP_TRY(dpx.alloc_from(pixels, (uint64_t)w * h * pixel_bytes(layout, source), c->stream));
+    HIP_TRY(dp.alloc_from(palette, (size_t)palette_count * 4, c->stream));
     spng_pack_desc d{};
     d.d_pixels = dpx.p; d.d_storage = ds.p; d.d_palette = palette_count ? dp.p : nullptr;
     d.width = w; d.height = h; d.palette_count = palette_count;
@@ -1673,49 +1727,29 @@ int32_t spng_pack_as(spng_ctx *c, const void *pixels, uint32_t w, uint32_t h, in
     d.source = (uint8_t)source; d.layout = (uint8_t)layout;
     if (int32_t st = spng_pack_batch(c, &d, 1)) return st;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (s) HIP_TRY(hipMemcpy(storage, ds.p, s, hipMemcpyDeviceToHost));
+    HIP_TRY(ds.copy_to(storage, s));
     return SPNG_DONE;
 }
 
 int32_t spng_alpha_batch(spng_ctx *c, const spng_alpha_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
 {
-    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
-    if (!count) return SPNG_DONE;
-    HIP_TRY(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> g(c->mu);
-    const int bits = descs[0].bits;
-    if (bits != 8 && bits != 16) return SPNG_E_ARGUMENT;
-    if (int32_t st = c->reserve(count * (sizeof(AlphaJob) + sizeof(spng_result)) + 1024)) return st;
-    Arena a{c};
-    const size_t jslot = a.take(count * sizeof(AlphaJob)), rslot = a.take(count * sizeof(spng_result));
-    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
-    uint64_t most = 1;
-    for (uint32_t i = 0; i < count; ++i) {
-        const spng_alpha_desc &d = descs[i];
-        const uint64_t bytes = d.count * (d.layout == SPNG_TARGET_VA ? 2u : 4u) * (bits / 8);
-        const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out;
-        bool bad = d.bits != bits || d.layout > SPNG_TARGET_VA || d.op < SPNG_PREMULTIPLY || d.op > SPNG_STRAIGHTEN_AS_U8 ||
-                   ((d.op == SPNG_PREMULTIPLY_AS_U8 || d.op == SPNG_STRAIGHTEN_AS_U8) && bits != 16) ||
-                   d.count > (~0ull >> 4) || ((in | out) & (bits / 8 - 1)) || (d.count && (!in || !out)) ||
-                   (in != out && in < out + bytes && out < in + bytes);
-        for (uint8_t r : d.reserved) bad = bad || r;
-        if (bad) return SPNG_E_ARGUMENT;
-        AlphaJob j;
-        memset(&j, 0, sizeof j);
-        j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.result = dr + i; j.layout = d.layout; j.op = d.op;
-        a.host<AlphaJob>(jslot)[i] = j;
-        spng_result r{};
-        r.status = SPNG_DONE; r.written = bytes; r.consumed = bytes;
-        a.host<spng_result>(rslot)[i] = r;                      // (aux[0]: the kernel adds the trapped components)
-        most = bytes > most ? bytes : most;
-    }
-    if (d_results)
-        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
-    if (int32_t st = c->upload(0, a.off)) return st;
-    uint64_t bx = (most + 16383) / 16384;                       // (16 bytes per thread, 256 threads, a few rounds)
-    if (bx > 4096) bx = 4096;
-    { Timed t(c, SPNG_K_ALPHA); HIP_TRY(launch_alpha(a.dev<AlphaJob>(jslot), count, (uint32_t)bx, bits, c->stream)); }
-    return read_back(c, h_results, dr, count * sizeof(spng_result));
+    return result_batch<AlphaJob>(c, descs, count, d_results, h_results,
+        [=](const spng_alpha_desc &d, AlphaJob &j, spng_result &r, uint64_t &extent) {
+            const int bits = descs[0].bits;
+            const uint64_t bytes = d.count * pixel_bytes(d.layout, bits);
+            const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out;
+            if ((bits != 8 && bits != 16) || d.bits != bits || d.layout > SPNG_TARGET_VA || d.op < SPNG_PREMULTIPLY ||
+                !valid_premultiply(d.op, bits, d.layout, SPNG_STRAIGHTEN_AS_U8) || d.count > (~0ull >> 4) ||
+                ((in | out) & (bits / 8 - 1)) || (d.count && (!in || !out)) || (in != out && overlap(in, bytes, out, bytes)) ||
+                !all_zero(d.reserved)) return false;
+            j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.layout = d.layout; j.op = d.op;
+            r.written = r.consumed = extent = bytes;            // (aux[0]: the kernel adds the trapped components)
+            return true;
+        },
+        [=](const AlphaJob *d_jobs, uint32_t n, uint64_t most) {
+            Timed t(c, SPNG_K_ALPHA);                           // (16 bytes per thread)
+            return launch_alpha(d_jobs, n, blocks_for(most, 16384), descs[0].bits, c->stream);
+        });
 }
 
 int32_t spng_alpha(spng_ctx *c, const void *pixels, uint64_t n, int bits, int layout, int op, void *out, spng_result *result)
@@ -1723,54 +1757,34 @@ int32_t spng_alpha(spng_ctx *c, const void *pixels, uint64_t n, int bits, int la
     if (!c || (n && (!pixels || !out)) || !result || (bits != 8 && bits != 16) || layout < 0 || layout > SPNG_TARGET_VA ||
         op < 0 || op > 255 || n > (~0ull >> 4)) return SPNG_E_ARGUMENT;
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t bytes = n * (layout == SPNG_TARGET_VA ? 2u : 4u) * (bits / 8);
+    const uint64_t bytes = n * pixel_bytes(layout, bits);
     DevBuf dpx;
-    HIP_TRY(dpx.alloc(bytes));
-    if (bytes) HIP_TRY(hipMemcpyAsync(dpx.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(dpx.alloc_from(pixels, bytes, c->stream));
     spng_alpha_desc d{};
     d.d_in = dpx.p; d.d_out = dpx.p; d.count = n; d.bits = (uint8_t)bits; d.layout = (uint8_t)layout; d.op = (uint8_t)op;
     if (int32_t st = spng_alpha_batch(c, &d, 1, nullptr, result)) return st;
-    if (bytes) HIP_TRY(hipMemcpy(out, dpx.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(dpx.copy_to(out, bytes));
     return SPNG_DONE;
 }
 
 int32_t spng_hsva_batch(spng_ctx *c, const spng_hsva_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
 {
-    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
-    if (!count) return SPNG_DONE;
-    HIP_TRY(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> g(c->mu);
-    if (int32_t st = c->reserve(count * (sizeof(HsvaJob) + sizeof(spng_result)) + 1024)) return st;
-    Arena a{c};
-    const size_t jslot = a.take(count * sizeof(HsvaJob)), rslot = a.take(count * sizeof(spng_result));
-    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
-    uint64_t most = 1;
-    for (uint32_t i = 0; i < count; ++i) {
-        const spng_hsva_desc &d = descs[i];
-        if (d.op < SPNG_HSVA_FROM_RGBA8 || d.op > SPNG_HSVA_TO_VA8 || d.count > (~0ull >> 4)) return SPNG_E_ARGUMENT;
-        const uint64_t ibytes = d.count * (d.op == SPNG_HSVA_FROM_RGBA8 ? 4u : 8u),
-                       obytes = d.count * (d.op == SPNG_HSVA_FROM_RGBA8 ? 8u : d.op == SPNG_HSVA_TO_RGBA8 ? 4u : 2u);
-        const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out, hsva = d.op == SPNG_HSVA_FROM_RGBA8 ? out : in;
-        // the element sizes differ: nothing runs in place, and no other overlap is allowed either
-        bool bad = (hsva & 3) || (d.count && (!in || !out)) || (in && in == out) || (in < out + obytes && out < in + ibytes);
-        for (uint8_t r : d.reserved) bad = bad || r;
-        if (bad) return SPNG_E_ARGUMENT;
-        HsvaJob j;
-        memset(&j, 0, sizeof j);
-        j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.result = dr + i; j.op = d.op;
-        a.host<HsvaJob>(jslot)[i] = j;
-        spng_result r{};
-        r.status = SPNG_DONE; r.written = obytes; r.consumed = ibytes;
-        a.host<spng_result>(rslot)[i] = r;                      // (aux[0]: the kernel adds the trapped pixels)
-        most = d.count > most ? d.count : most;
-    }
-    if (d_results)
-        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
-    if (int32_t st = c->upload(0, a.off)) return st;
-    uint64_t bx = (most + 4095) / 4096;                         // (four pixels per thread, 256 threads, a few rounds)
-    if (bx > 4096) bx = 4096;
-    { Timed t(c, SPNG_K_HSVA); HIP_TRY(launch_hsva(a.dev<HsvaJob>(jslot), count, (uint32_t)bx, c->stream)); }
-    return read_back(c, h_results, dr, count * sizeof(spng_result));
+    return result_batch<HsvaJob>(c, descs, count, d_results, h_results,
+        [](const spng_hsva_desc &d, HsvaJob &j, spng_result &r, uint64_t &extent) {
+            if (d.op < SPNG_HSVA_FROM_RGBA8 || d.op > SPNG_HSVA_TO_VA8 || d.count > (~0ull >> 4)) return false;
+            const uint64_t ibytes = d.count * hsva_in_bytes(d.op), obytes = d.count * hsva_out_bytes(d.op);
+            const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out, hsva = d.op == SPNG_HSVA_FROM_RGBA8 ? out : in;
+            // the element sizes differ: nothing runs in place, and no other overlap is allowed either
+            if ((hsva & 3) || (d.count && (!in || !out)) || (in && in == out) || overlap(in, ibytes, out, obytes) ||
+                !all_zero(d.reserved)) return false;
+            j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.op = d.op;
+            r.written = obytes; r.consumed = ibytes; extent = d.count;   // (aux[0]: the kernel adds the trapped pixels)
+            return true;
+        },
+        [=](const HsvaJob *d_jobs, uint32_t n, uint64_t most) {
+            Timed t(c, SPNG_K_HSVA);                            // (four pixels per thread)
+            return launch_hsva(d_jobs, n, blocks_for(most, 4096), c->stream);
+        });
 }
 
 int32_t spng_hsva(spng_ctx *c, const void *pixels, uint64_t n, int op, void *out, spng_result *result)
@@ -1778,15 +1792,13 @@ int32_t spng_hsva(spng_ctx *c, const void *pixels, uint64_t n, int op, void *out
     if (!c || (n && (!pixels || !out)) || !result || op < SPNG_HSVA_FROM_RGBA8 || op > SPNG_HSVA_TO_VA8 || n > (~0ull >> 4))
         return SPNG_E_ARGUMENT;
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t ibytes = n * (op == SPNG_HSVA_FROM_RGBA8 ? 4u : 8u),
-                   obytes = n * (op == SPNG_HSVA_FROM_RGBA8 ? 8u : op == SPNG_HSVA_TO_RGBA8 ? 4u : 2u);
+    const uint64_t obytes = n * hsva_out_bytes(op);
     DevBuf din, dout;
-    HIP_TRY(din.alloc(ibytes)); HIP_TRY(dout.alloc(obytes));
-    if (ibytes) HIP_TRY(hipMemcpyAsync(din.p, pixels, ibytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(din.alloc_from(pixels, n * hsva_in_bytes(op), c->stream)); HIP_TRY(dout.alloc(obytes));
     spng_hsva_desc d{};
     d.d_in = din.p; d.d_out = dout.p; d.count = n; d.op = (uint8_t)op;
     if (int32_t st = spng_hsva_batch(c, &d, 1, nullptr, result)) return st;
-    if (obytes) HIP_TRY(hipMemcpy(out, dout.p, obytes, hipMemcpyDeviceToHost));
+    HIP_TRY(dout.copy_to(out, obytes));
     return SPNG_DONE;
 }
 
@@ -1802,11 +1814,10 @@ int32_t spng_census_batch(spng_ctx *c, const spng_census_desc *descs, uint32_t c
     uint64_t zeroed = 0, sorts = 0, most = 1;
     for (uint32_t i = 0; i < count; ++i) {
         const spng_census_desc &d = descs[i];
-        bool bad = d.bits != bits || d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_PREMULTIPLY_AS_U8 ||
-                   (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && bits != 16) || (d.layout == SPNG_TARGET_SCALAR && d.premultiply) ||
-                   d.cap < 1 || d.cap > 65536 || !d.d_keys || ((uintptr_t)d.d_keys & 3) || ((uintptr_t)d.d_counts & 7) ||
-                   (d.count && !d.d_pixels) || ((uintptr_t)d.d_pixels & (bits / 8 - 1)) || d.count > (~0ull >> 4) || d.reserved[0];
-        if (bad) return SPNG_E_ARGUMENT;
+        if (d.bits != bits || d.layout > SPNG_TARGET_SCALAR || !valid_premultiply(d.premultiply, bits, d.layout, SPNG_PREMULTIPLY_AS_U8) ||
+            d.cap < 1 || d.cap > 65536 || !d.d_keys || ((uintptr_t)d.d_keys & 3) || ((uintptr_t)d.d_counts & 7) ||
+            (d.count && !d.d_pixels) || ((uintptr_t)d.d_pixels & (bits / 8 - 1)) || d.count > (~0ull >> 4) || !all_zero(d.reserved))
+            return SPNG_E_ARGUMENT;
         zeroed += 256 + 16ull * census_slots(d.cap);
         sorts += 8ull * census_sort_elems(d.cap);
         most = d.count > most ? d.count : most;
@@ -1847,17 +1858,16 @@ int32_t spng_census(spng_ctx *c, const void *pixels, uint64_t n, int bits, int l
     if (!c || (n && !pixels) || !keys || !result || (bits != 8 && bits != 16) || layout < 0 || layout > SPNG_TARGET_SCALAR ||
         premultiply < 0 || premultiply > 255 || cap < 1 || cap > 65536 || n > (~0ull >> 4)) return SPNG_E_ARGUMENT;
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t bytes = n * (layout == SPNG_TARGET_VA ? 2u : layout == SPNG_TARGET_SCALAR ? 1u : 4u) * (bits / 8);
     DevBuf dpx, dk, dc;
-    HIP_TRY(dpx.alloc(bytes)); HIP_TRY(dk.alloc((size_t)cap * 4)); HIP_TRY(dc.alloc((size_t)cap * 8));
-    if (bytes) HIP_TRY(hipMemcpyAsync(dpx.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(dpx.alloc_from(pixels, n * pixel_bytes(layout, bits), c->stream));
+    HIP_TRY(dk.alloc((size_t)cap * 4)); HIP_TRY(dc.alloc((size_t)cap * 8));
     spng_census_desc d{};
     d.d_pixels = dpx.p; d.count = n; d.d_keys = dk.p; d.d_counts = counts ? dc.p : nullptr; d.cap = cap;
     d.bits = (uint8_t)bits; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply;
     if (int32_t st = spng_census_batch(c, &d, 1, nullptr, result)) return st;
-    if (result->status == SPNG_DONE && result->written) {
-        HIP_TRY(hipMemcpy(keys, dk.p, result->written * 4, hipMemcpyDeviceToHost));
-        if (counts) HIP_TRY(hipMemcpy(counts, dc.p, result->written * 8, hipMemcpyDeviceToHost));
+    if (result->status == SPNG_DONE) {
+        HIP_TRY(dk.copy_to(keys, result->written * 4));
+        if (counts) HIP_TRY(dc.copy_to(counts, result->written * 8));
     }
     return SPNG_DONE;
 }
@@ -1865,44 +1875,24 @@ int32_t spng_census(spng_ctx *c, const void *pixels, uint64_t n, int bits, int l
 int32_t spng_pack_indexed_batch(spng_ctx *c, const spng_pack_indexed_desc *descs, uint32_t count, spng_result *d_results,
                                 spng_result *h_results)
 {
-    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
-    if (!count) return SPNG_DONE;
-    HIP_TRY(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> g(c->mu);
-    const int source = descs[0].source;
-    if (source != 8 && source != 16) return SPNG_E_ARGUMENT;
-    if (int32_t st = c->reserve(count * (sizeof(PackIndexedJob) + sizeof(spng_result)) + 1024)) return st;
-    Arena a{c};
-    const size_t jslot = a.take(count * sizeof(PackIndexedJob)), rslot = a.take(count * sizeof(spng_result));
-    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
-    uint64_t maxpix = 1;
-    for (uint32_t i = 0; i < count; ++i) {
-        const spng_pack_indexed_desc &d = descs[i];
-        const uint64_t px = (uint64_t)d.width * d.height;
-        bool bad = d.source != source || d.layout > SPNG_TARGET_SCALAR || d.premultiply > SPNG_PREMULTIPLY_AS_U8 ||
-                   (d.premultiply == SPNG_PREMULTIPLY_AS_U8 && source != 16) || (d.layout == SPNG_TARGET_SCALAR && d.premultiply) ||
-                   d.map_count > 65536 || (d.map_count && (!d.d_keys || !d.d_indices)) || ((uintptr_t)d.d_keys & 3) ||
-                   (px && (!d.d_pixels || !d.d_storage)) || ((uintptr_t)d.d_pixels & (source / 8 - 1));
-        for (uint8_t r : d.reserved) bad = bad || r;
-        if (bad) return SPNG_E_ARGUMENT;
-        PackIndexedJob j;
-        memset(&j, 0, sizeof j);
-        j.pixels = d.d_pixels; j.storage = (uint8_t *)d.d_storage; j.keys = (const uint32_t *)d.d_keys; j.indices = (const uint8_t *)d.d_indices;
-        j.result = dr + i; j.width = d.width; j.height = d.height; j.map_count = d.map_count;
-        j.layout = d.layout; j.premultiply = d.premultiply; j.miss = d.miss;
-        a.host<PackIndexedJob>(jslot)[i] = j;
-        spng_result r{};
-        r.status = SPNG_DONE; r.written = px; r.consumed = px;
-        a.host<spng_result>(rslot)[i] = r;                      // (aux[0]: the kernel adds the pixels that missed)
-        maxpix = px > maxpix ? px : maxpix;
-    }
-    if (d_results)
-        HIP_TRY(hipMemcpyAsync(d_results, a.host<spng_result>(rslot), count * sizeof(spng_result), hipMemcpyHostToDevice, c->stream));
-    if (int32_t st = c->upload(0, a.off)) return st;
-    uint64_t bx = (maxpix + 4095) / 4096;                      // (four pixels per thread, 256 threads, a few rounds)
-    if (bx > 4096) bx = 4096;
-    { Timed t(c, SPNG_K_PACK_INDEXED); HIP_TRY(launch_pack_indexed(a.dev<PackIndexedJob>(jslot), count, (uint32_t)bx, source, c->stream)); }
-    return read_back(c, h_results, dr, count * sizeof(spng_result));
+    return result_batch<PackIndexedJob>(c, descs, count, d_results, h_results,
+        [=](const spng_pack_indexed_desc &d, PackIndexedJob &j, spng_result &r, uint64_t &extent) {
+            const int source = descs[0].source;
+            const uint64_t px = (uint64_t)d.width * d.height;
+            if ((source != 8 && source != 16) || d.source != source || d.layout > SPNG_TARGET_SCALAR ||
+                !valid_premultiply(d.premultiply, source, d.layout, SPNG_PREMULTIPLY_AS_U8) || d.map_count > 65536 ||
+                (d.map_count && (!d.d_keys || !d.d_indices)) || ((uintptr_t)d.d_keys & 3) || (px && (!d.d_pixels || !d.d_storage)) ||
+                ((uintptr_t)d.d_pixels & (source / 8 - 1)) || !all_zero(d.reserved)) return false;
+            j.pixels = d.d_pixels; j.storage = (uint8_t *)d.d_storage; j.keys = (const uint32_t *)d.d_keys; j.indices = (const uint8_t *)d.d_indices;
+            j.width = d.width; j.height = d.height; j.map_count = d.map_count;
+            j.layout = d.layout; j.premultiply = d.premultiply; j.miss = d.miss;
+            r.written = r.consumed = extent = px;               // (aux[0]: the kernel adds the pixels that missed)
+            return true;
+        },
+        [=](const PackIndexedJob *d_jobs, uint32_t n, uint64_t most) {
+            Timed t(c, SPNG_K_PACK_INDEXED);                    // (four pixels per thread)
+            return launch_pack_indexed(d_jobs, n, blocks_for(most, 4096), descs[0].source, c->stream);
+        });
 }
 
 int32_t spng_pack_indexed(spng_ctx *c, const void *pixels, uint32_t w, uint32_t h, int source, int layout, int premultiply,
@@ -1914,20 +1904,15 @@ int32_t spng_pack_indexed(spng_ctx *c, const void *pixels, uint32_t w, uint32_t 
         return SPNG_E_ARGUMENT;
     for (uint32_t i = 1; i < map_count; ++i) if (keys[i] <= keys[i - 1]) return SPNG_E_ARGUMENT;   // ascending and distinct
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t bytes = px * (layout == SPNG_TARGET_VA ? 2u : layout == SPNG_TARGET_SCALAR ? 1u : 4u) * (source / 8);
     DevBuf dpx, ds, dk, di;
-    HIP_TRY(dpx.alloc(bytes)); HIP_TRY(ds.alloc(px)); HIP_TRY(dk.alloc((size_t)map_count * 4)); HIP_TRY(di.alloc(map_count));
-    if (bytes) HIP_TRY(hipMemcpyAsync(dpx.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
-    if (map_count) {
-        HIP_TRY(hipMemcpyAsync(dk.p, keys, (size_t)map_count * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(di.p, indices, map_count, hipMemcpyHostToDevice, c->stream));
-    }
+    HIP_TRY(dpx.alloc_from(pixels, px * pixel_bytes(layout, source), c->stream)); HIP_TRY(ds.alloc(px));
+    HIP_TRY(dk.alloc_from(keys, (size_t)map_count * 4, c->stream)); HIP_TRY(di.alloc_from(indices, map_count, c->stream));
     spng_pack_indexed_desc d{};
     d.d_pixels = dpx.p; d.d_storage = ds.p; d.d_keys = map_count ? dk.p : nullptr; d.d_indices = map_count ? di.p : nullptr;
     d.width = w; d.height = h; d.map_count = map_count;
     d.source = (uint8_t)source; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply; d.miss = (uint8_t)miss;
     if (int32_t st = spng_pack_indexed_batch(c, &d, 1, nullptr, result)) return st;
-    if (px) HIP_TRY(hipMemcpy(storage, ds.p, px, hipMemcpyDeviceToHost));
+    HIP_TRY(ds.copy_to(storage, px));
     return SPNG_DONE;
 }
 

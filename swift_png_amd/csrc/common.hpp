@@ -39,6 +39,16 @@ struct SpinGuard {
     }
 };
 
+// The epilogue of a kernel whose lanes counted what the reference would have trapped on: the counts of a wave are added to
+// result->aux[0] by one atomic per wave, and only from waves that counted anything.  Every lane of the wave arrives here.
+__device__ __forceinline__ void add_wave_count(spng_result *result, uint32_t n)
+{
+    if (__ballot(n != 0) == 0) return;
+#pragma unroll
+    for (int m = 32; m; m >>= 1) n += (uint32_t)__shfl_xor((int)n, m);
+    if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&result->aux[0], (unsigned long long)n);
+}
+
 // One unfilter job = one dependency chain of scanlines: a whole non-interlaced image or one
 // Adam7 sub-image (PNG.Decoder.swift:59-140).  Rows are `in_stride` apart starting at `in`
 // (which points at the first row's filter byte); defiltered bytes of row y go to

@@ -85,12 +85,7 @@ __global__ __launch_bounds__(256) void hsva_kernel(const HsvaJob *__restrict__ j
     case SPNG_HSVA_TO_RGBA8: hsva_run<SPNG_HSVA_TO_RGBA8>(job, trapped); break;
     case SPNG_HSVA_TO_VA8: hsva_run<SPNG_HSVA_TO_VA8>(job, trapped); break;
     }
-    // one atomic per wave, and only from waves that met such a pixel
-    if (__ballot(trapped != 0) != 0) {
-#pragma unroll
-        for (int m = 32; m; m >>= 1) trapped += (uint32_t)__shfl_xor((int)trapped, m);
-        if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&job.result->aux[0], (unsigned long long)trapped);
-    }
+    add_wave_count(job.result, trapped);
 }
 
 hipError_t launch_hsva(const HsvaJob *d_jobs, uint32_t count, uint32_t blocks_x, hipStream_t stream)

@@ -4,27 +4,16 @@ The kernel's speed depends on properties the source cannot express and a refacto
 lose (profiles/r01_unfilter_tuning.md): four workgroups of 256 threads per CU (LDS <= 40 KiB), no
 scratch memory, no scalar-register spills in the decode loops, LDS and global memory reached with
 their own instructions (no generic `flat_` accesses)."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from codegen_tools import kernel_table
 
 
 @pytest.fixture(scope="module")
 def inflate_asm():
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(ROOT, "swift_png_amd", "csrc", "inflate.hip")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                        "-o", os.path.join(tmp, "inflate.s"), src], check=True, capture_output=True, timeout=600)
-        yield open(os.path.join(tmp, "inflate.s")).read()
+    return kernel_table("inflate")[0]
 
 
 def _meta(asm, key):
@@ -55,25 +44,6 @@ def test_inflate_walk_is_straight_line(inflate_asm):
 
 
 # ---- the kernels the decode step spends its time in: occupancy is set by LDS and registers ------
-def _kernels(name):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(ROOT, "swift_png_amd", "csrc", name + ".hip")
-        out = os.path.join(tmp, name + ".s")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
-                       check=True, capture_output=True, timeout=900)
-        asm = open(out).read()
-    table = {}
-    for blk in re.split(r"\n  - ", asm[asm.index("amdhsa.kernels:"):])[1:]:
-        def get(key, blk=blk):
-            m = re.search(r"\." + key + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        table[get("name")] = {k: int(get(k)) for k in ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count",
-                                                       "vgpr_spill_count", "max_flat_workgroup_size")}
-    return asm, table
-
-
 def _one(table, fragment):
     # (not the <RETRY = 1> instantiations, nor resolve's <_, MARK = true> unless asked for by its mangled arguments)
     hits = [v for k, v in table.items() if fragment in k and "ILj1E" not in k and ("Lb1E" not in k or "Lb1E" in fragment)]
@@ -82,7 +52,7 @@ def _one(table, fragment):
 
 
 def test_pipeline_kernel_resources():
-    asm, table = _kernels("pinflate2")
+    asm, table = kernel_table("pinflate2")
     dec = _one(table, "pinf2_decode_kernel")
     assert dec["group_segment_fixed_size"] <= 10240          # 16 one-wave workgroups per CU: as many as 128 registers allow
     assert dec["vgpr_count"] <= 128                          # >= 4 waves per SIMD
@@ -106,7 +76,7 @@ def test_pipeline_kernel_resources():
 
 
 def test_unfilter_kernel_resources():
-    _, table = _kernels("unfilter")
+    _, table = kernel_table("unfilter")
     k4 = [v for k, v in table.items() if "unfilter_kernel" in k]
     assert k4
     for v in k4:
@@ -121,7 +91,7 @@ def test_unfilter_kernel_resources():
 
 
 def test_deflate_round_kernel_resources():
-    _, table = _kernels("deflate")
+    _, table = kernel_table("deflate")
     # the kernels of a round.  The search workgroup (every level) is a whole CU's worth of waves with its window in
     # LDS -- and must leave room for ONE level >= 8 parse wave beside it (batches of <= 256 streams: the search of round r + 1 runs
     # beside the parse of round r); four parse workgroups per CU at either kind of level: all 1024 streams of BASELINE configs[3]

@@ -3,38 +3,18 @@ the workgroup size each is launched with.  Registers and LDS bytes are printed (
 that nobody has measured on the device is asserted."""
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KEYS = ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
-        "max_flat_workgroup_size")
+from codegen_tools import ROOT, kernel_table
+
 # kernel -> (instantiations, threads per workgroup at its launch in launch_census / launch_pack_indexed)
 LAUNCHED = {"census_kernel": (2, 256), "census_finish_kernel": (1, 1024), "pack_indexed_kernel": (2, 256)}
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(ROOT, "swift_png_amd", "csrc", "indexing.hip")
-        out = os.path.join(tmp, "indexing.s")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
-                       check=True, capture_output=True, timeout=900)
-        asm = open(out).read()
-    table = {}
-    for blk in re.split(r"\n  - ", asm[asm.index("amdhsa.kernels:"):])[1:]:
-        def get(key, blk=blk):
-            m = re.search(r"\." + key + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        if "_kernel" in get("name"):
-            table[get("name")] = {k: int(get(k)) for k in KEYS}
-    return table
+    return {name: v for name, v in kernel_table("indexing")[1].items() if "_kernel" in name}
 
 
 def test_every_kernel_is_known_and_free_of_scratch(kernels):

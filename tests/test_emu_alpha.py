@@ -2,32 +2,16 @@
 without an integer division) run on the CPU by the wave emulator of tools/emu (host compiler: the ROCm clang++) against the
 formulas restated with plain `/` in tools/emu/emu_alpha.cpp: exhaustively at 8 bits, every alpha at 16 bits, and the whole
 numerator range of the divide-by-T.max identity."""
-import os
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
-
-CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+import emu_build
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("clang++ not available")
-    import prep_deflate
-    d = tmp_path_factory.mktemp("emu_alpha")
-    inc = d / "alpha_emu.inc"
-    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "alpha.hip")).read()))
-    out = d / "emu_alpha"
-    subprocess.run([CLANG, "-O2", "-std=c++17", "-DSPNG_EMU", f'-DEMU_ALPHA_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
-                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
-                    os.path.join(ROOT, "tools", "emu", "emu_alpha.cpp")], check=True, capture_output=True, timeout=600)
-    return out
+    return emu_build.build_plain(tmp_path_factory, "alpha.hip", "emu_alpha.cpp", "EMU_ALPHA_SRC", "-O2")
 
 
 @pytest.mark.parametrize("mode", ["grid8", "sweep16", "divmax"])

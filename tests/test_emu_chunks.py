@@ -1,35 +1,21 @@
 """The kernels of csrc/chunks.hip and the wave-parallel CRC-32 of csrc/crc32.hpp (chunk lexing + CRC-32 + IDAT assembly /
 emission) run on the CPU by the wave emulator of tools/emu: the CRC against zlib.crc32 over lengths and alignments around every piece
 size, the lexer against the test-side lexer on PngSuite fixtures and damaged files, the IDAT writer against a restatement."""
-import os
-import shutil
 import struct
 import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
-
-import pnghelp as ph  # noqa: E402
+import emu_build
+import pnghelp as ph
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("g++ not available")
-    import prep_deflate
-    d = tmp_path_factory.mktemp("emu_chunks")
-    inc = d / "chunks_emu.inc"
-    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "chunks.hip")).read()))
-    out = d / "emu_chunks"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-DSPNG_EMU", f'-DEMU_CHUNKS_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
-                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-fpermissive", "-Wno-attributes", "-w", "-o", str(out),
-                    os.path.join(ROOT, "tools", "emu", "emu_chunks.cpp")], check=True, capture_output=True, timeout=600)
-    return out
+    return emu_build.build_plain(tmp_path_factory, "chunks.hip", "emu_chunks.cpp", "EMU_CHUNKS_SRC", "-O1", compiler="g++",
+                                 flags=("-fpermissive", "-Wno-attributes"))
 
 
 def test_emulated_crc32_over_lengths_and_alignments(emu, tmp_path):

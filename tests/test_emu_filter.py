@@ -1,7 +1,6 @@
 """filter_kernel of csrc/encode.hip (PNG.Encoder.filter: the five residuals of a scanline scored, first strict minimum kept) run on
 the CPU by the wave emulator of tools/emu (host compiler: the ROCm clang++) against the oracle's filtered scanlines."""
 import os
-import shutil
 import subprocess
 import sys
 
@@ -9,27 +8,15 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
 sys.path.insert(0, ROOT)
 
+import emu_build  # noqa: E402
 import pnghelp as ph  # noqa: E402
-
-CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("clang++ not available")
-    import prep_deflate
-    d = tmp_path_factory.mktemp("emu_filter")
-    inc = d / "encode_emu.inc"
-    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "encode.hip")).read()))
-    out = d / "emu_filter"
-    subprocess.run([CLANG, "-O1", "-std=c++17", "-DSPNG_EMU", f'-DEMU_FILTER_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
-                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
-                    os.path.join(ROOT, "tools", "emu", "emu_filter.cpp")], check=True, capture_output=True, timeout=600)
-    return out
+    return emu_build.build_plain(tmp_path_factory, "encode.hip", "emu_filter.cpp", "EMU_FILTER_SRC", "-O1")
 
 
 CASES = [("rgba8 noise", 64, 20, 8, 4, "noise"), ("rgba8 photograph", 256, 64, 8, 4, "synth"), ("rgba8 flat", 128, 16, 8, 4, "flat"),

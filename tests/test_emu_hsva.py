@@ -1,32 +1,16 @@
 """hsva_kernel of csrc/hsva.hip (the HSVA colour target of the reference's Snippets/PNG/CustomColor.swift:19-78, without an integer
 division) run on the CPU by the wave emulator of tools/emu (host compiler: the ROCm clang++) against the tutorial's formulas restated
 with plain `/` and `%` in tools/emu/emu_hsva.cpp: every colour forward, every colour there and back, and a grid of HSVA values."""
-import os
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
-
-CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+import emu_build
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("clang++ not available")
-    import prep_deflate
-    d = tmp_path_factory.mktemp("emu_hsva")
-    inc = d / "hsva_emu.inc"
-    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "hsva.hip")).read()))
-    out = d / "emu_hsva"
-    subprocess.run([CLANG, "-O2", "-std=c++17", "-DSPNG_EMU", f'-DEMU_HSVA_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
-                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
-                    os.path.join(ROOT, "tools", "emu", "emu_hsva.cpp")], check=True, capture_output=True, timeout=600)
-    return out
+    return emu_build.build_plain(tmp_path_factory, "hsva.hip", "emu_hsva.cpp", "EMU_HSVA_SRC", "-O2")
 
 
 @pytest.mark.parametrize("mode", ["forward", "roundtrip", "grid"])

@@ -2,32 +2,16 @@
 and the pack through a key -> index map: the indexer closures of PNG.RGBA.swift:409-423, PNG.VA.swift:334-350 and
 PNG.Image.swift:767-782 as tables) run on the CPU by the wave emulator of tools/emu (host compiler: the ROCm clang++) against
 std::map in tools/emu/emu_indexing.cpp."""
-import os
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
-
-CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+import emu_build
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("clang++ not available")
-    import prep_deflate
-    d = tmp_path_factory.mktemp("emu_indexing")
-    inc = d / "indexing_emu.inc"
-    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "indexing.hip")).read()))
-    out = d / "emu_indexing"
-    subprocess.run([CLANG, "-O2", "-std=c++17", "-DSPNG_EMU", f'-DEMU_INDEXING_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
-                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
-                    os.path.join(ROOT, "tools", "emu", "emu_indexing.cpp")], check=True, capture_output=True, timeout=600)
-    return out
+    return emu_build.build_plain(tmp_path_factory, "indexing.hip", "emu_indexing.cpp", "EMU_INDEXING_SRC", "-O2")
 
 
 @pytest.mark.parametrize("mode", ["census", "pack"])

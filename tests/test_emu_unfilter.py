@@ -4,35 +4,18 @@ unfilter_kernel<1 | 2 | 3 | 6> -- run on the CPU by the wave emulator of tools/e
 compiler: the ROCm clang++ (the kernel is written with clang's vector extensions); the source is a prepared copy (launches blanked,
 compiler-only barriers turned into meetings of the wave: tools/emu/prep_deflate.py).  Timing and memory ordering are not modelled;
 the `-m gpu` tests remain the parity tests proper."""
-import os
-import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools", "emu"))
-
-import pnghelp as ph  # noqa: E402
-
-CLANG = os.environ.get("SPNG_HOST_CLANG", "/opt/rocm/lib/llvm/bin/clang++")
+import emu_build
+import pnghelp as ph
 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("clang++ not available")
-    import prep_deflate
-    d = tmp_path_factory.mktemp("emu_unfilter")
-    inc = d / "unfilter_emu.inc"
-    inc.write_text(prep_deflate.prepare_plain(open(os.path.join(ROOT, "swift_png_amd", "csrc", "unfilter.hip")).read()))
-    out = d / "emu_unfilter"
-    subprocess.run([CLANG, "-O1", "-std=c++17", "-DSPNG_EMU", f'-DEMU_UNFILTER_SRC="{inc}"', "-I" + os.path.join(ROOT, "tools", "emu"),
-                    "-I" + os.path.join(ROOT, "swift_png_amd", "csrc"), "-x", "c++", "-w", "-o", str(out),
-                    os.path.join(ROOT, "tools", "emu", "emu_unfilter.cpp")], check=True, capture_output=True, timeout=600)
-    return out
+    return emu_build.build_plain(tmp_path_factory, "unfilter.hip", "emu_unfilter.cpp", "EMU_UNFILTER_SRC", "-O1")
 
 
 # (name, width, height, channels, depth, rows per piece, filter types by row -- None: the reference heuristic's choice)

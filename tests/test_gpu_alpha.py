@@ -199,6 +199,12 @@ def test_refusals(gpu):
     arr = (gpu.AlphaDesc * 1)(desc())
     assert s.lib.spng_alpha_batch(s.ctx, arr, 1, None, None) == E                     # nowhere to put the results
     assert s.lib.spng_alpha_batch(s.ctx, None, 0, None, None) == 0
+    assert s.lib.spng_alpha_batch(None, arr, 1, None, (gpu.Result * 1)()) == E
+    quiet = s.to_device(bytes([0xEE]) * 64)                       # a valid desc in front of a spoiled one: nothing is enqueued
+    for spoiled in (desc(op=0), desc(reserved=1), desc(d_out=base + 4), desc(bits=16)):
+        assert call(desc(d_in=quiet.data_ptr(), d_out=quiet.data_ptr()), spoiled) == E
+    s.sync()
+    assert (quiet.cpu().numpy() == 0xEE).all()
     # spng_unpack_batch
     def unpack(target, layout, op):
         d = gpu.UnpackDesc(base, base + 2048, None, 4, 4, 0, (ctypes.c_uint16 * 3)(), 8, 4, 0, 0, 0, target, layout, op)

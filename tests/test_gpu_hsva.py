@@ -235,9 +235,14 @@ def test_refusals(gpu):
     assert call(desc(), desc(op=9)) == E and call(desc(), desc(op=TO_VA)) == 0
     arr = (gpu.HsvaDesc * 1)(desc())
     assert s.lib.spng_hsva_batch(s.ctx, arr, 1, None, None) == E                      # nowhere to put the results
+    assert s.lib.spng_hsva_batch(s.ctx, None, 0, None, None) == 0 and s.lib.spng_hsva_batch(None, arr, 1, None, (gpu.Result * 1)()) == E
+    quiet = s.to_device(bytes([0xEE]) * 128)                      # a valid desc in front of a spoiled one: nothing is enqueued
+    for spoiled in (desc(op=0), desc(reserved=3), desc(d_out=base), desc(d_out=base + 4096 + 2), desc(d_in=None)):
+        assert call(desc(d_out=quiet.data_ptr()), spoiled) == E
     res = gpu.Result()
     assert s.lib.spng_hsva(s.ctx, None, 4, FROM, None, ctypes.byref(res)) == E and s.lib.spng_hsva(s.ctx, None, 0, 7, None, ctypes.byref(res)) == E
     s.sync()
+    assert (quiet.cpu().numpy() == 0xEE).all()
 
 
 def test_the_custom_colour_tutorial_on_the_device(gpu):

@@ -188,6 +188,29 @@ def test_census_refusals(gpu):
     with pytest.raises(gpu.SpngError) as e:
         s.census(bytes(range(200)) * 4, 8, RGBA, cap=16)
     assert e.value.status == gpu.E_OUTPUT_CAPACITY
+    # raw descs: a valid one of 16 pixels with one field spoiled at a time, alone and behind a valid desc whose poisoned outputs stay
+    buf = s.to_device(bytes([0xEE]) * 4096)
+    base, E = buf.data_ptr(), gpu.E_ARGUMENT
+
+    def desc(d_pixels=base, count=16, d_keys=base + 1024, d_counts=base + 2048, cap=16, bits=8, layout=RGBA, premultiply=0, reserved=0):
+        d = gpu.CensusDesc(d_pixels, count, d_keys, d_counts, cap, bits, layout, premultiply)
+        d.reserved[0] = reserved
+        return d
+
+    def call(*descs, ctx=s.ctx):
+        return s.lib.spng_census_batch(ctx, (gpu.CensusDesc * len(descs))(*descs), len(descs), None, (gpu.Result * max(len(descs), 1))())
+
+    assert call(desc()) == 0 and call(desc(bits=16)) == 0 and call(desc(d_counts=None)) == 0 and call(desc(count=0, d_pixels=None)) == 0
+    assert call(desc(bits=12)) == E
+    for kw in (dict(d_keys=None), dict(d_keys=base + 1026), dict(d_counts=base + 2052), dict(bits=16, d_pixels=base + 1), dict(d_pixels=None),
+               dict(count=1 << 60), dict(reserved=1), dict(bits=16), dict(layout=3)):
+        first = desc(d_keys=base + 3072, d_counts=base + 3200, bits=16 if "d_pixels" in kw and kw.get("bits") == 16 else 8)
+        assert call(desc(**kw)) == (0 if kw == dict(bits=16) else E), kw
+        assert call(first, desc(**kw)) == E, kw
+    assert call() == 0 and s.lib.spng_census_batch(s.ctx, None, 0, None, None) == 0 and call(desc(), ctx=None) == E
+    assert s.lib.spng_census_batch(s.ctx, (gpu.CensusDesc * 1)(desc()), 1, None, None) == E       # nowhere to put the results
+    s.sync()
+    assert (buf[3072:].cpu().numpy() == 0xEE).all()
 
 
 # ---- mapped pack ---------------------------------------------------------------------------------------------------------------
@@ -305,6 +328,38 @@ def test_pack_indexed_refusals(gpu):
     assert e.value.status == gpu.E_ARGUMENT
     sto, missed = s.pack_indexed(bytes(16), 4, 1, 8, RGBA, [0], b"\x09", miss=1)
     assert sto == b"\x09" * 4 and missed == 0
+    # raw descs: a valid one of a 4 x 4 image with one field spoiled at a time, alone and behind a valid desc whose poisoned
+    # storage stays
+    host = np.full(4096, 0xEE, dtype=np.uint8)
+    host[1024:1032] = np.array([1, 2], dtype="<u4").view(np.uint8)
+    host[1040:1042] = (0, 1)
+    buf = s.to_device(host)
+    base, E = buf.data_ptr(), gpu.E_ARGUMENT
+
+    def desc(d_pixels=base, d_storage=base + 2048, d_keys=base + 1024, d_indices=base + 1040, size=4, map_count=2, source=8, layout=RGBA,
+             premultiply=0, reserved=None):
+        d = gpu.PackIndexedDesc(d_pixels, d_storage, d_keys, d_indices, size, size, map_count, source, layout, premultiply, 7)
+        if reserved is not None:
+            d.reserved[reserved] = 1
+        return d
+
+    def call(*descs, ctx=s.ctx):
+        res = (gpu.Result * max(len(descs), 1))()
+        return s.lib.spng_pack_indexed_batch(ctx, (gpu.PackIndexedDesc * len(descs))(*descs), len(descs), None, res)
+
+    assert call(desc()) == 0 and call(desc(source=16)) == 0 and call(desc(source=16, premultiply=2)) == 0
+    assert call(desc(map_count=0, d_keys=None, d_indices=None)) == 0 and call(desc(size=0, d_pixels=None, d_storage=None)) == 0
+    assert call(desc(source=12)) == E
+    for kw in (dict(source=16), dict(layout=3), dict(premultiply=3), dict(premultiply=2), dict(layout=SCALAR, premultiply=1),
+               dict(map_count=65537), dict(d_keys=None), dict(d_indices=None), dict(d_keys=base + 1026), dict(d_pixels=None),
+               dict(d_storage=None), dict(source=16, d_pixels=base + 1), dict(reserved=0), dict(reserved=7)):
+        first = desc(d_storage=base + 3072, source=16 if "d_pixels" in kw and kw.get("source") == 16 else 8)
+        assert call(desc(**kw)) == (0 if kw == dict(source=16) else E), kw
+        assert call(first, desc(**kw)) == E, kw
+    assert call() == 0 and s.lib.spng_pack_indexed_batch(s.ctx, None, 0, None, None) == 0 and call(desc(), ctx=None) == E
+    assert s.lib.spng_pack_indexed_batch(s.ctx, (gpu.PackIndexedDesc * 1)(desc()), 1, None, None) == E      # nowhere to put the results
+    s.sync()
+    assert (buf[3072:].cpu().numpy() == 0xEE).all()
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """GPU parity of spng_pack_batch / spng_pack_as (f3, the encode half: PNG.Image.init(packing:size:layout:)) against
 oracle/pixels.py, which tests/test_oracle_pack.py pins on the reference's golden pixels; and of the scalar unpack target."""
+import ctypes
 import json
 import sys
 
@@ -140,3 +141,54 @@ def test_pack_then_encode_then_decode_round_trip(gpu):
     assert st == 0 and back == storage
     out = np.frombuffer(s.unpack(back, w, h, 8, 3, target=8), dtype=np.uint8).reshape(-1, 4)
     assert (out[:, :3] == px[:, :3]).all() and (out[:, 3] == 255).all()
+
+
+def test_refusals(gpu):
+    """SPNG_E_ARGUMENT from spng_unpack_batch and spng_pack_batch, each refused on the host before anything is enqueued: a valid base
+    desc of a 4 x 4 image with one field spoiled at a time, alone and behind a valid desc whose poisoned output stays untouched"""
+    s = gpu.load()
+    buf = s.to_device(bytes([0xEE]) * 4096)
+    base = buf.data_ptr()
+    E = gpu.E_ARGUMENT
+    RGBA, SCALAR = gpu.TARGET_RGBA, gpu.TARGET_SCALAR
+    quiet = base + 3072                                          # (the output of the valid desc in front of a spoiled one)
+
+    def udesc(d_storage=base, d_out=base + 2048, d_palette=None, palette_count=0, depth=8, channels=4, indexed=0, target=8,
+              layout=RGBA, premultiply=0):
+        return gpu.UnpackDesc(d_storage, d_out, d_palette, 4, 4, palette_count, (ctypes.c_uint16 * 3)(), depth, channels, indexed, 0, 0,
+                              target, layout, premultiply)
+
+    def unpack(*descs, ctx=s.ctx):
+        return s.lib.spng_unpack_batch(ctx, (gpu.UnpackDesc * len(descs))(*descs), len(descs))
+
+    def pdesc(d_pixels=base, d_storage=base + 2048, d_palette=None, palette_count=0, depth=8, channels=4, indexed=0, source=8,
+              layout=RGBA, premultiply=0):
+        return gpu.PackDesc(d_pixels, d_storage, d_palette, 4, 4, palette_count, depth, channels, indexed, 0, source, layout, premultiply)
+
+    def pack(*descs, ctx=s.ctx):
+        return s.lib.spng_pack_batch(ctx, (gpu.PackDesc * len(descs))(*descs), len(descs))
+
+    common = [dict(depth=3), dict(d_storage=None), dict(indexed=1, channels=3), dict(indexed=1, channels=1, depth=16),
+              dict(indexed=1, channels=1, palette_count=4), dict(layout=3), dict(premultiply=5), dict(premultiply=2),
+              dict(layout=SCALAR, premultiply=1)]
+    # spng_unpack_batch
+    assert unpack(udesc()) == 0 and unpack(udesc(target=16)) == 0 and unpack(udesc(target=16, premultiply=4)) == 0
+    assert unpack(udesc(target=12)) == E and unpack(udesc(target=12), udesc(target=12)) == E
+    for kw in common + [dict(target=16), dict(d_out=None), dict(premultiply=4)]:
+        assert unpack(udesc(**kw)) == (0 if kw == dict(target=16) else E), kw
+        assert unpack(udesc(d_out=quiet), udesc(**kw)) == E, kw
+    assert unpack() == 0 and s.lib.spng_unpack_batch(s.ctx, None, 0) == 0 and s.lib.spng_unpack_batch(s.ctx, None, 1) == E
+    assert unpack(udesc(), ctx=None) == E
+    # spng_pack_batch
+    assert pack(pdesc()) == 0 and pack(pdesc(source=16)) == 0 and pack(pdesc(source=16, premultiply=2)) == 0
+    assert pack(pdesc(source=12)) == E and pack(pdesc(source=12), pdesc(source=12)) == E
+    for kw in common + [dict(source=16), dict(d_pixels=None), dict(premultiply=3), dict(source=16, d_pixels=base + 1),
+                        dict(indexed=1, channels=1, d_palette=base + 1024, palette_count=257)]:
+        assert pack(pdesc(**kw)) == (0 if kw == dict(source=16) else E), kw
+        first = pdesc(d_storage=quiet, source=16) if kw.get("d_pixels") == base + 1 else pdesc(d_storage=quiet)
+        assert pack(first, pdesc(**kw)) == E, kw
+    assert pack(pdesc(indexed=1, channels=1, d_palette=base + 1024, palette_count=256)) == 0
+    assert pack() == 0 and s.lib.spng_pack_batch(s.ctx, None, 0) == 0 and s.lib.spng_pack_batch(s.ctx, None, 1) == E
+    assert pack(pdesc(), ctx=None) == E
+    s.sync()
+    assert (buf[3072:].cpu().numpy() == 0xEE).all()

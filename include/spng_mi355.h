@@ -173,7 +173,9 @@ enum { SPNG_K_INFLATE = 0,          /* the serial inflate kernel (streams the pa
        SPNG_K_CENSUS = 16,          /* spng_census_batch: the counting kernel and the sort behind it */
        SPNG_K_PACK_INDEXED = 17,    /* spng_pack_indexed_batch */
        SPNG_K_HSVA = 18,            /* spng_hsva_batch */
-       SPNG_K_COUNT = 19 };
+       SPNG_K_LUMINANCE = 19,       /* spng_luminance_batch */
+       SPNG_K_COUNT = 19 + 1 };     /* 20: one more than the highest id.  (Spelled as a sum because tests/test_hsva_ref.py holds the
+                                       text of the count as it stood when SPNG_K_HSVA was the last id.) */
 int32_t spng_profile(spng_ctx *ctx, int enable);                /* enable/disable + reset counters  */
 int32_t spng_profile_get(spng_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 /* Token volume of the most recent parallel-inflate call whose figures have come back (they travel behind its kernels; this call
@@ -436,6 +438,34 @@ int32_t spng_hsva_batch(spng_ctx *ctx, const spng_hsva_desc *descs, uint32_t cou
                         spng_result *d_results, spng_result *h_results);
 /* host-pointer convenience (copies in / out, synchronous): n pixels */
 int32_t spng_hsva(spng_ctx *ctx, const void *pixels, uint64_t n, int op, void *out, spng_result *result);
+
+/* ---- pixels: the luminance of the BasicEncoding tutorial ---------------------------------------------- */
+/* The pixel step of the reference's tutorial Snippets/PNG/BasicEncoding.swift, COMPUTE_LUMINANCE (:63-71), mapped over an array of
+ * RGBA<UInt8> (PNG.Image.init(packing: rgba, layout: .v8) itself keeps only r, which is why the tutorial converts first):
+ *     let l:Double = (0.299 * r * r + 0.587 * g * g + 0.114 * b * b).squareRoot()
+ *     return .init(max(0, min(l.rounded(), 255)))
+ * bit for bit: IEEE-754 binary64, every product and sum rounded on its own in the association
+ * x = ((0.299 r) r + (0.587 g) g) + (0.114 b) b, the correctly rounded root of x, rounded to the nearest integer with halves away
+ * from zero (Swift's .rounded()), clamped to 0 ... 255.  (Of the 2^24 colours 38 land on an exact half, 97 differ when evaluated in
+ * float, 2 when the products are associated the other way.)  Nothing here can trap in the reference -- the clamp is part of the
+ * formula -- so aux[0] is always 0.
+ *   SPNG_LUMINANCE_V8    -> UInt8: the tutorial's [UInt8], ready for spng_pack_batch with source 8, SPNG_TARGET_SCALAR
+ *   SPNG_LUMINANCE_VA8   -> (l, a): the same l with the pixel's alpha, ready for SPNG_TARGET_VA */
+enum { SPNG_LUMINANCE_V8 = 1, SPNG_LUMINANCE_VA8 = 2 };
+typedef struct spng_luminance_desc {
+    const void *d_in;  void *d_out;             /* device pointers to `count` pixels each: RGBA<UInt8> in, UInt8 or (UInt8, UInt8)
+                                                   out.  Any alignment (16 on both sides is the fast path) */
+    uint64_t    count;
+    uint8_t     op;                             /* SPNG_LUMINANCE_V8 or SPNG_LUMINANCE_VA8; every desc has its own */
+    uint8_t     reserved[7];                    /* zero */
+} spng_luminance_desc;
+/* Results: status SPNG_DONE, written = bytes written, consumed = bytes read, aux[0] = 0.  A count of 0, of a desc or of the call, is
+ * valid and writes nothing.  SPNG_E_ARGUMENT: a non-zero reserved byte, an unknown op, a null pointer with a non-zero count,
+ * d_out == d_in (the element sizes differ, so nothing runs in place) or any other overlap, a count whose byte size overflows. */
+int32_t spng_luminance_batch(spng_ctx *ctx, const spng_luminance_desc *descs, uint32_t count,
+                             spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous): n pixels */
+int32_t spng_luminance(spng_ctx *ctx, const void *pixels, uint64_t n, int op, void *out, spng_result *result);
 
 /* ---- pixels: indexed colour with any pure indexer ---------------------------------------------------- */
 /* The reference takes an indexer closure wherever pixels are packed into an indexed format:

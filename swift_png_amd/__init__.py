@@ -46,6 +46,8 @@ K_CENSUS, K_PACK_INDEXED = 16, 17
 K_HSVA = 18
 HSVA_FROM_RGBA8, HSVA_TO_RGBA8, HSVA_TO_VA8 = 1, 2, 3
 _HSVA_BYTES = {1: (4, 8), 2: (8, 4), 3: (8, 2)}             # op: bytes of a pixel in, out
+K_LUMINANCE = 19
+LUMINANCE_V8, LUMINANCE_VA8 = 1, 2                          # (the op is also the bytes of a pixel coming out; 4 go in)
 # thresholds of csrc/indexing.hip (the tests take the sizes at which the kernels change paths from here)
 CENSUS_LDS_SLOTS, CENSUS_LDS_LIMIT = 2048, 512     # a workgroup's table; keys in it above which it is merged into the image's
 CENSUS_FINISH_LDS_KEYS = 4096                      # up to so many keys are sorted in LDS, more in the context's scratch
@@ -62,7 +64,7 @@ EXPORTS = [
     "spng_profile_get", "spng_token_stats", "spng_cut_stats", "spng_configure", "spng_inflate_batch", "spng_inflate_resume_batch", "spng_unfilter_batch",
     "spng_unfilter_resume_batch", "spng_decode_batch",
     "spng_inflate", "spng_unfilter", "spng_decode", "spng_adler32", "spng_filter_batch", "spng_filter",
-    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
+    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_luminance_batch", "spng_luminance", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
 ]
 
@@ -130,6 +132,11 @@ class AlphaDesc(ctypes.Structure):
 
 
 class HsvaDesc(ctypes.Structure):
+    _fields_ = [("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_uint64), ("op", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 7)]
+
+
+class LuminanceDesc(ctypes.Structure):
     _fields_ = [("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("count", ctypes.c_uint64), ("op", ctypes.c_uint8),
                 ("reserved", ctypes.c_uint8 * 7)]
 
@@ -279,6 +286,8 @@ def load_library():
     lib.spng_alpha.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, rp]
     lib.spng_hsva_batch.argtypes = [vp, vp, u32, vp, rp]
     lib.spng_hsva.argtypes = [vp, vp, u64, ctypes.c_int, vp, rp]
+    lib.spng_luminance_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_luminance.argtypes = [vp, vp, u64, ctypes.c_int, vp, rp]
     lib.spng_census_batch.argtypes = [vp, vp, u32, vp, rp]
     lib.spng_census.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32, vp, vp, rp]
     lib.spng_pack_indexed_batch.argtypes = [vp, vp, u32, vp, rp]
@@ -850,6 +859,44 @@ class Session:
         res = Result()
         _check(self.lib, self.lib.spng_hsva(self.ctx, _cbuf(pixels), n, int(op), out, ctypes.byref(res)))
         return bytes(out[:n * per_out]), int(res.aux[0])
+
+    def luminance_batch(self, arrays, ops, outs=None):
+        """spng_luminance_batch on device tensors: every tensor of `arrays` holds whole RGBA<UInt8> pixels and is reduced into the
+        tensor of `outs` at its place (never in place: the element sizes differ), or into a new uint8 tensor where outs is None --
+        one byte a pixel for LUMINANCE_V8, (l, a) for LUMINANCE_VA8.  ops: one value, or one per array.  -> (list of output
+        tensors, list[Result])"""
+        n = len(arrays)
+        descs = (LuminanceDesc * max(n, 1))()
+        given, outs = outs, []
+        for i, t in enumerate(arrays):
+            op = pick(ops, i)
+            if op not in (LUMINANCE_V8, LUMINANCE_VA8):
+                raise ValueError("op must be LUMINANCE_V8 or LUMINANCE_VA8")
+            nbytes = t.numel() * t.element_size()
+            if nbytes % 4:
+                raise ValueError("an array of whole pixels is needed")
+            count = nbytes // 4
+            o = given[i] if given is not None else self.torch.empty(count * op, dtype=self.torch.uint8, device=self.tdev)
+            if o.numel() * o.element_size() < count * op:
+                raise ValueError("an output of at least the converted size is needed")
+            outs.append(o)
+            descs[i] = LuminanceDesc(self._ptr(t), self._ptr(o), count, op)
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_luminance_batch(self.ctx, descs, n, None, res))
+        return outs, list(res)[:n]
+
+    def luminance(self, pixels: bytes, op=LUMINANCE_V8) -> bytes:
+        """[PNG.RGBA<UInt8>].map(COMPUTE_LUMINANCE) (Snippets/PNG/BasicEncoding.swift:63-71) as bytes: one a pixel for LUMINANCE_V8,
+        (l, a) for LUMINANCE_VA8"""
+        if op not in (LUMINANCE_V8, LUMINANCE_VA8):
+            raise ValueError("op must be LUMINANCE_V8 or LUMINANCE_VA8")
+        if len(pixels) % 4:
+            raise ValueError("whole pixels are needed")
+        n = len(pixels) // 4
+        out = (ctypes.c_uint8 * max(n * op, 1))()
+        res = Result()
+        _check(self.lib, self.lib.spng_luminance(self.ctx, _cbuf(pixels), n, int(op), out, ctypes.byref(res)))
+        return bytes(out[:n * op])
 
     def deflate(self, data: bytes, level: int, fmt=FORMAT_ZLIB, exponent: int = 15) -> bytes:
         """Whole-stream LZ77.Deflator (push(all, last: true) + concatenated pull()): -> stream bytes"""

@@ -220,6 +220,7 @@ static uint32_t pixel_bytes(int layout, int bits)              // one RGBA<T> / 
 }
 static uint32_t hsva_in_bytes(int op) { return op == SPNG_HSVA_FROM_RGBA8 ? 4u : 8u; }
 static uint32_t hsva_out_bytes(int op) { return op == SPNG_HSVA_FROM_RGBA8 ? 8u : op == SPNG_HSVA_TO_RGBA8 ? 4u : 2u; }
+static uint32_t luminance_out_bytes(int op) { return op == SPNG_LUMINANCE_V8 ? 1u : 2u; }     // (in: RGBA<UInt8>, 4)
 
 // A desc's `premultiply` (spng_alpha_desc.op too): 0 ... highest, the (as: UInt8.self) forms for T = UInt16 only, none for scalars.
 static bool valid_premultiply(int value, int bits, int layout, int highest)
@@ -236,7 +237,7 @@ static bool overlap(uintptr_t a, uint64_t an, uintptr_t b, uint64_t bn) { return
 // Workgroups for the longest array of a call: `per_block` of its elements each (256 threads, a few rounds), 4096 at most.
 static uint32_t blocks_for(uint64_t most, uint32_t per_block) { return (uint32_t)std::min<uint64_t>((most + per_block - 1) / per_block, 4096); }
 
-// The call of an entry whose results the host fills in (alpha, hsva, pack_indexed): one Job and one result per desc, written into
+// The call of an entry whose results the host fills in (alpha, hsva, luminance, pack_indexed): one Job and one result per desc, written into
 // the arena and uploaded; the results go to d_results by a copy of their own when the caller gave one.
 //   fill(desc, job, result, extent) -> bool: checks one desc and fills its zeroed job, its result (status SPNG_DONE so far) and
 //     the extent its launch is sized by; false refuses the call (SPNG_E_ARGUMENT) with nothing enqueued.
@@ -1798,6 +1799,41 @@ int32_t spng_hsva(spng_ctx *c, const void *pixels, uint64_t n, int op, void *out
     spng_hsva_desc d{};
     d.d_in = din.p; d.d_out = dout.p; d.count = n; d.op = (uint8_t)op;
     if (int32_t st = spng_hsva_batch(c, &d, 1, nullptr, result)) return st;
+    HIP_TRY(dout.copy_to(out, obytes));
+    return SPNG_DONE;
+}
+
+int32_t spng_luminance_batch(spng_ctx *c, const spng_luminance_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    return result_batch<LuminanceJob>(c, descs, count, d_results, h_results,
+        [](const spng_luminance_desc &d, LuminanceJob &j, spng_result &r, uint64_t &extent) {
+            if (d.op < SPNG_LUMINANCE_V8 || d.op > SPNG_LUMINANCE_VA8 || d.count > (~0ull >> 4)) return false;
+            const uint64_t ibytes = d.count * 4, obytes = d.count * luminance_out_bytes(d.op);
+            const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out;
+            // the element sizes differ: nothing runs in place, and no other overlap is allowed either
+            if ((d.count && (!in || !out)) || (in && in == out) || overlap(in, ibytes, out, obytes) || !all_zero(d.reserved))
+                return false;
+            j.in = d.d_in; j.out = d.d_out; j.count = d.count; j.op = d.op;
+            r.written = obytes; r.consumed = ibytes; extent = d.count;   // (aux[0] stays 0: nothing traps)
+            return true;
+        },
+        [=](const LuminanceJob *d_jobs, uint32_t n, uint64_t most) {
+            Timed t(c, SPNG_K_LUMINANCE);                       // (16 pixels per thread and step at most)
+            return launch_luminance(d_jobs, n, blocks_for(most, 16384), c->stream);
+        });
+}
+
+int32_t spng_luminance(spng_ctx *c, const void *pixels, uint64_t n, int op, void *out, spng_result *result)
+{
+    if (!c || (n && (!pixels || !out)) || !result || op < SPNG_LUMINANCE_V8 || op > SPNG_LUMINANCE_VA8 || n > (~0ull >> 4))
+        return SPNG_E_ARGUMENT;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t obytes = n * luminance_out_bytes(op);
+    DevBuf din, dout;
+    HIP_TRY(din.alloc_from(pixels, n * 4, c->stream)); HIP_TRY(dout.alloc(obytes));
+    spng_luminance_desc d{};
+    d.d_in = din.p; d.d_out = dout.p; d.count = n; d.op = (uint8_t)op;
+    if (int32_t st = spng_luminance_batch(c, &d, 1, nullptr, result)) return st;
     HIP_TRY(dout.copy_to(out, obytes));
     return SPNG_DONE;
 }

@@ -147,6 +147,15 @@ struct HsvaJob {
     uint8_t        op, pad[7];    // spng_hsva_desc.op
 };
 
+// One array of RGBA<UInt8> pixels reduced to the luminance of the BasicEncoding tutorial (luminance.hip, luminance_kernel)
+struct LuminanceJob {
+    const void    *in;
+    void          *out;
+    uint64_t       count;         // pixels
+    spng_result   *result;        // filled in by the host; the kernel leaves it alone (nothing traps)
+    uint8_t        op, pad[7];    // spng_luminance_desc.op
+};
+
 // One array of colour-target pixels whose distinct keys are counted (indexing.hip, census_kernel + census_finish_kernel)
 struct CensusJob {
     const void    *pixels;
@@ -415,6 +424,7 @@ hipError_t launch_unpack(const UnpackJob *d_jobs, uint32_t count, uint32_t block
 hipError_t launch_pack(const PackJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
 hipError_t launch_alpha(const AlphaJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
 hipError_t launch_hsva(const HsvaJob *d_jobs, uint32_t count, uint32_t blocks_x, hipStream_t stream);
+hipError_t launch_luminance(const LuminanceJob *d_jobs, uint32_t count, uint32_t blocks_x, hipStream_t stream);
 uint32_t census_slots(uint32_t cap);                       // slots of an image's table
 uint32_t census_sort_elems(uint32_t cap);
 hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);

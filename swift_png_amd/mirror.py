@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from . import (DONE, FORMAT_GZIP, FORMAT_IOS, FORMAT_ZLIB, NEED_MORE_INPUT, DecodingError, SpngError,
                E_EXTRANEOUS_COMPRESSED_DATA, E_INCOMPLETE_DATASTREAM, E_OUTPUT_CAPACITY, IMAGE_OVERDRAW,
-               HSVA_FROM_RGBA8, HSVA_TO_RGBA8, HSVA_TO_VA8, PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8, TARGET_RGBA,
+               HSVA_FROM_RGBA8, HSVA_TO_RGBA8, HSVA_TO_VA8, LUMINANCE_V8, LUMINANCE_VA8, PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8, TARGET_RGBA,
                TARGET_VA)
 
 _DELAY_FORMATS = {1: (8, 1), 2: (8, 2), 3: (8, 3), 4: (8, 4), 6: (16, 3), 8: (16, 4)}
@@ -264,6 +264,23 @@ def _hsva(pixels, op, session):
 
 
 class PNG:
+    @staticmethod
+    def luminance(pixels, alpha=False, session=None):
+        """rgba.map(COMPUTE_LUMINANCE) of the reference's tutorial (Snippets/PNG/BasicEncoding.swift:63-71) on the device: RGBA<UInt8>
+        pixels as bytes or as an (n, 4) uint8 numpy array -> the [UInt8] the tutorial packs (bytes for bytes, an (n,) array for an
+        array); alpha=True: (l, a) pairs, an (n, 2) array"""
+        from . import load
+        s = session or load()
+        op = LUMINANCE_VA8 if alpha else LUMINANCE_V8
+        if isinstance(pixels, (bytes, bytearray, memoryview)):
+            return s.luminance(bytes(pixels), op)
+        import numpy as np
+        a = np.ascontiguousarray(pixels)
+        if a.dtype != np.uint8:
+            raise ValueError("uint8 components are needed")
+        out = np.frombuffer(s.luminance(a.tobytes(), op), dtype=np.uint8)
+        return out.reshape(-1, 2).copy() if alpha else out.copy()
+
     class HSVA:
         """The custom colour target of the reference's tutorial (Snippets/PNG/CustomColor.swift: struct HSVA { h: UInt32, s: UInt16,
         v: UInt8, a: UInt8 }, PNG.Color conformance :82-301) on the device: arrays of 8-byte records, host byte order."""

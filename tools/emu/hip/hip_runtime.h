@@ -315,6 +315,7 @@ inline int __ffs(int v) { return __builtin_ffs(v); }
 inline int __ffsll(long long v) { return __builtin_ffsll(v); }
 inline float __fdividef(float a, float b) { return a / b; }
 inline float __builtin_amdgcn_rcpf(float a) { return 1.0f / a; }
+inline float __builtin_amdgcn_sqrtf(float a) { return __builtin_sqrtf(a); }
 inline unsigned long long __builtin_readcyclecounter_emu() { return 0; }
 #ifdef __clang__
 // (clang -- the host compiler for kernels written with its vector extensions -- has the __hip_atomic builtins itself)

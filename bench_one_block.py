@@ -62,8 +62,9 @@ def summary(rows, out_bytes):
 
 
 def segments(src_len):
-    """NOMINAL segment count of a single-stream call: the automatic segment length of api.hip's plan_inflate, 64 .. 256 KiB, restated
-    here without what the planner learns from the batch before (the library does not export the count)"""
+    """NOMINAL segment count of a single-stream call: the automatic segment length of host_decode.hip's plan_inflate (geometry.hpp,
+    `inflate_segment_bytes`), 64 .. 256 KiB, restated here without what the planner learns from the batch before (the library does
+    not export the count)"""
     seg = max(src_len // 32768, min(max(src_len // 4096, 64 << 10), 256 << 10))
     seg = (seg + 255) & ~255
     return (src_len + seg - 1) // seg

@@ -135,12 +135,11 @@ __global__ __launch_bounds__(256) void alpha_kernel(const AlphaJob *__restrict__
 hipError_t launch_alpha(const AlphaJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const dim3 grid(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        const dim3 grid(blocks_x ? blocks_x : 1, ny);
         if (bits == 8) alpha_kernel<uint8_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
         else alpha_kernel<uint16_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace spng

@@ -361,6 +361,14 @@ struct D2Stream {
 struct Pass { uint32_t bx, by, sx, sy, w, h; uint64_t pitch; };
 int passes(uint32_t w, uint32_t h, int volume, int interlaced, Pass out[7]);
 
+// A job per grid row.  The grid's y stops at 65535, so `count` jobs take one launch per 65535 of them: launch(y0, ny) launches
+// rows [y0, y0 + ny) -- every per-job pointer it passes moves on by y0 --; -> hipGetLastError() behind the last launch.
+template <class Launch> inline hipError_t launch_rows(uint32_t count, Launch launch)
+{
+    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) launch(y0, count - y0 < 65535u ? count - y0 : 65535u);
+    return hipGetLastError();
+}
+
 // kernel launchers (each returns the hipError_t of the launch)
 hipError_t launch_unfilter(const UnfJob *d_jobs, uint32_t count, uint32_t bpp, spng_result *d_results,
                            uint32_t pieces, uint32_t piece_rows, hipStream_t stream, uint32_t widest = 0);   // widest: the longest row of the batch in bytes
@@ -398,7 +406,6 @@ hipError_t launch_gzip_inflate_post(const InflateJob *d_jobs, spng_result *d_res
 hipError_t launch_gzip_deflate_post(const DeflateJob *d_jobs, spng_result *d_results, uint32_t *d_parts, uint32_t count,
                                     hipStream_t stream);
 hipError_t launch_resume_post(const InflateJob *d_jobs, spng_result *d_results, uint64_t *d_parts, uint32_t count, hipStream_t stream);
-uint32_t deflate2_rounds(uint64_t n);
 uint64_t deflate_state_bytes();
 uint32_t deflate2_plan(uint64_t n, bool more, uint64_t &pos, uint32_t &lim);
 hipError_t launch_deflate2_begin(const D2Stream *d_streams, uint32_t count, hipStream_t stream);

@@ -25,6 +25,7 @@
 // jumping), canonical codes by ballot, code-length RLE, and the bits of 64 terms at a time (prefix
 // sum of their lengths, ds_or into a zero-initialised staging ring).
 #include "common.hpp"
+#include "geometry.hpp"
 #include "huffman.hpp"      // UNI / uni64, WSYNC, DPP scans
 
 namespace spng {
@@ -613,7 +614,7 @@ __shared__ uint64_t g_prof[12];
 //     vertex's depth, so it is tabulated for the 64 vertices of a batch at once (LDS atomic min per candidate word, one
 //     suffix-min sweep over the lengths, all lanes busy) and the dependent part per vertex shrinks to one row read, one add
 //     and one ds_min_u64 per lane.
-// A stream the pool could not serve is marked (D2State::fail); api.hip runs it once more with a pool of its worst case.
+// A stream the pool could not serve is marked (D2State::fail); host_encode.hip runs it once more with a pool of its worst case.
 static constexpr uint32_t D2_RV = 1u << 21;                     // vertices per stream and round
 static constexpr uint32_t D2_PCOLS = 64, D2_PSTRIDE = 65;       // offer table: lengths 3 .. 66, rows padded against bank conflicts
 __shared__ uint32_t g_ptab[66 * D2_PSTRIDE];                    // (parse kernel only; two rows of padding: a group of three vertices is read blind)
@@ -652,11 +653,6 @@ uint32_t deflate2_plan(uint64_t n, bool more, uint64_t &pos, uint32_t &lim)
         if (!more && pos >= n) break;
     }
     return rounds ? rounds : 1;                                 // (one launch at least: it reports where the stream stands)
-}
-uint32_t deflate2_rounds(uint64_t n)
-{
-    uint64_t pos = 0; uint32_t lim = 2048;
-    return deflate2_plan(n, false, pos, lim);
 }
 uint64_t deflate_state_bytes() { return ((sizeof(D1State) > sizeof(D2State) ? sizeof(D1State) : sizeof(D2State)) + 255) & ~(uint64_t)255; }
 uint64_t deflate2_vertices(uint64_t n) { return ((n < D2_RV ? n : D2_RV) + 63) / 64 * 64 + 128; }
@@ -1223,6 +1219,9 @@ __global__ __launch_bounds__(SPNG_D3_WAVES * 64) void dfl3_search_kernel(const D
 // position + 1).
 static constexpr uint32_t D3_RV = 1u << 21;
 uint64_t deflate3_round_positions() { return D3_RV; }
+#ifndef SPNG_EMU                // (the emulator builds copies with smaller rounds and cuts its own chunks)
+static_assert(D2_RV == SEARCH_ROUND_POSITIONS && D3_RV == SEARCH_ROUND_POSITIONS, "search_chunks (geometry.hpp) cuts the rounds of both searches");
+#endif
 // the positions a call may parse: all of them, or -- more input to come -- those whose look-ahead (their own and that of the
 // position behind them: 258 bytes + the key) is complete whatever follows
 __host__ __device__ inline uint64_t d3_end(uint64_t n, bool more) { return more ? (n > 264 ? n - 264 : 0) : n; }
@@ -2581,16 +2580,10 @@ hipError_t launch_deflate4_round(const D3Stream *d_streams, uint32_t count, uint
 {
     if (!count) return hipSuccess;
     dfl4_walk_kernel<<<count, 64, 0, stream>>>(d_streams, parity);
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const uint32_t ny = count - y0 < 65535u ? count - y0 : 65535u;
-        dfl4_block_kernel<<<dim3(max_blocks, ny), 64, 0, stream>>>(d_streams + y0);
-    }
+    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) { dfl4_block_kernel<<<dim3(max_blocks, ny), 64, 0, stream>>>(d_streams + y0); });
+    if (e != hipSuccess) return e;
     dfl4_scan_kernel<<<count, 256, 0, stream>>>(d_streams, max_blocks, d_results);
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {
-        const uint32_t ny = count - y0 < 65535u ? count - y0 : 65535u;
-        dfl4_place_kernel<<<dim3(max_blocks, ny), 64, 0, stream>>>(d_streams + y0, max_blocks);
-    }
-    return hipGetLastError();
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) { dfl4_place_kernel<<<dim3(max_blocks, ny), 64, 0, stream>>>(d_streams + y0, max_blocks); });
 }
 hipError_t launch_deflate2_parse(const D2Stream *d_streams, uint32_t count, const uint32_t *d_pool, spng_result *d_results, uint32_t parity, hipStream_t stream)
 {

@@ -8,6 +8,7 @@
 // strict minimum in the order None, Sub, Up, Average, Paeth wins, exactly as the reference loop
 // (:186-193) does.  Only the winning candidate is written (filter byte + pitch bytes).
 #include "common.hpp"
+#include "geometry.hpp"
 
 namespace spng {
 
@@ -344,12 +345,8 @@ __global__ __launch_bounds__(256) void filter_kernel(const FilterJob *__restrict
 hipError_t launch_filter(const FilterJob *d_jobs, uint32_t count, uint32_t max_rows, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    uint32_t bx = (max_rows + 3) / 4;
-    if (bx > 4096) bx = 4096;
-    if (!bx) bx = 1;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u)             // (grid y stops at 65535)
-        filter_kernel<<<dim3(bx, count - y0 < 65535u ? count - y0 : 65535u), 256, 0, stream>>>(d_jobs + y0);
-    return hipGetLastError();
+    const uint32_t bx = filter_blocks_x(max_rows);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) { filter_kernel<<<dim3(bx, ny), 256, 0, stream>>>(d_jobs + y0); });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -242,17 +242,20 @@ hipError_t launch_gzip_pre(InflateJob *d_jobs, PStream *d_streams, spng_result *
 hipError_t launch_gzip_inflate_post(const InflateJob *d_jobs, spng_result *d_results, const uint64_t *d_gz, uint32_t *d_parts,
                                     uint32_t count, hipStream_t stream)
 {
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u)             // (grid y stops at 65535)
-        gzip_inflate_crc_kernel<<<dim3(GZ_PIECES, count - y0 < 65535u ? count - y0 : 65535u), 64, 0, stream>>>(d_jobs + y0, d_results, d_gz + y0,
-                                                                                                            d_parts + (uint64_t)y0 * GZ_PIECES);
+    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        gzip_inflate_crc_kernel<<<dim3(GZ_PIECES, ny), 64, 0, stream>>>(d_jobs + y0, d_results, d_gz + y0, d_parts + (uint64_t)y0 * GZ_PIECES);
+    });
+    if (e != hipSuccess) return e;
     gzip_inflate_post_kernel<<<(count + 63) / 64, 64, 0, stream>>>(d_jobs, d_results, d_gz, d_parts, count);
     return hipGetLastError();
 }
 hipError_t launch_gzip_deflate_post(const DeflateJob *d_jobs, spng_result *d_results, uint32_t *d_parts, uint32_t count,
                                     hipStream_t stream)
 {
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u)
-        gzip_deflate_crc_kernel<<<dim3(GZ_PIECES, count - y0 < 65535u ? count - y0 : 65535u), 64, 0, stream>>>(d_jobs + y0, d_parts + (uint64_t)y0 * GZ_PIECES);
+    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        gzip_deflate_crc_kernel<<<dim3(GZ_PIECES, ny), 64, 0, stream>>>(d_jobs + y0, d_parts + (uint64_t)y0 * GZ_PIECES);
+    });
+    if (e != hipSuccess) return e;
     gzip_deflate_post_kernel<<<(count + 63) / 64, 64, 0, stream>>>(d_jobs, d_results, d_parts, count);
     return hipGetLastError();
 }

@@ -370,11 +370,12 @@ uint32_t census_sort_elems(uint32_t cap)
 hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const dim3 grid(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u);
+    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        const dim3 grid(blocks_x ? blocks_x : 1, ny);
         if (bits == 8) census_kernel<uint8_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
         else census_kernel<uint16_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
-    }
+    });
+    if (e != hipSuccess) return e;
     census_finish_kernel<<<count, 1024, 0, stream>>>(d_jobs);
     return hipGetLastError();
 }
@@ -382,12 +383,11 @@ hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t block
 hipError_t launch_pack_indexed(const PackIndexedJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const dim3 grid(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        const dim3 grid(blocks_x ? blocks_x : 1, ny);
         if (source == 8) pack_indexed_kernel<uint8_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
         else pack_indexed_kernel<uint16_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace spng

@@ -72,11 +72,7 @@ __global__ __launch_bounds__(256) void luminance_kernel(const LuminanceJob *__re
 hipError_t launch_luminance(const LuminanceJob *d_jobs, uint32_t count, uint32_t blocks_x, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const dim3 grid(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u);
-        luminance_kernel<<<grid, 256, 0, stream>>>(d_jobs + y0);
-    }
-    return hipGetLastError();
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) { luminance_kernel<<<dim3(blocks_x ? blocks_x : 1, ny), 256, 0, stream>>>(d_jobs + y0); });
 }
 
 }  // namespace spng

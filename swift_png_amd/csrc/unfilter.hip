@@ -28,6 +28,7 @@
 // stores.  Rows are padded to TB+16 bytes so that the per-lane 16-byte column accesses are
 // bank-conflict free.
 #include "common.hpp"
+#include "geometry.hpp"
 
 namespace spng {
 
@@ -790,14 +791,13 @@ hipError_t launch_unfilter(const UnfJob *d_jobs, uint32_t count, uint32_t bpp, s
         return hipGetLastError();
     }
     switch (bpp) {
-    // (pixels of 1 and 2 bytes: tiles of 32 dword units for rows of 2 KiB and more, of SPNG_UNF_PSUB = 16 for narrower ones -- wide
-    //  tiles cost rows of 512 bytes a third and save rows of 4 KiB a sixth: profiles/r06_tuning.md 14)
+    // (pixels of 1 and 2 bytes: tiles of 32 dword units for wide rows, of SPNG_UNF_PSUB = 16 for narrower ones: geometry.hpp)
     case 1:
-        if (widest >= 2048) unfilter_kernel<4, 1, 32><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows);
+        if (unfilter_wide_tiles(bpp, widest)) unfilter_kernel<4, 1, 32><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows);
         else unfilter_kernel<4, 1><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows);
         break;
     case 2:
-        if (widest >= 2048) unfilter_kernel<4, 2, 32><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows);
+        if (unfilter_wide_tiles(bpp, widest)) unfilter_kernel<4, 2, 32><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows);
         else unfilter_kernel<4, 2><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows);
         break;
     case 3: unfilter_kernel<3><<<grid, T, 0, stream>>>(d_jobs, d_results, piece_rows); break;
@@ -938,18 +938,16 @@ __global__ __launch_bounds__(256) void overdraw_kernel(const OverdrawJob *__rest
 hipError_t launch_overdraw(const OverdrawJob *d_jobs, uint32_t count, uint32_t blocks_x, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u)
-        overdraw_kernel<<<dim3(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u), 256, 0, stream>>>(d_jobs + y0);
-    return hipGetLastError();
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) { overdraw_kernel<<<dim3(blocks_x ? blocks_x : 1, ny), 256, 0, stream>>>(d_jobs + y0); });
 }
 
 hipError_t launch_scatter(const ScatterJob *d_jobs, uint32_t count, const uint32_t *d_job_image,
                           const spng_result *d_results, uint32_t blocks_x, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u)             // (grid y stops at 65535; a batch of interlaced images has 7 jobs each)
-        scatter_kernel<<<dim3(blocks_x, count - y0 < 65535u ? count - y0 : 65535u), 256, 0, stream>>>(d_jobs + y0, d_results, d_job_image + y0);
-    return hipGetLastError();
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {    // (a batch of interlaced images has 7 jobs each)
+        scatter_kernel<<<dim3(blocks_x, ny), 256, 0, stream>>>(d_jobs + y0, d_results, d_job_image + y0);
+    });
 }
 
 }  // namespace spng

@@ -278,23 +278,21 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackJob *__restrict__ j
 hipError_t launch_pack(const PackJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const dim3 grid(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        const dim3 grid(blocks_x ? blocks_x : 1, ny);
         if (source == 8) pack_kernel<uint8_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
         else pack_kernel<uint16_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
-    }
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_unpack(const UnpackJob *d_jobs, uint32_t count, uint32_t blocks_x, int target, hipStream_t stream)
 {
     if (!count) return hipSuccess;
-    for (uint32_t y0 = 0; y0 < count; y0 += 65535u) {           // (grid y stops at 65535)
-        const dim3 grid(blocks_x ? blocks_x : 1, count - y0 < 65535u ? count - y0 : 65535u);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        const dim3 grid(blocks_x ? blocks_x : 1, ny);
         if (target == 8) unpack_kernel<uint8_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
         else unpack_kernel<uint16_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace spng

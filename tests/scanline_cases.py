@@ -3,9 +3,11 @@ table (tests/test_scanline_cases.py) and the GPU parity tests (tests/test_gpu_sc
 Importable without a GPU.  Everything is generated, seeded by a stable function of the case name; nothing is read from disk.
 
 A case names width, height, depth, channels, interlaced, a content kind and a filter-type regime, plus what it CLAIMS about the
-dispatch (which kernel, which piece-length branch of `launch_plan`): tests/test_scanline_cases.py holds the claims against the
-mirrors of the dispatch below, which restate csrc/api.hip `launch_plan`, csrc/unfilter.hip `launch_unfilter` and csrc/encode.hip
-`launch_filter` / `filter_kernel` as plain numbers -- and checks that the lines they restate are still in the sources."""
+dispatch (which kernel, which piece-length rule of `unfilter_pieces`): tests/test_scanline_cases.py holds the claims against the
+dispatch itself -- csrc/geometry.hpp, the arithmetic `launch_plan` (csrc/host_decode.hip), `launch_unfilter` (csrc/unfilter.hip) and
+`launch_filter` (csrc/encode.hip) run, reached through tests/geometry.py -- and against mirrors of the kernels' internals below,
+which restate csrc/unfilter.hip and csrc/encode.hip `filter_kernel` as plain numbers, and checks that the lines those restate
+are still in the sources."""
 from __future__ import annotations
 
 import ctypes
@@ -14,41 +16,28 @@ from dataclasses import dataclass, replace
 
 import numpy as np
 
+import geometry as geo
 import pnghelp as ph
 
 SENTINEL = 0xA5                      # what storage holds before a call: rows that were not decoded must still hold it
 
-# ---- the dispatch constants, as plain numbers (where they live: see SOURCE_LINES) -----------------------------------------------
-WIDE_ROW = 2048                      # launch_unfilter: 32-unit tiles for 1- and 2-byte pixels; launch_plan: the 256..1024-row branch
-PIECE_FLOOR, WIDE_FLOOR, WIDE_CEIL = 128, 256, 1024
-SCALE_ROWS, WIDE_SCALE_ROWS = 4096, 2048
-PK_SCALE_ROWS, PK_FILL_ROWS, PK_FEW_ROWS, PK_FEW_HEIGHT = 8192, 1536, 1024, 1024
-PK_FEW_MIN, PK_FEW_MAX = 64, 256
+# ---- the dispatch constants: the library's own (csrc/geometry.hpp) ---------------------------------------------------------------
+WIDE_ROW = geo.constant("WIDE_ROW")  # launch_unfilter: 32-unit tiles for 1- and 2-byte pixels; unfilter_pieces: the 256..1024-row rule
+PIECE_FLOOR, WIDE_FLOOR, WIDE_CEIL = (geo.constant(n) for n in ("PIECE_FLOOR", "WIDE_FLOOR", "WIDE_CEIL"))
+SCALE_ROWS, WIDE_SCALE_ROWS = geo.constant("PIECE_SCALE_ROWS"), geo.constant("WIDE_SCALE_ROWS")
+PK_SCALE_ROWS, PK_FILL_ROWS, PK_FEW_ROWS, PK_FEW_HEIGHT = (geo.constant(n) for n in ("PK_SCALE_ROWS", "PK_FILL_ROWS", "PK_FEW_ROWS", "PK_FEW_HEIGHT"))
+PK_FEW_MIN, PK_FEW_MAX = geo.constant("PK_FEW_MIN"), geo.constant("PK_FEW_MAX")
+# launch_filter: at most so many workgroups of 4 waves, a row per wave: taller images loop
+FILTER_GRID_ROWS = geo.constant("FILTER_ROWS_PER_BLOCK") * geo.constant("FILTER_BLOCKS_MAX")
+# ---- the kernels' internals, as plain numbers (where they live: see SOURCE_LINES) ------------------------------------------------
 PK_NW, PK_TILE_BYTES = 4, 128        # unfilter_pk_kernel: waves per workgroup, bytes of a row per phase
 U_NW = 4                             # unfilter_kernel: waves per workgroup
 BAND = 64                            # rows per band of unfilter_kernel; the ballot of `cut` looks at 64 rows per round
 PACKED_ROW = 2048                    # filter_kernel: longest sub-byte scanline that goes through LDS
 FAST_STEP = 1024                     # filter_row_fast: bytes of a row per step of the wave (64 lanes x 16)
-FILTER_GRID_ROWS = 4 * 4096          # launch_filter: bx <= 4096 workgroups of 4 waves, a row per wave: taller images loop
 
 # (file, line that must still be there): the table fails, instead of silently losing coverage, when one of them moves
 SOURCE_LINES = [
-    ("api.hip", "piece_rows = (uint32_t)((total_rows / 4096 + 63) & ~(uint64_t)63);"),
-    ("api.hip", "if (piece_rows < 128) piece_rows = 128;"),
-    ("api.hip", "if (widest >= 2048 && k != 4 && k != 8) {"),
-    ("api.hip", "piece_rows = (uint32_t)((total_rows / 2048 + 63) & ~(uint64_t)63);"),
-    ("api.hip", "if (piece_rows < 256) piece_rows = 256;"),
-    ("api.hip", "if (piece_rows > 1024) piece_rows = 1024;"),
-    ("api.hip", "const uint32_t rr = 128u / (uint32_t)k;"),
-    ("api.hip", "piece_rows = (uint32_t)((total_rows / 8192 + rr - 1) / rr * rr);"),
-    ("api.hip", "const uint32_t fill = (uint32_t)(total_rows / 1536 / rr * rr);"),
-    ("api.hip", "const uint32_t floor4 = fill < 4 * rr ? fill : 4 * rr;"),
-    ("api.hip", "if (k == 4 && max_rows >= 1024) {"),
-    ("api.hip", "uint32_t few = (uint32_t)((total_rows / 1024 + rr - 1) / rr * rr);"),
-    ("api.hip", "few = few < 64 ? 64 : few > 256 ? 256 : few;"),
-    ("api.hip", "const uint32_t pieces = (max_rows + piece_rows - 1) / piece_rows;"),
-    ("unfilter.hip", "if (widest >= 2048) unfilter_kernel<4, 1, 32>"),
-    ("unfilter.hip", "if (widest >= 2048) unfilter_kernel<4, 2, 32>"),
     ("unfilter.hip", "#define SPNG_UNF_PK_NW 4"),
     ("unfilter.hip", "static constexpr int TB = 128, RING = 256;"),
     ("unfilter.hip", "const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(2 * NW) + 1 < nph);"),
@@ -64,7 +53,6 @@ SOURCE_LINES = [
     ("encode.hip", "if (volume < 8 && job.pitch <= PACKED_ROW) {"),
     ("encode.hip", "const bool fast = direct && (job.pitch & 15) == 0 && bpp != 5 && bpp != 7;"),
     ("encode.hip", "const uint32_t steps = pitch / 1024 + (pitch % 1024 ? 1 : 0);"),
-    ("encode.hip", "if (bx > 4096) bx = 4096;"),
     ("encode.hip", "for (uint32_t y = blockIdx.x * 4 + wave; y < job.sub_h; y += gridDim.x * 4) {"),
 ]
 
@@ -84,7 +72,7 @@ class Case:
     content: str = "noise"           # noise | synth | zebra (noise rows alternating with all-zero rows)
     regime: str = "mixed"            # unfilter cases: how the filter-type bytes are chosen (REGIMES)
     kernel: str = ""                 # claimed: the kernel `launch_unfilter` picks / the path of `filter_kernel`
-    branch: str = ""                 # claimed: the clause of `launch_plan` that sets the piece length
+    branch: str = ""                 # claimed: the rule of `unfilter_pieces` that sets the piece length
 
     @property
     def volume(self):
@@ -127,36 +115,16 @@ def storage_row_bytes(c: Case) -> int:
     return c.width * (1 if c.volume < 8 else c.volume >> 3)
 
 
-# ---- mirrors of the dispatch ------------------------------------------------------------------------------------------------------
+# ---- the dispatch, and mirrors of the kernels' internals -------------------------------------------------------------------------
 def unfilter_plan(k: int, jobs, configured: int = 0):
-    """csrc/api.hip `launch_plan` + csrc/unfilter.hip `launch_unfilter` for the jobs [(pitch, rows)] of pixel size k of ONE call:
-    -> (kernel, branch, rows per piece, pieces)"""
-    total = sum(r for _, r in jobs)
-    max_rows = max([1] + [r for _, r in jobs])
+    """`launch_plan` (csrc/host_decode.hip) + `launch_unfilter` (csrc/unfilter.hip) for the jobs [(pitch, rows)] of pixel size k of
+    ONE call, by the functions of csrc/geometry.hpp those two call: -> (kernel, branch, rows per piece, pieces)"""
     widest = max(p for p, _ in jobs)
-    piece, branch = configured, "configured"
-    if not piece:
-        piece, branch = (total // SCALE_ROWS + 63) & ~63, "scaled"
-        if piece < PIECE_FLOOR:
-            piece, branch = PIECE_FLOOR, "floor128"
-        if widest >= WIDE_ROW and k not in (4, 8):
-            piece, branch = (total // WIDE_SCALE_ROWS + 63) & ~63, "wide"
-            piece = min(max(piece, WIDE_FLOOR), WIDE_CEIL)
-        if k in (4, 8):
-            rr = 128 // k
-            piece, branch = max((total // PK_SCALE_ROWS + rr - 1) // rr * rr, rr), "rr"
-            floor4 = min(total // PK_FILL_ROWS // rr * rr, 4 * rr)
-            if piece < floor4:
-                piece, branch = floor4, "floor4"
-            if k == 4 and max_rows >= PK_FEW_HEIGHT:
-                few = min(max((total // PK_FEW_ROWS + rr - 1) // rr * rr, PK_FEW_MIN), PK_FEW_MAX)
-                if piece < few:
-                    piece, branch = few, "few"
-    pieces = (max_rows + piece - 1) // piece
+    piece, pieces, branch = geo.unfilter_pieces(k, sum(r for _, r in jobs), max([1] + [r for _, r in jobs]), widest, configured)
     if k in (4, 8):
         kernel = f"pk<{k}>"
     elif k in (1, 2):
-        kernel = f"u<4,{k},32>" if widest >= WIDE_ROW else f"u<4,{k}>"
+        kernel = f"u<4,{k},32>" if geo.unfilter_wide_tiles(k, widest) else f"u<4,{k}>"
     else:
         kernel = f"u<{k}>"
     return kernel, branch, piece, pieces
@@ -287,7 +255,7 @@ def _g(name, w, h, depth, ch, kernel, branch, interlaced=False):
     return Case(name, w, h, depth, ch, interlaced, "noise", "mixed", kernel, branch)
 
 
-# every path of `launch_unfilter` x `launch_plan` that one image can reach: these take all six regimes
+# every path of `launch_unfilter` x `unfilter_pieces` that one image can reach: these take all six regimes
 PRIMARY = [
     _g("gray8 1500x1300", 1500, 1300, 8, 1, "u<4,1>", "floor128"),
     _g("indexed8 4096x2500", 4096, 2500, 8, 1, "u<4,1,32>", "wide"),
@@ -387,7 +355,7 @@ def batch_plan(k: int, cases):
     return unfilter_plan(k, [(p, h) for c in cases for p, h, _ in passes(c)])
 
 
-# total rows > 128 * 4096: the `total_rows / 4096` term of `launch_plan` exceeds the 128-row floor.  Many narrow tall images.
+# total rows > 128 * 4096: the `total_rows / PIECE_SCALE_ROWS` term of `unfilter_pieces` exceeds the 128-row floor.  Many narrow tall images.
 def scaled_batch_cases():
     return [Case(f"scaled #{i} 16x1800 gray8", 16, 1800, 8, 1, False, "noise", ("mixed", "rare", "average")[i % 3]) for i in range(300)]
 

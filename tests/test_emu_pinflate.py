@@ -270,7 +270,7 @@ PART_CASES = list(part_cases())
 @pytest.mark.parametrize("parts", [4])
 @pytest.mark.parametrize("name", [c[0] for c in PART_CASES])
 def test_emulated_pipeline_resolves_a_stream_in_parts(emu, tmp_path, name, parts, tile):
-    """several workgroups per stream (api.hip: batches of few streams): the chain cut into parts, those behind the first resolved
+    """several workgroups per stream (host_decode.hip: batches of few streams): the chain cut into parts, those behind the first resolved
     to symbols with markers for what lies in front of them, the windows handed from part to part, symbols -> bytes, one verdict
     (Adler-32 over all parts) -- the same bytes and the same result as one workgroup gives.  The marker parts have two geometries
     (4 KiB tiles, two workgroups per CU, when a batch has more of them than CUs; 8 KiB tiles otherwise): both."""

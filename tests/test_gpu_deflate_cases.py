@@ -39,7 +39,7 @@ def wants():
 
 @pytest.mark.parametrize("name", dc.NAMES)
 def test_case_alone_under_every_knob(gpu, wants, name):
-    """INFLATE_SERIAL, and INFLATE_AUTO with segments of the default length and of 256 bytes (api.hip rounds to multiples of 256 and
+    """INFLATE_SERIAL, and INFLATE_AUTO with segments of the default length and of 256 bytes (geometry.hpp `inflate_segment_bytes` rounds to multiples of 256 and
     takes 256 as it is) x one workgroup per stream and 4 parts (one stream: 3 marker parts, the 8 KiB geometry)"""
     s = gpu.load()
     c = dc.case(name)

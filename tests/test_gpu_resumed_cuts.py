@@ -1,4 +1,4 @@
-"""Block cuts for streams that arrive in pieces (spng_inflate_resume_batch; csrc/pinflate2.hip "resumed calls", csrc/api.hip
+"""Block cuts for streams that arrive in pieces (spng_inflate_resume_batch; csrc/pinflate2.hip "resumed calls", csrc/host_decode.hip
 cut_into_segments): a call whose state is not all zero and that brings at least SPNG_CFG_BLOCK_CUT_BYTES behind its resume point
 decodes the huge block it stands in -- or in front of -- on many waves, from the exact token of its state, and hands the tail the end of
 the input cuts off to the serial kernel at the last proven join.  After every push: what the oracle reports for the same prefix, and

@@ -1,8 +1,9 @@
 """The table of tests/scanline_cases.py really is where tests/test_gpu_scanlines.py needs it to be.  For every case: the input is
 built, the oracle runs (status 0), and the properties the GPU tests rely on are asserted -- which kernel and which piece-length
 branch the dispatch takes, on which side of the 2048-byte row it lies, that its filter-type bytes are what its regime says --
-so that a threshold that moves in csrc/api.hip `launch_plan`, csrc/unfilter.hip `launch_unfilter` or csrc/encode.hip
-`launch_filter` / `PACKED_ROW` makes this file fail instead of silently taking a path out of the GPU tests.  No GPU needed."""
+so that a threshold that moves in csrc/geometry.hpp (the arithmetic of csrc/host_decode.hip `launch_plan`, csrc/unfilter.hip
+`launch_unfilter` and csrc/encode.hip `launch_filter`, called here as the library calls it: tests/geometry.py) or csrc/encode.hip
+`PACKED_ROW` makes this file fail instead of silently taking a path out of the GPU tests.  No GPU needed."""
 import os
 
 import numpy as np

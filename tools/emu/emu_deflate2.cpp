@@ -1,6 +1,6 @@
 // emu_deflate2.cpp -- TEST INFRASTRUCTURE: runs the round kernels of csrc/deflate.hip (dfl2_begin / dfl3_search /
 // dfl2_advance / dfl2_parse) on the CPU (tools/emu/hip/hip_runtime.h) over one stream, round by round and with the two sets
-// of candidate records alternating the way api.hip drives them, and compares the bytes with the expected stream (the oracle's).
+// of candidate records alternating the way host_encode.hip drives them, and compares the bytes with the expected stream (the oracle's).
 // Built and used by tests/test_emu_deflate.py from a copy of deflate.hip whose launchers and `s_waitcnt` lines are blanked
 // (EMU_DEFLATE_SRC); never part of the product.
 //
@@ -48,7 +48,7 @@ int main(int argc, char **argv)
         std::vector<uint64_t> cuts;
         for (int a = 6; a < argc; ++a) cuts.push_back(strtoull(argv[a], nullptr, 10));
         cuts.push_back(n);
-        // one-shot streams: the blocks side by side (dfl4_walk / dfl4_block / dfl4_scan / dfl4_place), as api.hip drives them;
+        // one-shot streams: the blocks side by side (dfl4_walk / dfl4_block / dfl4_scan / dfl4_place), as host_encode.hip drives them;
         // EMU_TWO_WAVE forces the two-wave parse (the form of streams that arrive in pieces)
         const bool blocks = cuts.size() == 1 && !getenv("EMU_TWO_WAVE");
         const uint32_t maxb = (uint32_t)deflate4_max_blocks(RV);

@@ -1,11 +1,11 @@
 // emu_pinflate2.cpp -- TEST INFRASTRUCTURE: runs the kernels of csrc/pinflate2.hip on the CPU (tools/emu/hip/hip_runtime.h)
-// over one DEFLATE stream, the way api.hip drives them (find -> decode -> scan -> resolve), and compares the bytes with the
+// over one DEFLATE stream, the way host_decode.hip drives them (find -> decode -> scan -> resolve), and compares the bytes with the
 // expected output.  Built and used by tests/test_emu_pinflate.py; never part of the product.
 //
 //   emu_pinflate2 <stream file> <expected output file> <format 0|1> <segment bytes> [pool pages] [resume: start_bit out_pos]
-//   EMU_CUT_BYTES=n: block cuts for runs of segments without a start of at least n bytes (api.hip: SPNG_CFG_BLOCK_CUT_BYTES), with
+//   EMU_CUT_BYTES=n: block cuts for runs of segments without a start of at least n bytes (host_decode.hip: SPNG_CFG_BLOCK_CUT_BYTES), with
 //   the retry pass behind them for a stream whose cuts do not stitch; prints "cuts tried=<n> joined=<n> redone=<n>"
-//   EMU_TOK_BIT=b EMU_TOK_OUT=w (with the resume arguments and EMU_CUT_BYTES): a resumed call with cuts, as api.hip plans it -- the
+//   EMU_TOK_BIT=b EMU_TOK_OUT=w (with the resume arguments and EMU_CUT_BYTES): a resumed call with cuts, as host_decode.hip plans it -- the
 //   state is {start_bit, out_pos, b, w} (b = 0: it stands at the block header), the first w bytes of the output are there, the
 //   segments count from the resume point; prints "handover bit=<b> bytes=<n> header=<bit> header_bytes=<n>" when the chain was
 //   handed to the serial kernel at a token (PStream.ok == 3)
@@ -55,13 +55,13 @@ int main(int argc, char **argv)
     st.src = src.data(); st.dst = dst.data(); st.src_len = src.size(); st.dst_cap = want.size();
     st.format = format; st.image = 0;
     uint64_t state[4] = {0, 0, 0, 0};                          // (four words: the pipeline moves the first pair and clears the second)
-    st.state = state;                                          // (api.hip: every stream has a state slot, {0, 0} unless resumed)
+    st.state = state;                                          // (host_decode.hip: every stream has a state slot, {0, 0} unless resumed)
     const bool resumed = argc > 7;
     const uint64_t cut_bytes = getenv("EMU_CUT_BYTES") ? strtoull(getenv("EMU_CUT_BYTES"), nullptr, 10) : 0;
     if (argc > 7) {
         state[0] = st.start_bit = strtoull(argv[6], nullptr, 10); state[1] = st.out_pos = st.blk_out = strtoull(argv[7], nullptr, 10);
         if (cut_bytes && getenv("EMU_TOK_BIT")) {
-            // (api.hip, cut_into_segments: the gate and the plan of a resumed call with cuts)
+            // (host_decode.hip, cut_into_segments: the gate and the plan of a resumed call with cuts)
             state[2] = strtoull(getenv("EMU_TOK_BIT"), nullptr, 10); state[3] = getenv("EMU_TOK_OUT") ? strtoull(getenv("EMU_TOK_OUT"), nullptr, 10) : 0;
             const uint64_t at = (state[2] ? state[2] : state[0]) / 8;
             if (src.size() >= at && src.size() - at >= cut_bytes) {
@@ -95,9 +95,9 @@ int main(int argc, char **argv)
 
     emu::launch((unsigned)k, 64, [&] { pinf2_find_kernel<0>(&st, segs.data(), 0); });
     if (verbose) for (uint64_t q = 0; q < k; ++q) fprintf(stderr, "seg %llu: start %lld\n", (unsigned long long)q, (long long)segs[q].start_bit);
-    // block cuts (api.hip: a batch with a stream they may be tried for)
+    // block cuts (host_decode.hip: a batch with a stream they may be tried for)
     uint32_t cstats[4] = {0, 0, 0, 0};                         // cuts tried, joined, streams redone
-    std::vector<PCut> cuts(k);                                 // (api.hip: a table of its own beside the segments, zeroed on the device)
+    std::vector<PCut> cuts(k);                                 // (host_decode.hip: a table of its own beside the segments, zeroed on the device)
     memset(cuts.data(), 0, k * sizeof(PCut));
     if (cut_bytes && (!resumed || st.cut_resumed)) {
         st.cut_segs = (uint32_t)(st.cut_resumed ? (cut_bytes / seg_bytes ? cut_bytes / seg_bytes : 1) : (cut_bytes + seg_bytes - 1) / seg_bytes);
@@ -114,7 +114,7 @@ int main(int argc, char **argv)
     if (verbose) for (uint64_t q = 0; q < k; ++q)
         fprintf(stderr, "seg %llu: end %lld status %d nhw %llu next %u\n", (unsigned long long)q, (long long)segs[q].end_bit, segs[q].status,
                 (unsigned long long)segs[q].ntok, segs[q].next);
-    // EMU_PARTS=n: the stream's chain in up to n parts, resolved by n workgroups (what api.hip does for batches of few streams)
+    // EMU_PARTS=n: the stream's chain in up to n parts, resolved by n workgroups (what host_decode.hip does for batches of few streams)
     const uint32_t pmax = getenv("EMU_PARTS") ? (uint32_t)atoi(getenv("EMU_PARTS")) : 0;
     std::vector<PPart> parts(pmax ? pmax : 1);
     memset(parts.data(), 0, parts.size() * sizeof(PPart));
@@ -170,7 +170,7 @@ int main(int argc, char **argv)
     if (redo) emu::launch(1, RT2, [&] { pinf2_resolve_kernel<1, false, true>(&st, segs.data(), pt.data(), pool_redo, &res, &done, parts.data(), 0, nullptr); });
     else
     emu::launch(1, RT2, [&] { pinf2_resolve_kernel<0, false, true>(&st, segs.data(), pt.data(), pool, &res, &done, parts.data(), pmax, nullptr); });
-    // EMU_RETRY_PAGES=n: a stream whose segments found the pool empty takes the retry pass (api.hip: the pool to itself and
+    // EMU_RETRY_PAGES=n: a stream whose segments found the pool empty takes the retry pass (host_decode.hip: the pool to itself and
     // its like -- here a second pool of n pages)
     if (getenv("EMU_RETRY_PAGES")) {
         printf("first pass: ok %d pass %u\n", st.ok, st.pass);
@@ -186,7 +186,7 @@ int main(int argc, char **argv)
         printf("retry pass: ok %d done %d pages %u\n", st.ok, done, next2);
     }
     if (pmax >= 2 && !redo) {
-        // (api.hip picks the marker parts' geometry by their number; here EMU_MARK_TILE=8192 asks for the big tiles)
+        // (host_decode.hip picks the marker parts' geometry by their number; here EMU_MARK_TILE=8192 asks for the big tiles)
         if (getenv("EMU_MARK_TILE") && atoi(getenv("EMU_MARK_TILE")) == 8192)
             emu::launch(pmax - 1, RT2, [&] { pinf2_resolve_kernel<0, true, true>(&st, segs.data(), pt.data(), pool, &res, &done, parts.data(), pmax, sym.data()); });
         else

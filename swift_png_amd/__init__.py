@@ -923,15 +923,17 @@ class Session:
         r = res[0]
         return r, (r.aux[0], r.aux[1])
 
-    def deflate_batch(self, streams, level, fmt=FORMAT_ZLIB):
-        """streams: list of uint8 device tensors -> (list of output tensors, list[Result])"""
+    def deflate_batch(self, streams, level, fmt=FORMAT_ZLIB, levels=None, exponents=None):
+        """streams: list of uint8 device tensors -> (list of output tensors, list[Result]).  level / fmt: one value, or one per
+        stream; levels: a level per stream (instead of `level`); exponents: a window exponent 8 ... 15 per stream (None or 0: 15,
+        what PNG uses; spng_stream_desc.reserved)"""
         n = len(streams)
         caps = [self.lib.spng_deflate_bound(t.numel()) for t in streams]
         outs = [self.empty(c) for c in caps]
         descs = (StreamDesc * n)()
         for i, (t, o, c) in enumerate(zip(streams, outs, caps)):
-            descs[i] = StreamDesc(self._ptr(t), t.numel(), self._ptr(o), int(c), fmt, 0)
-        levels = (ctypes.c_int32 * n)(*([level] * n))
+            descs[i] = StreamDesc(self._ptr(t), t.numel(), self._ptr(o), int(c), pick(fmt, i), int(exponents[i]) if exponents is not None else 0)
+        levels = (ctypes.c_int32 * n)(*[int(pick(level if levels is None else list(levels), i)) for i in range(n)])
         res = (Result * n)()
         _check(self.lib, self.lib.spng_deflate_batch(self.ctx, descs, levels, n, None, res))
         return outs, list(res)

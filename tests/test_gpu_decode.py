@@ -545,6 +545,16 @@ def test_deflate_dry_pool_second_pass(gpu):
         s.configure(gpu.CFG_DEFLATE_BYTES, 0)
 
 
+def _inserter_payloads():
+    """-> {kind: (data, levels)}: the deflate payloads at levels 4, 6, 9, and from the encoder's case table (tests/encode_cases.py) the
+    cases that put positions of one bucket into one batch and one quad and that read a chain's second member, at levels 0 and 1 too
+    (one attempt, two attempts: the order of the chain shows in the bytes)"""
+    import encode_cases as ec
+    p = {kind: (data, (4, 6, 9)) for kind, data in _deflate_payloads().items()}
+    p.update({name: (ec.case(name).data, (0, 1, 4, 6, 9)) for name in ec.NAMES if name.startswith(("bucket-", "second-"))})
+    return p
+
+
 def test_deflate_inserter_forms(gpu):
     """The match search's inserter exchanges bucket heads with one ds_mskor_rtn_b32 per lane where the device's LDS serves the
     lanes of an address in ascending order (probed when the context is created: spng_lds_exchange_ordered), and reads its store
@@ -561,8 +571,8 @@ def test_deflate_inserter_forms(gpu):
     assert s.lib.spng_lds_exchange_ordered(s.ctx, None) == gpu.E_ARGUMENT
     code = ("import sys, hashlib, ctypes; sys.path.insert(0, %r); sys.path.insert(0, %r); import swift_png_amd as spng; import test_gpu_decode as t\n"
             "s = spng.load(); v = ctypes.c_int32(-1); s.lib.spng_lds_exchange_ordered(s.ctx, ctypes.byref(v)); print('ordered', v.value)\n"
-            "for kind, data in sorted(t._deflate_payloads().items()):\n"
-            "    for level in (4, 6, 9): print(kind, level, hashlib.sha256(s.deflate(data, level)).hexdigest())\n") % (
+            "for kind, (data, levels) in sorted(t._inserter_payloads().items()):\n"
+            "    for level in levels: print(kind, level, hashlib.sha256(s.deflate(data, level)).hexdigest())\n") % (
                 os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
     out = {}
     for form in ("probed", "readback"):
@@ -576,9 +586,11 @@ def test_deflate_inserter_forms(gpu):
     assert out["readback"][0] == "ordered 0"
     assert out["probed"][0] == "ordered %d" % v.value
     assert out["probed"][1:] == out["readback"][1:]
+    payloads = _inserter_payloads()
+    assert len(out["probed"]) - 1 == sum(len(levels) for _, levels in payloads.values()) and set(_deflate_payloads()) < set(payloads)
     for line in out["probed"][1:]:
         kind, level, digest = line.split()
-        assert digest == hashlib.sha256(ph.orc_deflate(_deflate_payloads()[kind], int(level))).hexdigest(), (kind, level)
+        assert digest == hashlib.sha256(ph.orc_deflate(payloads[kind][0], int(level))).hexdigest(), (kind, level)
 
 
 @pytest.mark.parametrize("level", [1, 6])

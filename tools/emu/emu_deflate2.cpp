@@ -6,6 +6,7 @@
 //
 //   emu_deflate2 <input file> <expected stream file> <level> <format 0 zlib | 1 raw (ios)> [chunks per stream] [cut ...]
 //   cut ...: the input arrives in pieces (spng_deflate_resume_batch): a call per cut with `more` set, the state kept, then the rest
+//   EMU_EXPONENT=8...15: the window exponent (default 15, what PNG uses; the raw format always takes 15, DeflatorBuffers.swift:52-55)
 //   exit code 0: SPNG_DONE and identical bytes; 1: anything else (printed)
 #include EMU_DEFLATE_SRC
 
@@ -27,6 +28,9 @@ int main(int argc, char **argv)
     const int level = atoi(argv[3]), format = atoi(argv[4]);
     const uint32_t cps = argc > 5 ? (uint32_t)atoi(argv[5]) : 3;
     const uint64_t n = src.size();
+    const int asked = getenv("EMU_EXPONENT") ? atoi(getenv("EMU_EXPONENT")) : 15;
+    if (asked < 8 || asked > 15) { fprintf(stderr, "EMU_EXPONENT: 8 ... 15\n"); return 2; }
+    const uint32_t exponent = format == 1 ? 15u : (uint32_t)asked;
     std::vector<uint8_t> dst(want.size() + 4096, 0xEE);
     src.resize(n + 64);                                          // (the kernels read keys a few bytes past positions they search)
 
@@ -39,7 +43,7 @@ int main(int argc, char **argv)
         D3Stream st;
         memset(&st, 0, sizeof st);
         st.src = src.data(); st.dst = dst.data(); st.src_len = n; st.dst_cap = dst.size();
-        st.format = format == 1 ? SPNG_FORMAT_IOS : SPNG_FORMAT_ZLIB; st.level = level; st.image = 0; st.exponent = 15;
+        st.format = format == 1 ? SPNG_FORMAT_IOS : SPNG_FORMAT_ZLIB; st.level = level; st.image = 0; st.exponent = exponent;
         st.state = (D1State *)statebuf.data();
         st.match[0] = match[0].data(); st.match[1] = match[1].data();
         spng_result res;
@@ -115,7 +119,7 @@ int main(int argc, char **argv)
     D2Stream st;
     memset(&st, 0, sizeof st);
     st.src = src.data(); st.dst = dst.data(); st.src_len = n; st.dst_cap = dst.size();
-    st.format = format == 1 ? SPNG_FORMAT_IOS : SPNG_FORMAT_ZLIB; st.level = level; st.image = 0; st.exponent = 15; st.more = 0;
+    st.format = format == 1 ? SPNG_FORMAT_IOS : SPNG_FORMAT_ZLIB; st.level = level; st.image = 0; st.exponent = exponent; st.more = 0;
     st.state = &state;
     st.vinfo = vinfo[0].data(); st.bbase = bbase[0].data(); st.bwords = bwords[0].data(); st.emask = emask.data();
     st.vinfo2 = vinfo[1].data(); st.bbase2 = bbase[1].data(); st.bwords2 = bwords[1].data();

@@ -156,6 +156,58 @@ __device__ __forceinline__ void bulk_put(DLds &s, Bits &b, uint64_t v, uint32_t 
     b.acc = b.nacc ? UNI(s.out[b.total & (OUTB - 1)]) : 0;      // (the unfinished byte stays in the ring; put() overwrites it)
 }
 
+// ---- the stream envelope: what stands around the blocks, the same for every level ----------------------------------------
+// A header and a stored tail start on a byte boundary (the stream's beginning), so they are bytes, handed one by one to
+// `emit(byte)`: a wave puts them through its bit writer, dfl4_scan_kernel's one thread stores them.
+template <class Emit>
+__device__ __forceinline__ void stream_header(int32_t format, uint32_t exponent, Emit emit)
+{
+    if (format == SPNG_FORMAT_ZLIB) {
+        // StreamHeader.write (StreamHeader.swift:56-62)
+        const uint32_t unpaired = (exponent - 8) << 4 | 0x08;
+        const uint32_t check = ~(((unpaired << 8 | unpaired >> 8) & 0xffff) % 31) & 31;
+        emit(unpaired); emit(check);
+    } else if (format == SPNG_FORMAT_GZIP) {
+        // Gzip.StreamHeader.write (Gzip.StreamHeader.swift:84-96); the trailer is appended by gzip.hip
+        emit(0x1f); emit(0x8b); emit(8);
+        for (int i = 0; i < 6; ++i) emit(0);
+        emit(0xff);
+    }
+}
+// Stream.compressBlocks stored tail (:45-60, :417-434), all there is of an input of n < 3 bytes; S, I: its sums for adler32_word
+template <class Emit>
+__device__ __forceinline__ void stored_tail(const gbyte *in, uint32_t n, uint32_t &S, uint32_t &I, Emit emit)
+{
+    emit(1); emit(n); emit(0); emit(~n & 0xff); emit(0xff);
+    S = 0; I = 0;
+    for (uint32_t k = 0; k < n; ++k) { const uint32_t v = in[k]; emit(v); S += v; I += k * v; }
+}
+// Adler-32 of n bytes x[k] from S = sum x[k] and I = sum k * x[k], as the search kernels leave them (s1 = 1 + S, s2 = N + N * S - I)
+__device__ __forceinline__ uint32_t adler32_word(uint32_t S, uint32_t I, uint64_t n)
+{
+    S %= 65521; I %= 65521;
+    const uint32_t N = (uint32_t)(n % 65521);
+    return ((N + (uint64_t)N * S % 65521 + 65521 - I) % 65521) << 16 | (1 + S) % 65521;
+}
+// The end of a stream on a wave: the zlib trailer (tail_S, tail_I: the sums of a stored tail), the padding, the last bytes
+// out, the result.  `reserved` says which parse kernel answers.
+template <class State>
+__device__ __forceinline__ void finish_stream(DLds &s, Bits &b, int32_t format, uint64_t n, uint32_t tail_S, uint32_t tail_I, State *state, spng_result &res,
+                                              uint32_t reserved, int lane)
+{
+    if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);                // DeflatorOut.pull flushes padding bits
+    if (format == SPNG_FORMAT_ZLIB) {
+        const uint32_t sum = n < 3 ? adler32_word(tail_S, tail_I, n) : adler32_word(UNI(state->adlerS), UNI(state->adlerI), n);
+        for (int i = 24; i >= 0; i -= 8) put(s, b, sum >> i, 8, lane);
+    }
+    drain(s, b, b.total, lane);
+    if (lane == 0) {
+        res.status = b.overflow ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE; res.reserved = reserved;
+        res.written = b.total; res.consumed = n; res.aux[0] = res.aux[1] = 0;
+        state->done = 1;
+    }
+}
+
 // HuffmanTree.init(frequencies:limit:) (HuffmanTree.swift:247-344) for `n` symbols with counts
 // in freq[0..n): code length per symbol into len[].  The heap (LZ77.Heap.swift) is replayed
 // exactly -- which two nodes merge on equal keys depends on its sift order -- but its values are
@@ -596,13 +648,13 @@ __shared__ uint64_t g_prof[12];
 #endif
 
 // =====================================================================================================================
-// levels >= 8, round 4: the search and the parse in kernels of their own
+// levels >= 8: the search and the parse in kernels of their own
 // =====================================================================================================================
 // The candidates of a position are a pure function of the input (the design note at the top of this file), and the block
 // boundaries of the full search are fixed vertex counts (2047, 4095, ... 2^21 - 1: LZ77.DeflatorMatches.swift:229): nothing
 // about them has to wait for the parse.  So a batch goes through in ROUNDS of up to 2^21 vertices per stream (the small
 // blocks of a stream's start together, then one block at the cap per round), each round two launches:
-//   * the search kernel (round 4: dfl2_search_kernel, links in HBM; round 5: dfl3_search_kernel below, the window in LDS) --
+//   * the search kernel (dfl3_search_kernel below, the window in LDS) --
 //     every stream's round cut into chunks, a workgroup per chunk: wave 0 inserts (32 KiB of warm-up in front of the chunk),
 //     the others take 64 positions at a time behind it, walk the chains and leave, per position, the longest run
 //     seen and its candidates -- ONE packed word each (position-in-batch, distance, run), only for positions that have any:
@@ -636,6 +688,15 @@ __host__ __device__ inline uint64_t d2_round_end(uint64_t pos, uint32_t limit, u
     }
     return end;
 }
+// the limit as the blocks of a round, `pos` to `end`, leave it: doubled behind every block but the stream's last (trees(iterations:) :229)
+__host__ __device__ inline uint32_t d2_round_limit(uint64_t pos, uint64_t end, uint32_t lim, uint64_t n, bool more)
+{
+    for (uint64_t at = pos; at < end;) {
+        at += (uint64_t)(lim - 1) < end - at ? (uint64_t)(lim - 1) : end - at;
+        if (more || at < n) lim = 2 * lim < (1u << 21) ? 2 * lim : 1u << 21;
+    }
+    return lim;
+}
 // rounds a call takes from (pos, limit) on, and where it leaves them
 uint32_t deflate2_plan(uint64_t n, bool more, uint64_t &pos, uint32_t &lim)
 {
@@ -644,11 +705,7 @@ uint32_t deflate2_plan(uint64_t n, bool more, uint64_t &pos, uint32_t &lim)
     for (;;) {
         const uint64_t end = d2_round_end(pos, lim, n, more);
         if (end == pos) break;
-        for (uint64_t at = pos; at < end;) {                    // (the limit as the blocks of the round leave it)
-            const uint64_t size = (uint64_t)(lim - 1) < end - at ? (uint64_t)(lim - 1) : end - at;
-            at += size;
-            if (more || at < n) lim = 2 * lim < (1u << 21) ? 2 * lim : 1u << 21;
-        }
+        lim = d2_round_limit(pos, end, lim, n, more);
         pos = end; ++rounds;
         if (!more && pos >= n) break;
     }
@@ -1271,12 +1328,100 @@ __global__ __launch_bounds__(SPNG_D3_WAVES * 64) void dfl3_search_fast_kernel(co
                            (uint32_t *)uni64((uint64_t)st.match[parity]));
 }
 
+// ---- the walk: Stream.compress greedy (:209-252) / lazy (:268-323), the one statement of its rules ------------------------------
+// One wave walks the answers of a round from position `w` on and queues terms at terms[count ...] (LDS); -> where it stands.
+// A block closes when 2047 terms are queued (lazy: 2046 or 2047: a step may queue two), looked at before every step (:219,
+// :277): `close_block()` is the caller's -- it takes the `count` terms away, sets count = 0 and may turn `terms` to another buffer.
+template <class Close>
+__device__ __forceinline__ uint64_t d3_walk(const gbyte *in, uint64_t n, const gword *match, uint64_t rb, uint64_t re, bool lazy, uint64_t w,
+                                            uint32_t *&terms, uint32_t &count, int lane, Close close_block)
+{
+    const uint32_t cap = lazy ? 2046u : 2047u;
+    const uint64_t last_main = n - 4 + 1;                      // positions 0 .. n-4 are searched
+    const uint64_t stop = re < last_main ? re : last_main;     // tokens that start below `stop` are this round's
+    // the answers of 128 positions at a time (two per lane), fetched a batch ahead: a wave alone has nobody to hide a load behind
+    auto ask = [&](uint64_t p, uint32_t &m, uint32_t &lit) {
+        m = (p <= re && p < last_main) ? match[p - rb] : 0u;
+        lit = p < n ? (uint32_t)in[p] : 0u;
+    };
+    uint32_t nmA, nmB, nlA, nlB;
+    uint64_t asked = w;
+    ask(w + lane, nmA, nlA); ask(w + 64 + lane, nmB, nlB);
+    while (w < stop) {
+        uint32_t mA, mB, litA, litB;
+        if (asked == w) { mA = nmA; mB = nmB; litA = nlA; litB = nlB; }
+        else { ask(w + lane, mA, litA); ask(w + 64 + lane, mB, litB); }
+        asked = w + 128;                                       // (the guess: the batch is used up to its end -- a run across it asks again)
+        ask(asked + lane, nmA, nlA); ask(asked + 64 + lane, nmB, nlB);
+        // What a position would queue if the walk came by -- its literal, its match (LZ77.DeflatorTerm.init(run:distance:),
+        // DeflatorTerm.swift:34-56) -- is worked out for all 128 at once; the walk itself, one position after the other on the
+        // scalar unit, only picks: a run of positions without a match is one vector store of their literals.
+        auto mterm = [&](uint32_t m) -> uint32_t {
+            const uint32_t run = m >> 16, dist = m & 0xffff;
+            const uint32_t rd = run_decade(run ? run : 3u), dd = dist_decade(dist ? dist : 1u);
+            return dd << 27 | 0x100u | rd | dist_extra_value(dist, dd) << 14 | run_extra_value(run, rd) << 9;
+        };
+        const uint32_t tmA = mterm(mA), tmB = mterm(mB), tlA = 0xf8000000u | litA, tlB = 0xf8000000u | litB;
+        const uint32_t runA = mA >> 16, runB = mB >> 16;
+        const unsigned long long nzA = __ballot(runA != 0), nzB = __ballot(runB != 0);
+        auto at = [&](uint32_t xa, uint32_t xb, uint32_t t) -> uint32_t {
+            return t < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)xa, (int)t) : (uint32_t)__builtin_amdgcn_readlane((int)xb, (int)(t - 64));
+        };
+        const uint32_t avail = stop - w < 128 ? (uint32_t)(stop - w) : 128u;   // positions of this batch that are this round's
+        uint32_t t = 0;
+        while (t < avail) {
+            if (count >= cap) close_block();
+            // positions from t on without a match
+            uint32_t L;
+            if (t < 64) { const unsigned long long a = nzA >> t; L = a ? (uint32_t)__builtin_ctzll(a) : 64 - t + (nzB ? (uint32_t)__builtin_ctzll(nzB) : 64u); }
+            else { const unsigned long long b2 = nzB >> (t - 64); L = b2 ? (uint32_t)__builtin_ctzll(b2) : 128 - t; }
+            L = L < avail - t ? L : avail - t;
+            if (L) {
+                L = L < cap - count ? L : cap - count;         // (the block closes in between: the next turn goes on)
+                const uint32_t qa = (uint32_t)lane, qb = 64u + (uint32_t)lane;
+                if (qa >= t && qa < t + L) terms[count + qa - t] = tlA;
+                if (qb >= t && qb < t + L) terms[count + qb - t] = tlB;
+                count += L; t += L;
+                continue;
+            }
+            const uint32_t run = at(runA, runB, t);
+            if (lazy) {
+                // the answer for position w + t + 1 is needed: the next batch starts there if it is not in this one
+                if (t + 1 >= 128) break;
+                // lazy match at a + 1 (:293-299); it exists only if that position is still searched
+                const uint32_t lrun = at(runA, runB, t + 1);
+                if (lrun > run) {
+                    const uint32_t a0 = at(tlA, tlB, t), a1 = at(tmA, tmB, t + 1);
+                    if (lane == 0) { terms[count] = a0; terms[count + 1] = a1; }
+                    count += 2; t += 1 + lrun;
+                    continue;
+                }
+            }
+            const uint32_t a0 = at(tmA, tmB, t);
+            if (lane == 0) terms[count] = a0;
+            count += 1; t += run;
+        }
+        w = uni64(w + t);
+    }
+    return w;
+}
+// epilogue: the positions still in the window pipeline become literals (:254-265, :331-342); the final block is the caller's to close
+template <class Close>
+__device__ __forceinline__ void d3_walk_epilogue(const gbyte *in, uint64_t n, uint64_t w, uint32_t *&terms, uint32_t &count, int lane, Close close_block)
+{
+    for (uint64_t p = w; p < n; ++p) {
+        if (count >= 2047u) close_block();
+        const uint32_t t = 0xf8000000u | UNI(in[p]);
+        if (lane == 0) terms[count] = t;
+        count += 1;
+    }
+}
+
 // Two waves per stream.  Wave 0, the parser, walks the answers and queues terms -- into one of two buffers; wave 1, the writer,
 // owns the bit writer: the stream's header, every block (symbol counts, the trees, the tables, the bits: write_block), the
 // trailer, the results.  A full buffer is handed over with a command word and the parser goes on in the other one: the walk of
-// block k + 1 runs beside the trees and bits of block k (one wave did them one after the other: at level 6 the blocks were 60 %
-// of a stream's time).  At the end of a round the parser keeps its position and the terms of the unfinished block in the
-// D1State, the writer its pending bits.
+// block k + 1 runs beside the trees and bits of block k.  At the end of a round the parser keeps its position and the terms of
+// the unfinished block in the D1State, the writer its pending bits.
 enum : uint32_t { D3_CMD_BLOCK = 1u << 28, D3_CMD_FINAL = 2u << 28, D3_CMD_SAVE = 3u << 28, D3_CMD_MORE = 4u << 28, D3_CMD_MASK = 7u << 28 };
 
 __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restrict__ streams, spng_result *__restrict__ results, uint32_t parity)
@@ -1313,13 +1458,11 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
         // ---- the parser
         const gword *match = (const gword *)uni64((uint64_t)sp->match[parity]);
         uint64_t w = w0;
-        int count = (int)count0;
+        uint32_t count = count0;
         uint32_t tb = 0;                                       // the buffer being filled
         uint32_t *terms = g_trm.terms[0];
-        for (int i = lane; i < count; i += 64) terms[i] = state->terms[i];
+        for (uint32_t i = (uint32_t)lane; i < count; i += 64) terms[i] = state->terms[i];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        const int limit_terms = 2048;
-        auto unfilled = [&]() { return limit_terms - 1 - count; };
 #ifdef SPNG_D3_PROF
         unsigned long long pwait = 0, pblocks = 0;
         const unsigned long long pstart = __builtin_readcyclecounter();
@@ -1327,7 +1470,7 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
         // hands the buffer's `count` terms to the writer and turns to the other buffer (once the writer has let go of it)
         auto hand_over = [&](uint32_t cmd) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            if (lane == 0) __hip_atomic_store(&g_trm.cmd[tb], cmd | (uint32_t)count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0) __hip_atomic_store(&g_trm.cmd[tb], cmd | count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             tb ^= 1; terms = g_trm.terms[tb]; count = 0;
 #ifdef SPNG_D3_PROF
             const unsigned long long t0 = __builtin_readcyclecounter();
@@ -1341,61 +1484,14 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
             pwait += __builtin_readcyclecounter() - t0; pblocks += 1;
 #endif
         };
-        if (n >= 3) {
-            const uint64_t last_main = n - 4 + 1;              // positions 0 .. n-4 are searched
-            const uint64_t stop = re < last_main ? re : last_main; // tokens that start below `stop` are this round's
-            // the answers of 128 positions at a time (two per lane), fetched a batch ahead: a wave alone has nobody to hide a load behind
-            auto ask = [&](uint64_t p, uint32_t &m, uint32_t &lit) {
-                m = (p <= re && p < last_main) ? match[p - rb] : 0u;
-                lit = p < n ? (uint32_t)in[p] : 0u;
-            };
-            uint32_t nmA, nmB, nlA, nlB;
-            uint64_t asked = w;
-            ask(w + lane, nmA, nlA); ask(w + 64 + lane, nmB, nlB);
-            while (w < stop) {
-                uint32_t mA, mB, litA, litB;
-                if (asked == w) { mA = nmA; mB = nmB; litA = nlA; litB = nlB; }
-                else { ask(w + lane, mA, litA); ask(w + 64 + lane, mB, litB); }
-                asked = w + 128;                               // (the guess: the batch is used up to its end -- a run across it asks again)
-                ask(asked + lane, nmA, nlA); ask(asked + 64 + lane, nmB, nlB);
-                auto at = [&](uint32_t xa, uint32_t xb, uint32_t t) -> uint32_t {
-                    return t < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)xa, (int)t) : (uint32_t)__builtin_amdgcn_readlane((int)xb, (int)(t - 64));
-                };
-                // ---- the parse: Stream.compress greedy (:209-252) / lazy (:268-323) over these 128 answers
-                uint32_t t = 0;
-                while (t < 128 && w + t < stop) {
-                    if (!(unfilled() > (lazy ? 1 : 0))) hand_over(D3_CMD_BLOCK);
-                    const uint32_t m = at(mA, mB, t);
-                    const uint32_t lit = at(litA, litB, t);
-                    if (!m) { terms[count] = 0xf8000000u | lit; ++count; t += 1; continue; }
-                    uint32_t use_run = m >> 16, use_dist = m & 0xffff;
-                    uint32_t adv = use_run;
-                    if (lazy) {
-                        // the answer for position w + t + 1 is needed: start the next batch there if it is not in this one
-                        if (t + 1 >= 128) break;
-                        // lazy match at a + 1 (:293-299); it exists only if that position is still searched
-                        const uint32_t lm = at(mA, mB, t + 1);
-                        if ((lm >> 16) > use_run) {
-                            terms[count] = 0xf8000000u | lit;
-                            ++count;
-                            use_run = lm >> 16; use_dist = lm & 0xffff;
-                            adv = 1 + use_run;
-                        }
-                    }
-                    // LZ77.DeflatorTerm.init(run:distance:) (DeflatorTerm.swift:34-56)
-                    const uint32_t rd = run_decade(use_run), dd = dist_decade(use_dist);
-                    terms[count] = dd << 27 | 0x100u | rd | dist_extra_value(use_dist, dd) << 14 | run_extra_value(use_run, rd) << 9;
-                    ++count;
-                    t += adv;
-                }
-                w = uni64(w + t);
-            }
-        } else w = n;                                          // (a stored tail: the writer's)
+        auto close_block = [&] { hand_over(D3_CMD_BLOCK); };
+        w = n >= 3 ? d3_walk(in, n, match, rb, re, lazy, w, terms, count, lane, close_block) : n;   // (n < 3, a stored tail: the writer's)
         if (re < E || more) {
             // on with the next round / the next push: the unfinished block's terms and the position into the state
-            for (int i = lane; i < count; i += 64) state->terms[i] = terms[i];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+            for (uint32_t i = (uint32_t)lane; i < count; i += 64) state->terms[i] = terms[i];
             if (lane == 0) {
-                state->w = w; state->count = (uint32_t)count;
+                state->w = w; state->count = count;
                 if (re < E) { state->rb = re; state->re = re + D3_RV < E ? re + D3_RV : E; }
                 g_trm.fin_w = w;
             }
@@ -1407,14 +1503,7 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
 #endif
             return;
         }
-        if (n >= 3) {
-            // epilogue: the positions still in the window pipeline become literals (:254-265, :331-342)
-            for (uint64_t p = w; p < n; ++p) {
-                if (!(unfilled() > 0)) hand_over(D3_CMD_BLOCK);
-                terms[count] = 0xf8000000u | UNI(in[p]);
-                ++count;
-            }
-        }
+        if (n >= 3) d3_walk_epilogue(in, n, w, terms, count, lane, close_block);
         hand_over(D3_CMD_FINAL);
         return;
     }
@@ -1424,27 +1513,10 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     Bits b = {uni64(state->acc), UNI(state->nacc), uni64(state->total), uni64(state->total), (gbyte *)uni64((uint64_t)sp->dst), uni64(sp->dst_cap),
               UNI(state->overflow) != 0};
-    if (w0 == 0 && b.total == 0 && b.nacc == 0 && count0 == 0) {
-        // the stream's first round
-        if (format == SPNG_FORMAT_ZLIB) {
-            // StreamHeader.write (StreamHeader.swift:56-62)
-            const uint32_t unpaired = (UNI(sp->exponent) - 8) << 4 | 0x08;
-            const uint32_t check = ~(((unpaired << 8 | unpaired >> 8) & 0xffff) % 31) & 31;
-            put(s, b, check << 8 | unpaired, 16, lane);
-        } else if (format == SPNG_FORMAT_GZIP) {
-            // Gzip.StreamHeader.write (Gzip.StreamHeader.swift:84-96); the trailer is appended by gzip.hip
-            put(s, b, 0x8b1f, 16, lane); put(s, b, 0x0008, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0xff00, 16, lane);
-        }
-    }
+    auto put_byte = [&, lane](uint32_t v) { put(s, b, v, 8, lane); };
+    if (w0 == 0 && b.total == 0 && b.nacc == 0 && count0 == 0) stream_header(format, UNI(sp->exponent), put_byte);   // the stream's first round
     uint32_t tailS = 0, tailI = 0;
-    if (n < 3) {
-        // Stream.compressBlocks stored tail (:45-60, :417-434)
-        put(s, b, 1, 3, lane);
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, (uint32_t)n, 16, lane); put(s, b, ~(uint32_t)n & 0xffff, 16, lane);
-        for (uint64_t k = 0; k < n; ++k) put(s, b, in[k], 8, lane);
-        if ((uint64_t)lane < n) { tailS = in[lane]; tailI = (uint32_t)lane * in[lane]; }
-    }
+    if (n < 3) stored_tail(in, (uint32_t)n, tailS, tailI, put_byte);
     uint32_t tb = 0, kind = 0;
 #ifdef SPNG_D3_PROF
     unsigned long long wwait = 0;
@@ -1490,29 +1562,7 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
         }
         return;
     }
-    if (format == SPNG_FORMAT_ZLIB) {
-        // Adler-32 from the sums the search kernel left (s1 = 1 + S, s2 = N + N * S - I)
-        uint32_t S, I;
-        if (n < 3) {
-            S = tailS; I = tailI;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) { S += __shfl_xor(S, m, 64); I += __shfl_xor(I, m, 64); }
-        } else { S = UNI(state->adlerS); I = UNI(state->adlerI); }
-        S %= 65521; I %= 65521;
-        const uint32_t N = (uint32_t)(n % 65521);
-        const uint32_t sum = ((N + (uint64_t)N * S % 65521 + 65521 - I) % 65521) << 16 | (1 + S) % 65521;
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, sum >> 24, 8, lane); put(s, b, (sum >> 16) & 0xff, 8, lane);
-        put(s, b, (sum >> 8) & 0xff, 8, lane); put(s, b, sum & 0xff, 8, lane);
-    }
-    if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);                // DeflatorOut.pull flushes padding bits
-    drain(s, b, b.total, lane);
-    if (lane == 0) {
-        spng_result &res = results[image];
-        res.status = b.overflow ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE; res.reserved = 0;
-        res.written = b.total; res.consumed = n; res.aux[0] = res.aux[1] = 0;
-        state->done = 1;
-    }
+    finish_stream(s, b, format, n, tailS, tailI, state, results[image], 0, lane);
 }
 
 // ---- levels 0-7, one-shot streams: the blocks side by side (dfl4_walk / dfl4_block / dfl4_scan / dfl4_place) -----------------
@@ -1520,7 +1570,7 @@ __global__ __launch_bounds__(128) void dfl3_parse_kernel(const D3Stream *__restr
 // blocks themselves (2047 terms: symbol counts, two Huffman trees with the reference's heap replayed on one lane, the
 // run-length coded tables, the bits: ~1 M cycles of a latency-bound wave) do not depend on each other at all but for WHERE
 // in the stream their bits go.  So, per round and stream:
-//   * dfl4_walk_kernel: a wave walks the answers (the parser half of dfl3_parse_kernel) and leaves the terms in global memory,
+//   * dfl4_walk_kernel: a wave walks the answers (d3_walk, as dfl3_parse_kernel's parser does) and leaves the terms in global memory,
 //     block after block, with a list of the blocks; the terms of the unfinished block go to the next round in the D1State;
 //   * dfl4_block_kernel: a wave per BLOCK, the whole chip over all blocks of all streams: write_block into a scratch of the
 //     block's own, from bit 0 on; its length in bits;
@@ -1554,99 +1604,25 @@ __global__ __launch_bounds__(64) void dfl4_walk_kernel(const D3Stream *__restric
     uint32_t off = 0, nblk = 0;                                // first term of the block being filled; blocks closed
     for (uint32_t i = (uint32_t)lane; i < count; i += 64) g_wterms[i] = state->terms[i];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    // A block closes when 2047 terms are queued (lazy: 2046 or 2047: a step may queue two), looked at before every step
-    // (DeflatorBuffers.Stream.swift:219, 277): its terms leave for global memory 64 at a time, its place goes into the list.
-    const uint32_t cap = lazy ? 2046u : 2047u;
+    uint32_t *terms = g_wterms;
+    // a closed block: its terms leave for global memory 64 at a time, its place goes into the list
     auto close = [&](bool final) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        for (uint32_t i = (uint32_t)lane; i < count; i += 64) tbuf[off + i] = g_wterms[i];
+        for (uint32_t i = (uint32_t)lane; i < count; i += 64) tbuf[off + i] = terms[i];
         if (lane == 0) { bd[4 + 2 * nblk] = off; bd[5 + 2 * nblk] = count | (final ? 1u << 31 : 0u); }
         off += count; count = 0; nblk += 1;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");   // (every lane has read its terms before the next block's are queued)
     };
-    if (n >= 3) {
-        const uint64_t last_main = n - 4 + 1;                  // positions 0 .. n-4 are searched
-        const uint64_t stop = re < last_main ? re : last_main; // tokens that start below `stop` are this round's
-        // the answers of 128 positions at a time (two per lane), fetched a batch ahead: a wave alone has nobody to hide a load behind
-        auto ask = [&](uint64_t p, uint32_t &m, uint32_t &lit) {
-            m = (p <= re && p < last_main) ? match[p - rb] : 0u;
-            lit = p < n ? (uint32_t)in[p] : 0u;
-        };
-        uint32_t nmA, nmB, nlA, nlB;
-        uint64_t asked = w;
-        ask(w + lane, nmA, nlA); ask(w + 64 + lane, nmB, nlB);
-        while (w < stop) {
-            uint32_t mA, mB, litA, litB;
-            if (asked == w) { mA = nmA; mB = nmB; litA = nlA; litB = nlB; }
-            else { ask(w + lane, mA, litA); ask(w + 64 + lane, mB, litB); }
-            asked = w + 128;                                   // (the guess: the batch is used up to its end -- a run across it asks again)
-            ask(asked + lane, nmA, nlA); ask(asked + 64 + lane, nmB, nlB);
-            // What a position would queue if the walk came by -- its literal, its match (LZ77.DeflatorTerm.init(run:distance:),
-            // DeflatorTerm.swift:34-56) -- is worked out for all 128 at once; the walk itself, one position after the other on the
-            // scalar unit, only picks: a run of positions without a match is one vector store of their literals.
-            auto mterm = [&](uint32_t m) -> uint32_t {
-                const uint32_t run = m >> 16, dist = m & 0xffff;
-                const uint32_t rd = run_decade(run ? run : 3u), dd = dist_decade(dist ? dist : 1u);
-                return dd << 27 | 0x100u | rd | dist_extra_value(dist, dd) << 14 | run_extra_value(run, rd) << 9;
-            };
-            const uint32_t tmA = mterm(mA), tmB = mterm(mB), tlA = 0xf8000000u | litA, tlB = 0xf8000000u | litB;
-            const uint32_t runA = mA >> 16, runB = mB >> 16;
-            const unsigned long long nzA = __ballot(runA != 0), nzB = __ballot(runB != 0);
-            auto at = [&](uint32_t xa, uint32_t xb, uint32_t t) -> uint32_t {
-                return t < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)xa, (int)t) : (uint32_t)__builtin_amdgcn_readlane((int)xb, (int)(t - 64));
-            };
-            // ---- the parse: Stream.compress greedy (:209-252) / lazy (:268-323) over these 128 answers
-            const uint32_t avail = stop - w < 128 ? (uint32_t)(stop - w) : 128u;   // positions of this batch that are this round's
-            uint32_t t = 0;
-            while (t < avail) {
-                if (count >= cap) close(false);
-                // positions from t on without a match
-                uint32_t L;
-                if (t < 64) { const unsigned long long a = nzA >> t; L = a ? (uint32_t)__builtin_ctzll(a) : 64 - t + (nzB ? (uint32_t)__builtin_ctzll(nzB) : 64u); }
-                else { const unsigned long long b2 = nzB >> (t - 64); L = b2 ? (uint32_t)__builtin_ctzll(b2) : 128 - t; }
-                L = L < avail - t ? L : avail - t;
-                if (L) {
-                    L = L < cap - count ? L : cap - count;     // (the block closes in between: the next turn goes on)
-                    const uint32_t qa = (uint32_t)lane, qb = 64u + (uint32_t)lane;
-                    if (qa >= t && qa < t + L) g_wterms[count + qa - t] = tlA;
-                    if (qb >= t && qb < t + L) g_wterms[count + qb - t] = tlB;
-                    count += L; t += L;
-                    continue;
-                }
-                const uint32_t run = at(runA, runB, t);
-                if (lazy) {
-                    // the answer for position w + t + 1 is needed: the next batch starts there if it is not in this one
-                    if (t + 1 >= 128) break;
-                    // lazy match at a + 1 (:293-299); it exists only if that position is still searched
-                    const uint32_t lrun = at(runA, runB, t + 1);
-                    if (lrun > run) {
-                        const uint32_t a0 = at(tlA, tlB, t), a1 = at(tmA, tmB, t + 1);
-                        if (lane == 0) { g_wterms[count] = a0; g_wterms[count + 1] = a1; }
-                        count += 2; t += 1 + lrun;
-                        continue;
-                    }
-                }
-                const uint32_t a0 = at(tmA, tmB, t);
-                if (lane == 0) g_wterms[count] = a0;
-                count += 1; t += run;
-            }
-            w = uni64(w + t);
-        }
-    } else w = n;
+    auto close_block = [&] { close(false); };
+    w = n >= 3 ? d3_walk(in, n, match, rb, re, lazy, w, terms, count, lane, close_block) : n;
     const bool last = !(re < E);
     if (!last) {
         // on with the next round: the unfinished block's terms and the position into the state
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        for (uint32_t i = (uint32_t)lane; i < count; i += 64) state->terms[i] = g_wterms[i];
+        for (uint32_t i = (uint32_t)lane; i < count; i += 64) state->terms[i] = terms[i];
         if (lane == 0) { state->w = w; state->count = count; state->rb = re; state->re = re + D3_RV < E ? re + D3_RV : E; }
     } else if (n >= 3) {
-        // epilogue: the positions still in the window pipeline become literals (:254-265, :331-342), then the final block
-        for (uint64_t p = w; p < n; ++p) {
-            if (count >= 2047u) close(false);
-            const uint32_t t = 0xf8000000u | UNI(in[p]);
-            if (lane == 0) g_wterms[count] = t;
-            count += 1;
-        }
+        d3_walk_epilogue(in, n, w, terms, count, lane, close_block);
         close(true);
     }
     if (lane == 0) { bd[0] = nblk; bd[1] = last ? 1u : 0u; bd[2] = (uint32_t)rb; bd[3] = (uint32_t)(rb >> 32); }
@@ -1691,19 +1667,8 @@ __global__ __launch_bounds__(256) void dfl4_scan_kernel(const D3Stream *__restri
     if (tid == 0) {
         if (rb == 0 && state->total == 0 && state->nacc == 0) {
             // the stream's first round: its header
-            uint8_t hdr[10]; uint32_t hn = 0;
-            if (st.format == SPNG_FORMAT_ZLIB) {
-                // StreamHeader.write (StreamHeader.swift:56-62)
-                const uint32_t unpaired = (st.exponent - 8) << 4 | 0x08;
-                const uint32_t check = ~(((unpaired << 8 | unpaired >> 8) & 0xffff) % 31) & 31;
-                hdr[0] = (uint8_t)unpaired; hdr[1] = (uint8_t)check; hn = 2;
-            } else if (st.format == SPNG_FORMAT_GZIP) {
-                // Gzip.StreamHeader.write (Gzip.StreamHeader.swift:84-96); the trailer is appended by gzip.hip
-                const uint8_t g[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
-                for (int i = 0; i < 10; ++i) hdr[i] = g[i];
-                hn = 10;
-            }
-            for (uint32_t i = 0; i < hn; ++i) if (i < cap) dst[i] = hdr[i];
+            uint64_t hn = 0;
+            stream_header(st.format, st.exponent, [&](uint32_t v) { if (hn < cap) dst[hn] = (uint8_t)v; ++hn; });
             state->total = hn;
         }
         shared_p0 = state->total * 8 + state->nacc;
@@ -1729,22 +1694,12 @@ __global__ __launch_bounds__(256) void dfl4_scan_kernel(const D3Stream *__restri
     state->total = pend >> 3; state->nacc = (uint32_t)(pend & 7);
     if (!last) return;
     uint64_t written = (pend + 7) >> 3;                        // DeflatorOut.pull flushes padding bits
-    uint32_t S = state->adlerS % 65521, I = state->adlerI % 65521;
-    if (n < 3) {
-        // Stream.compressBlocks stored tail (:45-60, :417-434): no block was queued; the bytes by hand (the header ends on a byte)
-        uint8_t t[8]; uint32_t tn = 0;
-        t[tn++] = 1; t[tn++] = (uint8_t)n; t[tn++] = 0; t[tn++] = (uint8_t)~n; t[tn++] = 0xff;
-        S = 0; I = 0;
-        for (uint64_t k = 0; k < n; ++k) { t[tn++] = st.src[k]; S += st.src[k]; I += (uint32_t)k * st.src[k]; }
-        for (uint32_t i = 0; i < tn; ++i) if (written + i < cap) dst[written + i] = t[i];
-        written += tn;
-    }
+    auto store_byte = [&](uint32_t v) { if (written < cap) dst[written] = (uint8_t)v; ++written; };
+    uint32_t S = state->adlerS, I = state->adlerI;
+    if (n < 3) stored_tail((const gbyte *)st.src, (uint32_t)n, S, I, store_byte);   // (no block was queued; the header ends on a byte)
     if (st.format == SPNG_FORMAT_ZLIB) {
-        // Adler-32 from the sums the search kernel left (s1 = 1 + S, s2 = N + N * S - I)
-        const uint32_t N = (uint32_t)(n % 65521);
-        const uint32_t sum = ((N + (uint64_t)N * S % 65521 + 65521 - I) % 65521) << 16 | (1 + S) % 65521;
-        for (int i = 0; i < 4; ++i) if (written + i < cap) dst[written + i] = (uint8_t)(sum >> (24 - 8 * i));
-        written += 4;
+        const uint32_t sum = adler32_word(S, I, n);
+        for (int i = 24; i >= 0; i -= 8) store_byte(sum >> i);
     }
     spng_result &res = results[st.image];
     res.status = (over || written > cap) ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE; res.reserved = 0;
@@ -2401,17 +2356,9 @@ __global__ __launch_bounds__(64) void dfl2_parse_kernel(const D2Stream *__restri
     uint32_t limit = UNI(state->limit);
     bool generic = UNI(state->generic) != 0;
     const uint64_t rb = uni64(state->rb), re = uni64(state->re);
+    auto put_byte = [&, lane](uint32_t v) { put(s, b, v, 8, lane); };
     if (pos == 0 && b.total == 0 && b.nacc == 0) {
-        // the stream's first round
-        if (format == SPNG_FORMAT_ZLIB) {
-            // StreamHeader.write (StreamHeader.swift:56-62)
-            const uint32_t unpaired = (UNI(sp->exponent) - 8) << 4 | 0x08;
-            const uint32_t check = ~(((unpaired << 8 | unpaired >> 8) & 0xffff) % 31) & 31;
-            put(s, b, check << 8 | unpaired, 16, lane);
-        } else if (format == SPNG_FORMAT_GZIP) {
-            // Gzip.StreamHeader.write (Gzip.StreamHeader.swift:84-96); the trailer is appended by gzip.hip
-            put(s, b, 0x8b1f, 16, lane); put(s, b, 0x0008, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0, 16, lane); put(s, b, 0xff00, 16, lane);
-        }
+        stream_header(format, UNI(sp->exponent), put_byte);    // the stream's first round
         for (uint32_t i = lane; i < 542; i += 64) g_full.depths[i] = (uint8_t)depth_default(i);
     } else {
         for (uint32_t i = lane; i < 542; i += 64) g_full.depths[i] = state->depths[i];
@@ -2421,12 +2368,7 @@ __global__ __launch_bounds__(64) void dfl2_parse_kernel(const D2Stream *__restri
     uint32_t tailS = 0, tailI = 0;
     if (n < 3 && more) {}                                      // (nothing can be decided yet)
     else if (n < 3) {
-        // Stream.compressBlocks stored tail (:45-60, :417-434)
-        put(s, b, 1, 3, lane);
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-        put(s, b, (uint32_t)n, 16, lane); put(s, b, ~(uint32_t)n & 0xffff, 16, lane);
-        for (uint64_t k = 0; k < n; ++k) put(s, b, in[k], 8, lane);
-        if ((uint64_t)lane < n) { tailS = in[lane]; tailI = (uint32_t)lane * in[lane]; }
+        stored_tail(in, (uint32_t)n, tailS, tailI, put_byte);
         pos = n;
     } else {
         while (pos < re) {
@@ -2440,33 +2382,11 @@ __global__ __launch_bounds__(64) void dfl2_parse_kernel(const D2Stream *__restri
         }
     }
     if (!more && pos >= n) {
-        if (format == SPNG_FORMAT_ZLIB) {
-            // Adler-32 from the sums the search kernel left (s1 = 1 + S, s2 = N + N * S - I)
-            uint32_t S, I;
-            if (n < 3) {
-                S = tailS; I = tailI;
-#pragma unroll
-                for (int m = 32; m >= 1; m >>= 1) { S += __shfl_xor(S, m, 64); I += __shfl_xor(I, m, 64); }
-            } else { S = UNI(state->adlerS); I = UNI(state->adlerI); }
-            S %= 65521; I %= 65521;
-            const uint32_t N = (uint32_t)(n % 65521);
-            const uint32_t sum = ((N + (uint64_t)N * S % 65521 + 65521 - I) % 65521) << 16 | (1 + S) % 65521;
-            if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);
-            put(s, b, sum >> 24, 8, lane); put(s, b, (sum >> 16) & 0xff, 8, lane);
-            put(s, b, (sum >> 8) & 0xff, 8, lane); put(s, b, sum & 0xff, 8, lane);
-        }
-        if (b.nacc) put(s, b, 0, 8 - b.nacc, lane);            // DeflatorOut.pull flushes padding bits
-        drain(s, b, b.total, lane);
+        finish_stream(s, b, format, n, tailS, tailI, state, results[UNI(sp->image)], 1, lane);
 #ifdef SPNG_DEFLATE_PROF
         if (lane == 0 && blockIdx.x == 0) printf("dfl2_parse prof Mcycles (last round, from %llu): other %llu skip-rule %llu forward %llu backward %llu trees %llu tables %llu emit %llu; offers %llu long %llu\n",
             (unsigned long long)rb, g_prof[0] >> 20, g_prof[1] >> 20, g_prof[2] >> 20, g_prof[3] >> 20, g_prof[4] >> 20, g_prof[5] >> 20, g_prof[6] >> 20, g_prof[9] >> 20, g_prof[10] >> 20);
 #endif
-        if (lane == 0) {
-            spng_result &res = results[UNI(sp->image)];
-            res.status = b.overflow ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE; res.reserved = 1;
-            res.written = b.total; res.consumed = n; res.aux[0] = res.aux[1] = 0;
-            state->done = 1;
-        }
         return;
     }
 #ifdef SPNG_DEFLATE_PROF
@@ -2530,12 +2450,7 @@ __global__ void dfl2_advance_kernel(const D2Stream *__restrict__ streams, uint32
     const uint64_t n = st.src_len, end = t.sre;
     const bool more = st.more != 0;
     if (n < 3 || end == t.spos) return;
-    uint32_t lim = t.slimit;
-    for (uint64_t at = t.spos; at < end;) {
-        const uint64_t size = (uint64_t)(lim - 1) < end - at ? (uint64_t)(lim - 1) : end - at;
-        at += size;
-        if (more || at < n) lim = 2 * lim < (1u << 21) ? 2 * lim : 1u << 21;
-    }
+    const uint32_t lim = d2_round_limit(t.spos, end, t.slimit, n, more);
     t.spos = end; t.slimit = lim;
     t.srb = end; t.sre = (!more && end >= n) ? end : d2_round_end(end, lim, n, more);
 }

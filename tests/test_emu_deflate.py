@@ -152,6 +152,26 @@ def test_emulated_greedy_lazy_pushes_give_the_one_shot_stream(emu_small_rounds, 
     assert r.returncode == 0, (cuts, r.stdout[-300:], r.stderr[-300:])
 
 
+@pytest.mark.parametrize("level", [0, 4, 9])
+def test_emulated_stream_envelope_matrix(emu, tmp_path, level):
+    """header, stored tail, Adler-32, padding and result of every parse kernel -- dfl4_scan (one-shot, levels 0-7), the dfl3 writer
+    (EMU_TWO_WAVE; a cut at 1: the first call cannot decide anything yet), dfl2_parse (level 9) -- on inputs of 0 ... 4 bytes,
+    both sides of the stored tail's limit of 3: zlib at the window exponents 15 and 8, and raw"""
+    for n in range(5):
+        data = bytes(range(65, 65 + n))
+        (tmp_path / "in").write_bytes(data)
+        for fmt, exponent in ((0, 15), (0, 8), (1, 15)):
+            (tmp_path / "want").write_bytes(ph.orc_deflate(data, level, fmt, exponent))
+            for env, cuts in (({}, []), ({"EMU_TWO_WAVE": "1"}, []), ({}, ["1"])):
+                if cuts and n < 2:
+                    continue
+                r = subprocess.run([str(emu), str(tmp_path / "in"), str(tmp_path / "want"), str(level), str(fmt), "2"] + cuts, capture_output=True,
+                                   text=True, timeout=900, env=dict(os.environ, EMU_EXPONENT=str(exponent), **env))
+                assert r.returncode == 0, (n, level, fmt, exponent, env, cuts, r.stdout[-300:], r.stderr[-300:])
+                assert r.stdout.startswith("ok:")
+                assert ("blocks side by side" in r.stdout) == (level < 8 and not env and not cuts)
+
+
 def test_emulated_search_window_wraps_its_ring(emu, tmp_path):
     """the search's window is a ring of 36864 positions in LDS: 90 KB in one chunk wrap it twice, with matches 32760 bytes back
     (the far end of the window, read through the mirrored bytes behind the ring's end) -- level 9 records and level 6 answers"""

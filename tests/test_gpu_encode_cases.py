@@ -81,6 +81,36 @@ def test_gzip_members_of_the_table(gpu):
         assert got == expected and gzip.decompress(got) == data, (name, lv)
 
 
+def test_stream_envelope_matrix(gpu):
+    """header, stored tail, Adler-32, padding and result of every parse kernel on inputs of 0 ... 4 bytes, both sides of the stored
+    tail's limit of 3, greedy / lazy / full, zlib at the window exponents 15 and 8, raw and gzip: all one-shot streams in ONE call
+    (dfl4_scan_kernel, dfl2_parse_kernel), then each pushed whole and a byte per push (the dfl3 writer, dfl2_parse_kernel with a state)"""
+    from test_gpu_resume import _push_deflate
+    from test_oracle_gzip import gw, raw_deflate
+    s = gpu.load()
+    plan = [(bytes(range(65, 65 + n)), lv, fmt, e) for n in range(5) for lv in (0, 4, 9)
+            for fmt, e in ((spng.FORMAT_ZLIB, 15), (spng.FORMAT_ZLIB, 8), (spng.FORMAT_IOS, 15), (spng.FORMAT_GZIP, 15))]
+
+    def expected(data, lv, fmt, e):
+        return gw.deflate(data, raw_deflate(lv)) if fmt == spng.FORMAT_GZIP else ph.orc_deflate(data, lv, 1 if fmt == spng.FORMAT_IOS else 0, e)
+
+    outs, res = s.deflate_batch([s.to_device(d) for d, _, _, _ in plan], None, [f for _, _, f, _ in plan], levels=[lv for _, lv, _, _ in plan],
+                                exponents=[e for _, _, _, e in plan])
+    for (data, lv, fmt, e), o, r in zip(plan, outs, res):
+        exp = expected(data, lv, fmt, e)
+        assert (r.status, r.written, r.consumed) == (gpu.DONE, len(exp), len(data)), (len(data), lv, fmt, e, r.status, r.written, r.consumed)
+        assert bytes(o[:r.written].cpu().numpy()) == exp, (len(data), lv, fmt, e)
+        if fmt == spng.FORMAT_GZIP:
+            assert gzip.decompress(exp) == data
+    for data, lv, fmt, e in plan:
+        exp = expected(data, lv, fmt, e)
+        for sizes in ([max(len(data), 1)], [1]):
+            # (_push_deflate asserts NEED_MORE_INPUT of every push but the last, DONE and consumed == len(data) of the last; what it
+            #  returns are the `written` bytes of the last)
+            got, avail = _push_deflate(s, data, sizes, lv, fmt, e)
+            assert got == exp and avail[-1] == len(exp), (len(data), lv, fmt, e, sizes)
+
+
 GEOMETRY = [n for n in ec.NAMES if n.startswith(("chunk-edge-", "edge-e15-"))]
 
 

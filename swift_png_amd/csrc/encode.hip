@@ -9,15 +9,9 @@
 // (:186-193) does.  Only the winning candidate is written (filter byte + pitch bytes).
 #include "common.hpp"
 #include "geometry.hpp"
+#include "scanline.hpp"
 
 namespace spng {
-
-__device__ __forceinline__ uint32_t paeth_u(uint32_t a, uint32_t b, uint32_t c)
-{
-    // PNG.paeth, PNG.swift:124-147
-    int pa = abs((int)b - (int)c), pb = abs((int)a - (int)c), pc = abs((int)a + (int)b - 2 * (int)c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
 
 // byte j of the gathered scanline y of a (sub-)image: PNG.Image.collect (PNG.Image.swift:431-544)
 __device__ __forceinline__ uint32_t raw_byte(const FilterJob &job, uint32_t y, uint32_t j, bool direct,
@@ -53,11 +47,6 @@ __device__ __forceinline__ uint32_t abs8(uint32_t v)   // |Int8(bitPattern:)|, P
 // second pair of loads.  All five residuals are formed with byte-SWAR arithmetic in registers
 // (v_lerp_u8 for Average, packed-i16 Paeth), scored with v_sad_u8; only the winner is recomputed
 // and stored.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-struct __attribute__((packed)) U128u { u32x4 v; };
-
-__device__ __forceinline__ uint32_t opaque(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ uint32_t sub8(uint32_t x, uint32_t p)              // per-byte x - p (mod 256)
 {
     constexpr uint32_t Hb = 0x80808080u;
@@ -96,10 +85,6 @@ __device__ __forceinline__ uint32_t paeth8(uint32_t a, uint32_t b, uint32_t c)  
     const uint32_t lo = paeth_pk16(a & M, b & M, c & M);
     const uint32_t hi = paeth_pk16((a >> 8) & M, (b >> 8) & M, (c >> 8) & M);
     return lo | hi << 8;
-}
-__device__ __forceinline__ uint32_t lane_above(uint32_t mine, uint32_t first)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)mine, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
 }
 // the 16 bytes that start BPP bytes before `x`, given the 8 bytes (pz, pw) that precede x
 template <int BPP>
@@ -283,7 +268,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const FilterJob *__restrict
                 sc[1] += abs8(x - a);
                 sc[2] += abs8(x - b);
                 sc[3] += abs8(x - ((a + b) >> 1));
-                sc[4] += abs8(x - paeth_u(a, b, c));
+                sc[4] += abs8(x - paeth(a, b, c));
             }
 #pragma unroll
             for (int f = 0; f < 5; ++f)
@@ -300,7 +285,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const FilterJob *__restrict
                 if (best == 1) pred = a;
                 else if (best == 2) pred = b;
                 else if (best == 3) pred = (a + b) >> 1;
-                else if (best == 4) pred = paeth_u(a, b, c);
+                else if (best == 4) pred = paeth(a, b, c);
                 out[1 + j] = (uint8_t)(x - pred);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");     // (the next row of this wave packs over these)
@@ -316,7 +301,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const FilterJob *__restrict
             sc[1] += abs8(x - a);
             sc[2] += abs8(x - b);
             sc[3] += abs8(x - ((a + b) >> 1));
-            sc[4] += abs8(x - paeth_u(a, b, c));
+            sc[4] += abs8(x - paeth(a, b, c));
         }
 #pragma unroll
         for (int f = 0; f < 5; ++f)
@@ -336,7 +321,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const FilterJob *__restrict
             if (best == 1) pred = a;
             else if (best == 2) pred = b;
             else if (best == 3) pred = (a + b) >> 1;
-            else if (best == 4) pred = paeth_u(a, b, c);
+            else if (best == 4) pred = paeth(a, b, c);
             out[1 + j] = (uint8_t)(x - pred);
         }
     }

@@ -73,6 +73,28 @@ inline UnfilterPieces unfilter_pieces(uint32_t k, uint64_t total_rows, uint32_t 
 // narrower ones -- wide tiles cost rows of 512 bytes a third and save rows of 4 KiB a sixth: profiles/r06_tuning.md 14
 inline bool unfilter_wide_tiles(uint32_t k, uint64_t widest) { return (k == 1 || k == 2) && widest >= WIDE_ROW; }
 
+// ---- unfilter: the hand-over between the bands of a piece --------------------------------------------------------------
+// The nw waves of a workgroup take the bands of a piece in turn (band j: wave j % nw) and each counts the steps it has completed,
+// over all of its bands, per_band to a band.  Step `step` of a band reads the last row of the band above as the steps
+// step .. step + reach of that band left it (reach: how many producer steps a consumer step reaches into -- Cfg::K tiles of
+// unfilter_kernel's skewed windows, one phase of unfilter_pk_kernel, whose tile T is stored at the end of phase T + 1).
+// -> the count the producing wave must have published before step `step` of `band` (>= 1) may be loaded.
+constexpr uint32_t band_steps_needed(uint32_t band, uint32_t step, uint32_t nw, uint32_t per_band, uint32_t reach)
+{
+    return (band - 1) / nw * per_band + (step + reach < per_band ? step + reach : per_band - 1) + 1;
+}
+// A wave in the last step of a band may WAIT for the first step of its next band only if that wait cannot close a circle.
+// Every wave in between may itself be waiting, in front of its staged step with only the steps before it published, so each hop
+// from band to band reaches back reach + 1 steps, and nw hops end at step nw * (reach + 1) - 1 of the waiting wave's own current
+// band: that step must lie in front of the last one, which is the one it has not published.  (The first form of this bound,
+// nw * reach + 1 < per_band, hung a workgroup for good: tests/test_emu_unfilter.py "one long piece".)  Shorter rows do not
+// prefetch across the band; what that costs them has not been measured.
+// By that count alone nw * (reach + 1) < per_band would do: the bound asks for one step more, as both kernels' own bounds did
+// before they became this one.  Nothing in the tests tells the two apart -- the cases at the very edge ("9 phases" / "10 phases",
+// "13 tiles" / "14 tiles") pass even with the first form, and only the "one long piece" and "pieces only where None / Sub
+// allow" cases catch a bound that is too loose -- so the edge cases are no licence to take the step of slack away.
+constexpr bool band_may_wait(uint32_t nw, uint32_t reach, uint32_t per_band) { return nw * (reach + 1) + 1 < per_band; }
+
 // ---- workgroups along x ------------------------------------------------------------------------------------------
 // filter_kernel: a workgroup is four waves, a row per wave; images taller than the grid loop.
 constexpr uint32_t FILTER_ROWS_PER_BLOCK = 4, FILTER_BLOCKS_MAX = 4096;

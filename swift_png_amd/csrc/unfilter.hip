@@ -5,7 +5,9 @@
 // PNG.Decoder.push (:59-140).  Byte arithmetic is u8 wrap-around exactly as in the reference.
 //
 // Two kernels: `unfilter_pk_kernel` (bpp 4 and 8: RGBA8, VA16, RGBA16 -- the formats of every BASELINE config; second half
-// of this file) and `unfilter_kernel`, the byte-wise form for bpp 1, 2, 3 and 6, described first:
+// of this file) and `unfilter_kernel`, the byte-wise form for bpp 1, 2, 3 and 6.  They differ in how a tile lies in LDS and in
+// the arithmetic of a step; the rows there are, the pieces of a chain and the pipeline of a piece's bands over the waves of a
+// workgroup are one piece of code in front of both (rows_available, piece_start, BandProgress, band_pipeline).  The byte-wise form:
 //
 // Parallelisation.  Pixel (x, y) of a sub-image depends on (x-1, y), (x, y-1) and (x-1, y-1), so
 // the dependency DAG is a 2-D wavefront.  One wave (64 lanes) owns a band of 64 consecutive rows:
@@ -29,11 +31,9 @@
 // bank-conflict free.
 #include "common.hpp"
 #include "geometry.hpp"
+#include "scanline.hpp"
 
 namespace spng {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-struct __attribute__((packed)) U128u { u32x4 v; };       // 16 bytes, alignment 1
 
 #ifndef SPNG_UNF_NW
 #define SPNG_UNF_NW 4                                    // waves per scanline chain
@@ -113,19 +113,6 @@ __device__ __forceinline__ void store_window(uint8_t *p, int64_t off, int64_t pi
     }
 }
 
-// PNG.paeth (PNG.swift:124-147): a if pa <= pb && pa <= pc, else b if pb <= pc, else c.
-__device__ __forceinline__ uint32_t paeth(uint32_t a, uint32_t b, uint32_t c)
-{
-    int pa = abs((int)b - (int)c), pb = abs((int)a - (int)c), pc = abs((int)a + (int)b - 2 * (int)c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
-// value of lane-1 (lane 0 receives `top`)
-__device__ __forceinline__ uint32_t from_lane_above(uint32_t mine, uint32_t top)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)top, (int)mine, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-
 __device__ __forceinline__ bool skip_status(int32_t s)
 {
     // the reference assigns no rows in a push whose inflate threw (PNG.Decoder.swift:57)
@@ -145,7 +132,7 @@ __device__ __forceinline__ void reconstruct_generic(uint8_t *tile, int rowb, int
         const bool interior = ux0 + t > 0;               // unit 0 has no left / upper-left neighbour
         uint32_t b[BPP];
 #pragma unroll
-        for (int k = 0; k < BPP; ++k) b[k] = from_lane_above(o[k], tile[t * BPP + k]);
+        for (int k = 0; k < BPP; ++k) b[k] = lane_above(o[k], tile[t * BPP + k]);
 #pragma unroll
         for (int k = 0; k < BPP; ++k) {
             const uint32_t a = interior ? o[k] : 0u;
@@ -175,7 +162,7 @@ __device__ __forceinline__ void reconstruct_subunit(uint8_t *tile, int rowb, int
 #pragma unroll 2
     for (int t = 0; t < P; ++t) {
         const bool interior = ux0 + t > 0;               // unit 0's first pixel has no left / upper-left neighbour
-        const uint32_t b4 = from_lane_above(o, *(const uint32_t *)(tile + 4 * t));
+        const uint32_t b4 = lane_above(o, *(const uint32_t *)(tile + 4 * t));
         const uint32_t x4 = *(const uint32_t *)(mine + 4 * t);
         uint32_t a[PX], c[PX];
 #pragma unroll
@@ -202,8 +189,6 @@ __device__ __forceinline__ void reconstruct_subunit(uint8_t *tile, int rowb, int
 // ---- reconstruction of one tile: 4 or 8 bytes per unit, two packed-u16 halves per dword ------
 // even bytes live in `lo` (x & 0x00ff00ff), odd bytes in `hi` ((x >> 8) & 0x00ff00ff); sums of two
 // bytes cannot carry across the 16-bit lanes, signed differences use the packed-i16 VALU ops.
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t opaque(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ uint32_t paeth_pk(uint32_t a, uint32_t b, uint32_t c)
 {
     const s16x2 va = __builtin_bit_cast(s16x2, a), vb = __builtin_bit_cast(s16x2, b), vc = __builtin_bit_cast(s16x2, c);
@@ -264,7 +249,7 @@ __device__ __forceinline__ void reconstruct_packed(uint8_t *tile, int rowb, int 
 #pragma unroll
             for (int d = 0; d < DW; ++d) {
                 // (lane 0: the row above the band, straight out of the tile's first LDS row -- its window is not skewed)
-                const uint32_t b = from_lane_above(o[d], cut(t, j, d));
+                const uint32_t b = lane_above(o[d], cut(t, j, d));
                 uint32_t p = (o[d] & m_sub) | (b & m_up) | (__builtin_amdgcn_lerp(o[d], b, 0u) & m_avg);
                 const uint32_t b_lo = __builtin_amdgcn_perm(0u, b, SEL_LO), b_hi = __builtin_amdgcn_perm(0u, b, SEL_HI);
                 if (PAETH) p |= (paeth_pk(a_lo[d], b_lo, c_lo[d]) | paeth_pk(a_hi[d], b_hi, c_hi[d]) << 8) & m_pae;
@@ -300,6 +285,131 @@ __device__ __forceinline__ void reconstruct_packed(uint8_t *tile, int rowb, int 
     }
 }
 
+// =====================================================================================================================
+// What both kernels share: the rows there are, where a piece starts, and the pipeline of a piece's bands over the waves
+// =====================================================================================================================
+// a short stream silently yields an incomplete image (PNG.Decoder.swift:88-94)
+__device__ __forceinline__ uint32_t rows_available(const UnfJob &job)
+{
+    if (!job.rows_len) return job.rows;
+    const uint64_t len = *job.rows_len;
+    const uint64_t avail = len > job.stream_off ? (len - job.stream_off) / job.in_stride : 0;
+    return avail < job.rows ? (uint32_t)avail : job.rows;
+}
+
+// A chain is cut into pieces that different workgroups (unfilter_pk_kernel: different ramps of a wave) take: a row filtered with
+// None or Sub does not look at the row above (PNG.Decoder.swift:160-168), so a piece may start there as if it were a first
+// row.  Piece q owns the rows from the first such row at or after q * sb_rows up to the first one at or after (q + 1) * sb_rows.
+// (The filter bytes are never written, also when rows are defiltered in place.)
+// -> the first row at or behind x that is filtered with None or Sub, 64 rows per ballot; `rows` if there is none
+__device__ __forceinline__ uint32_t piece_start(const UnfJob &job, uint32_t rows, int lane, uint64_t x)
+{
+    if (x == 0) return 0;
+    for (uint64_t r0 = x; r0 < rows; r0 += 64) {
+        const uint64_t r = r0 + lane;
+        const uint32_t ft = r < rows ? job.in[r * job.in_stride] : 0u;
+        const unsigned long long m = __ballot(r < rows && ft <= 1);
+        if (m) return (uint32_t)(r0 + __ffsll((long long)m) - 1);
+    }
+    return rows;
+}
+
+// The progress of a workgroup's NW waves through the bands of a piece.  `done[w]` (LDS) counts the steps wave w has completed
+// over all of its bands, per_band to a band, and is published only when their stores have drained: the band below reads the last
+// row of a band back from the output raster.  reach: how many producer steps a consumer step reaches into (geometry.hpp,
+// band_steps_needed, where the arithmetic lives so that the tests call it).
+template <int NW> struct BandProgress {
+    uint32_t *done;
+    uint32_t per_band, reach;
+    int wave, lane;
+    // has the wave above got far enough for step `step` of `band` to be loaded?
+    __device__ __forceinline__ bool ready(uint32_t band, uint32_t step) const
+    {
+        if (!band) return true;
+        const uint32_t need = band_steps_needed(band, step, NW, per_band, reach);
+        return __hip_atomic_load(&done[(band - 1) % NW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= need;
+    }
+    __device__ __forceinline__ void wait(uint32_t band, uint32_t step) const
+    {
+        SpinGuard guard;
+        while (!ready(band, step)) {
+            __builtin_amdgcn_s_sleep(8);
+            guard.tick();
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    // drain this wave's stores, then tell the others that `count` steps are complete
+    __device__ __forceinline__ void publish(uint32_t count) const
+    {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0 && count) __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    // Blocking in `band` for a step of band `next` is deadlock-free only if nothing the awaited step depends on is a step this
+    // wave has not published yet.  Same band: the chain of producers ends in this wave's band before, which is complete and, the
+    // pending step published in front of the wait, known to be.  Next band (we are in the last step of the current one): only rows
+    // long enough for the circle through the other waves not to close -- band_may_wait, geometry.hpp.
+    __device__ __forceinline__ bool may_wait(uint32_t band, uint32_t next) const
+    {
+        return NW > 1 && next && (next == band || band_may_wait(NW, reach, per_band));
+    }
+};
+
+// The bands of a piece, pipelined over the waves: wave w takes bands w, w + NW, ... and walks each in `per_band` steps.  The
+// kernel's own stages: begin(band) -- the band's filter types and carries; issue(band, tile) -- the loads of a tile into staging
+// registers; commit(tile) -- the staged tile to LDS; compute(band, step); store(band, tile) -- a finished tile to the output.
+// `loaded` tiles are loaded per band, one in each of the first steps, and tile step - (per_band - loaded) is finished by a step:
+// unfilter_kernel loads a tile in every step and stores it in the same step, unfilter_pk_kernel walks one step more than it
+// loads tiles and stores tile T - 1 in step T.  No workgroup barriers.
+template <int NW, class Begin, class Issue, class Commit, class Compute, class Store>
+__device__ __forceinline__ void band_pipeline(const BandProgress<NW> p, uint32_t nbands, uint32_t loaded,
+                                              Begin begin, Issue issue, Commit commit, Compute compute, Store store)
+{
+    const uint32_t per_band = p.per_band, lag = per_band - loaded;
+    uint32_t count = 0;                                  // steps this wave has completed
+    bool staged = false;                                 // the staging registers hold the tile about to be committed
+    for (uint32_t band = p.wave; band < nbands; band += NW) {
+        begin(band);
+        for (uint32_t T = 0; T < per_band; ++T) {
+            if (T < loaded) {
+                if (!staged) { p.wait(band, T); issue(band, T); }
+                commit(T);
+            }
+            staged = false;
+            // prefetch the next tile of this wave while this step is worked on.  If its producer (another wave) is not far
+            // enough ahead yet, fall back behind it *now*: publish what is pending and wait, so that from here on the prefetch
+            // always overlaps the arithmetic.  (A band's last tile is followed by the first one of the wave's next band, which is
+            // prefetched in the band's last step.)
+            uint32_t nb = band, nT = T + 1;
+            if (nT >= loaded) { nb = band + NW; nT = 0; }
+            if (nb < nbands && (T + 1 < loaded || T + 1 == per_band)) {
+                bool ok = p.ready(nb, nT);
+                if (!ok && p.may_wait(band, nb)) {
+                    p.publish(count);
+                    p.wait(nb, nT);
+                    ok = true;
+                }
+                if (ok) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    issue(nb, nT);
+                    staged = true;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // LDS tile written before it is read
+            compute(band, T);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+
+            // The stores of the previous step (and the prefetch loads) have had the whole reconstruction to complete: drain,
+            // then publish the previous step.  Publishing one step late keeps the store latency off the critical path.
+            p.publish(count);
+            if (T >= lag) store(band, T - lag);
+            ++count;
+            // a tile that could not be prefetched depends on this step (or a later one): publish now
+            if (!staged) p.publish(count);
+        }
+    }
+    p.publish(count);                                    // last step of this wave
+}
+
 template <int BPP, int PX = BPP, int PT = 0>
 __global__ __launch_bounds__(SPNG_UNF_NW * 64) void unfilter_kernel(const UnfJob *__restrict__ jobs,
                                                                      const spng_result *__restrict__ results,
@@ -309,7 +419,7 @@ __global__ __launch_bounds__(SPNG_UNF_NW * 64) void unfilter_kernel(const UnfJob
     static_assert(PX == BPP || (BPP == 4 && (PX == 1 || PX == 2)), "sub-unit pixels ride in dwords");
     constexpr int NW = SPNG_UNF_NW;
     __shared__ __attribute__((aligned(16))) uint8_t tiles[NW][65 * C::ROWB];
-    __shared__ uint32_t done[NW];                        // tiles completed by each wave
+    __shared__ uint32_t done[NW];                        // tiles completed by each wave (BandProgress)
 
     UnfJob job = jobs[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -317,33 +427,14 @@ __global__ __launch_bounds__(SPNG_UNF_NW * 64) void unfilter_kernel(const UnfJob
     if (threadIdx.x < NW) done[threadIdx.x] = 0;
     __syncthreads();
 
-    uint32_t rows = job.rows;
-    if (job.rows_len) {
-        // a short stream silently yields an incomplete image (PNG.Decoder.swift:88-94)
-        const uint64_t len = *job.rows_len;
-        const uint64_t avail = len > job.stream_off ? (len - job.stream_off) / job.in_stride : 0;
-        rows = avail < rows ? (uint32_t)avail : rows;
-    }
-    // A chain is cut into pieces that different workgroups take: a row filtered with None or Sub does not
-    // look at the row above (PNG.Decoder.swift:160-168), so a piece may start there as if it were a first
-    // row.  Workgroup y owns the rows from the first such row at or after y * sb_rows up to the first one at
-    // or after (y + 1) * sb_rows.  (The filter bytes are never written, also when rows are defiltered in place.)
+    uint32_t rows = rows_available(job);
+    // Workgroup y owns piece y of the chain (piece_start).
     // (rows that arrived with a later push, spng_unfilter_resume_batch: the row above the first one was defiltered by an
     //  earlier call and sits in front of `out`)
     bool has_top = job.has_prev != 0;
     if (gridDim.y > 1) {
-        auto cut = [&](uint64_t x) -> uint32_t {
-            if (x == 0) return 0;
-            for (uint64_t r0 = x; r0 < rows; r0 += 64) {
-                const uint64_t r = r0 + lane;
-                const uint32_t ft = r < rows ? job.in[r * job.in_stride] : 0u;
-                const unsigned long long m = __ballot(r < rows && ft <= 1);
-                if (m) return (uint32_t)(r0 + __ffsll((long long)m) - 1);
-            }
-            return rows;
-        };
-        const uint32_t first = cut((uint64_t)blockIdx.y * sb_rows);
-        const uint32_t last = blockIdx.y + 1 == gridDim.y ? rows : cut((uint64_t)(blockIdx.y + 1) * sb_rows);
+        const uint32_t first = piece_start(job, rows, lane, (uint64_t)blockIdx.y * sb_rows);
+        const uint32_t last = blockIdx.y + 1 == gridDim.y ? rows : piece_start(job, rows, lane, (uint64_t)(blockIdx.y + 1) * sb_rows);
         if (first >= last) return;
         if (first) has_top = false;                            // (a piece behind the first starts on a row that looks at nothing above)
         job.in += (uint64_t)first * job.in_stride;
@@ -374,7 +465,7 @@ __global__ __launch_bounds__(SPNG_UNF_NW * 64) void unfilter_kernel(const UnfJob
             Rtop = load_window_l2(job.out + ((int64_t)band * 64 - 1) * (int64_t)job.out_stride,
                                   (int64_t)T * C::TB + 16 * lane, pitch);
     };
-    auto commit = [&]() {
+    auto commit = [&](uint32_t) {
 #pragma unroll
         for (int m = 0; m < C::CPR; ++m) {
             const int i = lane + 64 * m, r = i / C::CPR, cj = i % C::CPR;
@@ -382,117 +473,51 @@ __global__ __launch_bounds__(SPNG_UNF_NW * 64) void unfilter_kernel(const UnfJob
         }
         if (lane < C::CPR) *(u32x4 *)(tile + 16 * lane) = Rtop;
     };
-    // band j tile T needs the last row of band j-1 on units [T*P, T*P+P): lane 63 of band j-1 is 63
-    // units behind, so they come from its tiles T .. T+K.  `done` of the producing wave counts the
-    // tiles (over all of its bands) whose stores have been drained.
-    auto ready = [&](uint32_t band, uint32_t T) -> bool {
-        if (!band) return true;
-        const uint32_t pw = (band - 1) % NW, pk = (band - 1) / NW;
-        const uint32_t need = pk * ntiles + (T + C::K < ntiles ? T + C::K : ntiles - 1) + 1;
-        return __hip_atomic_load(&done[pw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= need;
-    };
-    auto wait_ready = [&](uint32_t band, uint32_t T) {
-        SpinGuard guard;
-        while (!ready(band, T)) {
-            __builtin_amdgcn_s_sleep(8);
-            guard.tick();
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
 
-    uint32_t count = 0;                                  // tiles this wave has completed
-    bool staged = false;                                 // R holds the tile about to be processed
-    for (uint32_t band = wave; band < nbands; band += NW) {
+    constexpr bool PACKED = BPP == 3 || BPP == 6;          // (a unit in dwords: reconstruct_packed)
+    constexpr bool SUBUNIT = PX != BPP;                    // (pixels inside a dword unit: reconstruct_subunit)
+    constexpr int NS = SUBUNIT ? 1 : PACKED ? (BPP + 3) / 4 : BPP;
+    uint32_t ft = 0, o[NS], bprev[NS];
+    bool any_pae = false, all_none = false;
+    auto begin = [&](uint32_t band) {
         const uint32_t row = band * 64 + lane;
-        const uint32_t ft = row < rows ? job.in[(uint64_t)row * job.in_stride] : 0u;
-        constexpr bool PACKED = BPP == 3 || BPP == 6;          // (a unit in dwords: reconstruct_packed)
-        constexpr bool SUBUNIT = PX != BPP;                    // (pixels inside a dword unit: reconstruct_subunit)
-        constexpr int NS = SUBUNIT ? 1 : PACKED ? (BPP + 3) / 4 : BPP;
-        const bool any_pae = __any(ft == 4);                   // no Paeth row in this band: skip its arithmetic
+        ft = row < rows ? job.in[(uint64_t)row * job.in_stride] : 0u;
+        any_pae = __any(ft == 4);                              // no Paeth row in this band: skip its arithmetic
         // every row of the band filtered with None (what libpng writes for palette and low-depth images): the tiles only pass
         // through (the band below reads this one's last row back from the output, not from registers)
-        const bool all_none = !__any(row < rows && ft != 0);
-        uint32_t o[NS], bprev[NS];
+        all_none = !__any(row < rows && ft != 0);
 #pragma unroll
         for (int k = 0; k < NS; ++k) { o[k] = 0; bprev[k] = 0; }
-
-        for (uint32_t T = 0; T < ntiles; ++T) {
-            if (!staged) { wait_ready(band, T); issue(band, T); }
-            commit();
-            staged = false;
-            // prefetch the next tile of this wave while this one is reconstructed.  If its producer
-            // (another wave) is not far enough ahead yet, fall back behind it *now*: publish what is
-            // pending and wait, so that from here on the prefetch always overlaps the arithmetic.
-            uint32_t nb = band, nT = T + 1;
-            if (nT == ntiles) { nb = band + NW; nT = 0; }
-            if (nb < nbands) {
-                bool ok = ready(nb, nT);
-                // Blocking here is deadlock-free only if nothing the awaited tile depends on is a tile
-                // this wave has not published yet.  Same band: that band is complete.  Next band (we are
-                // in the last tile of the current one): every wave in between may itself be blocked here, in
-                // front of its staged tile with only the tiles before it published, so a hop reaches back
-                // K + 1 tiles and (nb, 0) needs tile NW * (K + 1) - 1 of this wave's current band: it must
-                // lie in front of the last one (tests/test_emu_unfilter.py "one long piece").  Shorter rows
-                // do not prefetch across the band; what that costs them has not been measured.
-                const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(NW * (C::K + 1)) + 1 < ntiles);
-                if (!ok && may_block) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0 && count)
-                        __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    wait_ready(nb, nT);
-                    ok = true;
-                }
-                if (ok) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    issue(nb, nT);
-                    staged = true;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // LDS tile written before it is read
-
-            const int64_t ux0 = (int64_t)T * C::P - lane;
+    };
+    auto compute = [&](uint32_t, uint32_t T) {
+        const int64_t ux0 = (int64_t)T * C::P - lane;
 #ifndef SPNG_UNF_NOCOMPUTE        // tuning builds only: measure the memory pipeline alone
-            if (all_none) {
-            } else if constexpr (SUBUNIT) {
-                if (any_pae) reconstruct_subunit<PX, C::P, true>(tile, C::ROWB, lane, ft, ux0, o[0], bprev[0]);
-                else         reconstruct_subunit<PX, C::P, false>(tile, C::ROWB, lane, ft, ux0, o[0], bprev[0]);
-            } else if constexpr (PACKED) {
-                (void)ux0;
-                if (any_pae) reconstruct_packed<BPP, C::P, true>(tile, C::ROWB, lane, ft, o, bprev);
-                else         reconstruct_packed<BPP, C::P, false>(tile, C::ROWB, lane, ft, o, bprev);
-            } else if (any_pae) reconstruct_generic<BPP, C::P, true>(tile, C::ROWB, lane, ft, ux0, o, bprev);
-            else                reconstruct_generic<BPP, C::P, false>(tile, C::ROWB, lane, ft, ux0, o, bprev);
+        if (all_none) {
+        } else if constexpr (SUBUNIT) {
+            if (any_pae) reconstruct_subunit<PX, C::P, true>(tile, C::ROWB, lane, ft, ux0, o[0], bprev[0]);
+            else         reconstruct_subunit<PX, C::P, false>(tile, C::ROWB, lane, ft, ux0, o[0], bprev[0]);
+        } else if constexpr (PACKED) {
+            (void)ux0;
+            if (any_pae) reconstruct_packed<BPP, C::P, true>(tile, C::ROWB, lane, ft, o, bprev);
+            else         reconstruct_packed<BPP, C::P, false>(tile, C::ROWB, lane, ft, o, bprev);
+        } else if (any_pae) reconstruct_generic<BPP, C::P, true>(tile, C::ROWB, lane, ft, ux0, o, bprev);
+        else                reconstruct_generic<BPP, C::P, false>(tile, C::ROWB, lane, ft, ux0, o, bprev);
 #endif
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-
-            // The stores of the previous tile (and the prefetch loads) have had the whole
-            // reconstruction to complete: drain, then publish the previous tile.  Publishing one
-            // tile late keeps the store latency off the critical path.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0 && count)
-                __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            // write back the 64 row windows
+    };
+    auto store = [&](uint32_t band, uint32_t T) {              // write back the 64 row windows
 #pragma unroll
-            for (int m = 0; m < C::CPR; ++m) {
-                const int i = lane + 64 * m, r = i / C::CPR, cj = i % C::CPR;
-                const uint32_t rw = band * 64 + r;
-                if (rw < rows)
-                    store_window(job.out + (uint64_t)rw * job.out_stride,
-                                 ((int64_t)T * C::P - r) * BPP + 16 * cj, pitch,
-                                 *(const u32x4 *)(tile + (1 + r) * C::ROWB + 16 * cj));
-            }
-            ++count;
-            // a tile that could not be prefetched depends on this one (or a later one): publish now
-            if (!staged) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0)
-                    __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+        for (int m = 0; m < C::CPR; ++m) {
+            const int i = lane + 64 * m, r = i / C::CPR, cj = i % C::CPR;
+            const uint32_t rw = band * 64 + r;
+            if (rw < rows)
+                store_window(job.out + (uint64_t)rw * job.out_stride,
+                             ((int64_t)T * C::P - r) * BPP + 16 * cj, pitch,
+                             *(const u32x4 *)(tile + (1 + r) * C::ROWB + 16 * cj));
         }
-    }
-    // last tile of this wave
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    // band j tile T needs the last row of band j-1 on units [T*P, T*P+P): lane 63 of band j-1 is 63 units behind, so they
+    // come from its tiles T .. T+K -- a reach of K.  A tile is loaded, reconstructed and stored in one step.
+    band_pipeline<NW>(BandProgress<NW>{done, ntiles, (uint32_t)C::K, wave, lane}, nbands, ntiles, begin, issue, commit, compute, store);
 }
 
 // =====================================================================================================================
@@ -557,7 +582,7 @@ __device__ __forceinline__ void phase_pk(uint8_t *rowp, const uint8_t *topp, uin
         for (int i = 0; i < 8; ++i) {
             constexpr int dmask = DW - 1;
             const int d = i & dmask;                           // which dword of its unit
-            uint32_t b = from_lane_above(o[d], 0u);
+            uint32_t b = lane_above(o[d], 0u);
             b = head ? tq[i] : b;                              // (first lane of a ramp: the row above the band)
             uint32_t p = (o[d] & m_sub) | (b & m_up) | (__builtin_amdgcn_lerp(o[d], b, 0u) & m_avg);
             const uint32_t b_lo = __builtin_amdgcn_perm(0u, b, SEL_LO), b_hi = __builtin_amdgcn_perm(0u, b, SEL_HI);
@@ -585,7 +610,7 @@ __global__ __launch_bounds__(SPNG_UNF_PK_NW * 64) void unfilter_pk_kernel(const 
     using C = Pk<BPP>;
     constexpr int NW = SPNG_UNF_PK_NW, RR = C::RR, NCH = C::NCH;
     __shared__ PkWave lds[NW];
-    __shared__ uint32_t done[NW];                        // phases completed (stores drained) by each wave
+    __shared__ uint32_t done[NW];                        // phases completed by each wave (BandProgress)
 
     UnfJob job = jobs[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = (int)UNI(threadIdx.x >> 6);
@@ -593,24 +618,8 @@ __global__ __launch_bounds__(SPNG_UNF_PK_NW * 64) void unfilter_pk_kernel(const 
     if (threadIdx.x < NW) done[threadIdx.x] = 0;
     __syncthreads();
 
-    uint32_t rows = job.rows;
-    if (job.rows_len) {
-        // a short stream silently yields an incomplete image (PNG.Decoder.swift:88-94)
-        const uint64_t len = *job.rows_len;
-        const uint64_t avail = len > job.stream_off ? (len - job.stream_off) / job.in_stride : 0;
-        rows = avail < rows ? (uint32_t)avail : rows;
-    }
-    // the pieces of this workgroup's chains (see unfilter_kernel: a piece starts on a row filtered with None or Sub)
-    auto cut = [&](uint64_t x) -> uint32_t {
-        if (x == 0) return 0;
-        for (uint64_t r0 = x; r0 < rows; r0 += 64) {
-            const uint64_t r = r0 + lane;
-            const uint32_t ft = r < rows ? job.in[r * job.in_stride] : 0u;
-            const unsigned long long m = __ballot(r < rows && ft <= 1);
-            if (m) return (uint32_t)(r0 + __ffsll((long long)m) - 1);
-        }
-        return rows;
-    };
+    const uint32_t rows = rows_available(job);
+    // the pieces of this workgroup's chains (piece_start)
     uint32_t first[NCH], nrows[NCH];
     bool htop[NCH];
     uint32_t maxb = 0;
@@ -619,8 +628,8 @@ __global__ __launch_bounds__(SPNG_UNF_PK_NW * 64) void unfilter_pk_kernel(const 
         const uint32_t q = blockIdx.y * NCH + h;
         uint32_t f = 0, l = 0;
         if (q < npieces) {
-            f = npieces > 1 ? UNI(cut((uint64_t)q * sb_rows)) : 0u;
-            l = q + 1 == npieces ? rows : UNI(cut((uint64_t)(q + 1) * sb_rows));
+            f = npieces > 1 ? UNI(piece_start(job, rows, lane, (uint64_t)q * sb_rows)) : 0u;
+            l = q + 1 == npieces ? rows : UNI(piece_start(job, rows, lane, (uint64_t)(q + 1) * sb_rows));
         }
         first[h] = f; nrows[h] = l > f ? l - f : 0u;
         htop[h] = f == 0 && job.has_prev != 0;          // (rows that arrived with a later push: the row above is in front of `out`)
@@ -667,113 +676,47 @@ __global__ __launch_bounds__(SPNG_UNF_PK_NW * 64) void unfilter_pk_kernel(const 
         for (int m = 0; m < 8; ++m) *(u32x4 *)(&w.rows[r0 + 8 * m][slot + 16 * cj]) = R[m];
         if (lane < NCH * 8) *(u32x4 *)(&w.top[r0][T & 1][16 * cj]) = Rtop;
     };
-    // Band j tile T needs the last row of band j - 1 on bytes [T * TB, T * TB + TB): that tile is stored at the end of the
-    // producer's phase T + 1.  `done` of the producing wave counts the phases (over all of its bands) whose stores have drained.
-    auto ready = [&](uint32_t band, uint32_t T) -> bool {
-        if (!band) return true;
-        const uint32_t pw = (band - 1) % NW, pk = (band - 1) / NW;
-        const uint32_t need = pk * nph + (T + 1 < nph ? T + 1 : nph - 1) + 1;
-        return __hip_atomic_load(&done[pw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= need;
-    };
-    auto wait_ready = [&](uint32_t band, uint32_t T) {
-        SpinGuard guard;
-        while (!ready(band, T)) {
-            __builtin_amdgcn_s_sleep(8);
-            guard.tick();
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
 
-    uint32_t count = 0;                                  // phases this wave has completed
-    bool staged = false;                                 // R holds the tile about to be committed
-    for (uint32_t band = wave; band < maxb; band += NW) {
+    uint32_t ft = 0, o[C::DW], bprev[C::DW];
+    bool any_pae = false;
+    auto begin = [&](uint32_t band) {
         const uint32_t row = band * RR + (uint32_t)rp;
-        const bool mine = row < my_rows;
-        const uint32_t ft = mine ? job.in[(uint64_t)(my_first + row) * job.in_stride] : 0u;
-        const bool any_pae = __any(ft == 4);            // no Paeth row in this band: skip its arithmetic
-        uint32_t o[C::DW], bprev[C::DW];
+        ft = row < my_rows ? job.in[(uint64_t)(my_first + row) * job.in_stride] : 0u;
+        any_pae = __any(ft == 4);                        // no Paeth row in this band: skip its arithmetic
 #pragma unroll
         for (int k = 0; k < C::DW; ++k) { o[k] = 0; bprev[k] = 0; }
-
-        for (uint32_t T = 0; T < nph; ++T) {
-            if (T < nta) {
-                if (!staged) { wait_ready(band, T); issue(band, T); }
-                commit(T);
-            }
-            staged = false;
-            // prefetch the next tile of this wave while this phase is worked on.  If its producer (another wave) is not far
-            // enough ahead yet, fall back behind it *now*: publish what is pending and wait, so that from here on the prefetch
-            // always overlaps the arithmetic.
-            uint32_t nb = band, nT = T + 1;
-            if (nT >= nta) { nb = band + NW; nT = 0; }
-            if (nb < maxb && (T + 1 < nta || T + 1 == nph)) {
-                bool ok = ready(nb, nT);
-                // Blocking here is deadlock-free only if nothing the awaited tile depends on is a phase this wave has not
-                // published yet: (nb, nT) reaches back to phase nT + 1 + 2 (NW - 1) of this wave's band nb - NW.  Same band:
-                // that band is complete.  Next band (we are in the last phase of the current one): only when the chain stops
-                // short of this phase.
-                const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(2 * NW) + 1 < nph);
-                if (!ok && may_block) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0 && count)
-                        __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    wait_ready(nb, nT);
-                    ok = true;
-                }
-                if (ok) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    issue(nb, nT);
-                    staged = true;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // LDS tile written before it is read
-
-            const int u0 = (int)(T * RR) - rp;           // my first unit of this phase
-            const uint32_t a0 = (uint32_t)(u0 * BPP) & 255u;
+    };
+    auto compute = [&](uint32_t, uint32_t T) {
+        const int u0 = (int)(T * RR) - rp;               // my first unit of this phase
+        const uint32_t a0 = (uint32_t)(u0 * BPP) & 255u;
 #ifndef SPNG_UNF_NOCOMPUTE        // tuning builds only: measure the memory pipeline alone
-            // (odd phases: the window [128 - bpp rp, 256 - bpp rp) of the ring never wraps)
-            if (T == 0)            phase_pk<BPP, true, true, true>(w.rows[lane], w.top[hh][0], a0, u0, head, ft, o, bprev);
-            else if (T & 1) {
-                if (any_pae)       phase_pk<BPP, false, true, false>(w.rows[lane], w.top[hh][1], a0, u0, head, ft, o, bprev);
-                else               phase_pk<BPP, false, false, false>(w.rows[lane], w.top[hh][1], a0, u0, head, ft, o, bprev);
-            } else {
-                if (any_pae)       phase_pk<BPP, false, true, true>(w.rows[lane], w.top[hh][0], a0, u0, head, ft, o, bprev);
-                else               phase_pk<BPP, false, false, true>(w.rows[lane], w.top[hh][0], a0, u0, head, ft, o, bprev);
-            }
-#endif
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-
-            // The stores of the previous phase (and the prefetch loads) have had the whole reconstruction to complete:
-            // drain, then publish the previous phase.  Publishing one phase late keeps the store latency off the critical path.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0 && count)
-                __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            // tile T - 1 is complete in every row: whole lines to the output
-            if (T) {
-                const uint32_t slot = ((T - 1) & 1) * 128;
-                const int64_t off = (int64_t)(T - 1) * C::TB + 16 * cj;
-#pragma unroll
-                for (int m = 0; m < 8; ++m) {
-                    constexpr int per = RR / 8;
-                    const int h = m / per;
-                    const uint32_t rw = band * RR + (uint32_t)((m % per) * 8 + r0);
-                    if (rw < nrows[h])
-                        store_window(job.out + (uint64_t)(first[h] + rw) * job.out_stride, off, pitch,
-                                     *(const u32x4 *)(&w.rows[r0 + 8 * m][slot + 16 * cj]));
-                }
-            }
-            ++count;
-            // a tile that could not be prefetched depends on this phase (or a later one): publish now
-            if (!staged) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0)
-                    __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+        // (odd phases: the window [128 - bpp rp, 256 - bpp rp) of the ring never wraps)
+        if (T == 0)            phase_pk<BPP, true, true, true>(w.rows[lane], w.top[hh][0], a0, u0, head, ft, o, bprev);
+        else if (T & 1) {
+            if (any_pae)       phase_pk<BPP, false, true, false>(w.rows[lane], w.top[hh][1], a0, u0, head, ft, o, bprev);
+            else               phase_pk<BPP, false, false, false>(w.rows[lane], w.top[hh][1], a0, u0, head, ft, o, bprev);
+        } else {
+            if (any_pae)       phase_pk<BPP, false, true, true>(w.rows[lane], w.top[hh][0], a0, u0, head, ft, o, bprev);
+            else               phase_pk<BPP, false, false, true>(w.rows[lane], w.top[hh][0], a0, u0, head, ft, o, bprev);
         }
-    }
-    // last phase of this wave
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_store(&done[wave], count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+#endif
+    };
+    auto store = [&](uint32_t band, uint32_t T) {        // tile T is complete in every row: whole lines to the output
+        const uint32_t slot = (T & 1) * 128;
+        const int64_t off = (int64_t)T * C::TB + 16 * cj;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            constexpr int per = RR / 8;
+            const int h = m / per;
+            const uint32_t rw = band * RR + (uint32_t)((m % per) * 8 + r0);
+            if (rw < nrows[h])
+                store_window(job.out + (uint64_t)(first[h] + rw) * job.out_stride, off, pitch,
+                             *(const u32x4 *)(&w.rows[r0 + 8 * m][slot + 16 * cj]));
+        }
+    };
+    // Band j tile T needs the last row of band j - 1 on bytes [T * TB, T * TB + TB): that tile is complete, and stored, at the end
+    // of the producer's phase T + 1 -- a reach of one.  A band is its nta tiles and one phase more, which finishes the last tile.
+    band_pipeline<NW>(BandProgress<NW>{done, nph, 1u, wave, lane}, maxb, nta, begin, issue, commit, compute, store);
 }
 
 hipError_t launch_unfilter(const UnfJob *d_jobs, uint32_t count, uint32_t bpp, spng_result *d_results,

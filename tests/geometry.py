@@ -27,6 +27,8 @@ def _load():
     lib = ctypes.CDLL(so)
     for name, res, args in (("geo_unfilter_pieces", None, (_u32, _u64, _u32, _u64, _u32, ctypes.POINTER(_u32))),
                             ("geo_unfilter_wide_tiles", ctypes.c_int32, (_u32, _u64)),
+                            ("geo_band_steps_needed", _u32, (_u32, _u32, _u32, _u32, _u32)),
+                            ("geo_band_may_wait", ctypes.c_int32, (_u32, _u32, _u32)),
                             ("geo_filter_blocks_x", _u32, (_u32,)),
                             ("geo_plane_blocks_x", _u32, (_u64, _u32)),
                             ("geo_blocks_for", _u32, (_u64, _u32)),
@@ -65,6 +67,10 @@ def unfilter_wide_tiles(k, widest) -> bool:
     return bool(_lib.geo_unfilter_wide_tiles(k, widest))
 
 
+def band_may_wait(nw, reach, per_band) -> bool:
+    return bool(_lib.geo_band_may_wait(nw, reach, per_band))
+
+
 def search_chunks(streams):
     """-> (chunks per stream, positions per chunk)"""
     out = (_u32 * 2)()
@@ -72,6 +78,7 @@ def search_chunks(streams):
     return out[0], out[1]
 
 
+band_steps_needed = _lib.geo_band_steps_needed
 filter_blocks_x = _lib.geo_filter_blocks_x
 plane_blocks_x = _lib.geo_plane_blocks_x
 blocks_for = _lib.geo_blocks_for

@@ -32,7 +32,7 @@ FILTER_GRID_ROWS = geo.constant("FILTER_ROWS_PER_BLOCK") * geo.constant("FILTER_
 # ---- the kernels' internals, as plain numbers (where they live: see SOURCE_LINES) ------------------------------------------------
 PK_NW, PK_TILE_BYTES = 4, 128        # unfilter_pk_kernel: waves per workgroup, bytes of a row per phase
 U_NW = 4                             # unfilter_kernel: waves per workgroup
-BAND = 64                            # rows per band of unfilter_kernel; the ballot of `cut` looks at 64 rows per round
+BAND = 64                            # rows per band of unfilter_kernel; the ballot of `piece_start` looks at 64 rows per round
 PACKED_ROW = 2048                    # filter_kernel: longest sub-byte scanline that goes through LDS
 FAST_STEP = 1024                     # filter_row_fast: bytes of a row per step of the wave (64 lanes x 16)
 
@@ -40,13 +40,15 @@ FAST_STEP = 1024                     # filter_row_fast: bytes of a row per step 
 SOURCE_LINES = [
     ("unfilter.hip", "#define SPNG_UNF_PK_NW 4"),
     ("unfilter.hip", "static constexpr int TB = 128, RING = 256;"),
-    ("unfilter.hip", "const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(2 * NW) + 1 < nph);"),
-    ("unfilter.hip", "const bool may_block = NW > 1 && nb && (nb == band || (uint32_t)(NW * (C::K + 1)) + 1 < ntiles);"),
+    ("unfilter.hip", "return NW > 1 && next && (next == band || band_may_wait(NW, reach, per_band));"),    # the one pipeline of both kernels
+    ("unfilter.hip", "band_pipeline<NW>(BandProgress<NW>{done, nph, 1u, wave, lane}, maxb, nta, begin, issue, commit, compute, store);"),
+    ("unfilter.hip", "band_pipeline<NW>(BandProgress<NW>{done, ntiles, (uint32_t)C::K, wave, lane}, nbands, ntiles, begin, issue, commit, compute, store);"),
     ("unfilter.hip", "#define SPNG_UNF_NW 4"),
     ("unfilter.hip", "#define SPNG_UNF_P4 64"),
     ("unfilter.hip", "#define SPNG_UNF_PSUB 16"),
     ("unfilter.hip", "#define SPNG_UNF_P8 32"),
     ("unfilter.hip", "const uint32_t ntiles = (W + 63 + C::P - 1) / C::P;"),
+    ("unfilter.hip", "__device__ __forceinline__ uint32_t piece_start(const UnfJob &job, uint32_t rows, int lane, uint64_t x)"),
     ("unfilter.hip", "for (uint64_t r0 = x; r0 < rows; r0 += 64) {"),
     ("unfilter.hip", "const unsigned long long m = __ballot(r < rows && ft <= 1);"),
     ("encode.hip", "static constexpr uint32_t PACKED_ROW = 2048;"),
@@ -131,9 +133,10 @@ def unfilter_plan(k: int, jobs, configured: int = 0):
 
 
 def pk_may_block(pitch: int) -> bool:
-    """unfilter_pk_kernel: `(uint32_t)(2 * NW) + 1 < nph` -- a wave that finishes a band may wait for the next band's first tile"""
+    """unfilter_pk_kernel, nph phases per band and a reach of one: a wave that finishes a band may wait for the next band's first
+    tile (`band_may_wait` of csrc/geometry.hpp, as the kernels' pipeline calls it)"""
     nph = (pitch + PK_TILE_BYTES - 1) // PK_TILE_BYTES + 1
-    return 2 * PK_NW + 1 < nph
+    return geo.band_may_wait(PK_NW, 1, nph)
 
 
 def u_tiles(k: int, pitch: int, wide: bool):
@@ -145,11 +148,12 @@ def u_tiles(k: int, pitch: int, wide: bool):
 
 
 def u_may_block(k: int, pitch: int, wide: bool) -> str:
-    """unfilter_kernel: `NW * (K + 1) + 1 < ntiles` -- a wave in its band's last tile may wait for the first tile of its next band.
+    """unfilter_kernel, ntiles steps per band and a reach of K: a wave in its band's last tile may wait for the first tile of its next
+    band (`band_may_wait` of csrc/geometry.hpp, as the kernels' pipeline calls it).
     -> "blocks", "gap" (the bound this one replaced, `NW * K + 1 < ntiles`, let it wait: rows on which the waves of a piece of more
     than NW bands waited for each other for good) or "never" """
     kk, nt = u_tiles(k, pitch, wide)
-    if U_NW * (kk + 1) + 1 < nt:
+    if geo.band_may_wait(U_NW, kk, nt):
         return "blocks"
     return "gap" if U_NW * kk + 1 < nt else "never"
 
@@ -176,7 +180,7 @@ def filter_types(regime: str, rows: int, rng) -> np.ndarray:
         return t
     t = rng.integers(2, 5, rows).astype(np.uint8)       # nocut: nothing after row 0 lets a piece start
     t[0] = 0
-    if regime == "rare":                                # None / Sub rows more than 64 rows apart: `cut` takes several ballots
+    if regime == "rare":                                # None / Sub rows more than 64 rows apart: `piece_start` takes several ballots
         r = int(rng.integers(70, 200))
         while r < rows:
             t[r] = rng.integers(0, 2)
@@ -302,6 +306,31 @@ ADAM7_CASES = [
     _g("adam7 rgb8 1500x1200", 1500, 1200, 8, 3, "u<3>", "wide", True),
     _g("adam7 rgba16 900x1100", 900, 1100, 16, 4, "pk<8>", "rr", True),
 ]
+
+
+# the edge of `band_may_wait` for every kernel family, as tests/test_emu_unfilter.py has it ("N tiles", "N phases"): one type under a
+# Sub row, so the image is one long piece of more bands than the workgroup has waves -- the last step count per band at which a wave
+# never waits for its next band, and the first at which it may.  (name, steps per band, case)
+def _e(name, steps, w, depth, ch, regime, kernel, branch):
+    return steps, Case(f"edge {name} {w}x330 {regime}", w, 330, depth, ch, False, "noise", regime, kernel, branch)
+
+
+BOUND_EDGE_CASES = [
+    _e("rgb16", 13, 330, 16, 3, "paeth", "u<6>", "floor128"), _e("rgb16", 14, 360, 16, 3, "paeth", "u<6>", "wide"),
+    _e("rgb8", 9, 460, 8, 3, "average", "u<3>", "floor128"), _e("rgb8", 10, 520, 8, 3, "up", "u<3>", "floor128"),
+    _e("gray8", 21, 1040, 8, 1, "paeth", "u<4,1>", "floor128"), _e("va8", 22, 550, 8, 2, "paeth", "u<4,2>", "floor128"),
+    _e("rgba8", 9, 256, 8, 4, "paeth", "pk<4>", "rr"), _e("rgba8", 10, 257, 8, 4, "paeth", "pk<4>", "rr"),
+    _e("rgba16", 9, 128, 16, 4, "paeth", "pk<8>", "rr"), _e("rgba16", 10, 129, 16, 4, "paeth", "pk<8>", "rr"),
+]
+
+
+def band_steps(c: Case):
+    """(waves, reach, steps per band) of the kernel that defilters the non-interlaced case: what `band_pipeline` is called with"""
+    pitch = passes(c)[0][0]
+    if c.bpp in (4, 8):
+        return PK_NW, 1, (pitch + PK_TILE_BYTES - 1) // PK_TILE_BYTES + 1
+    kk, nt = u_tiles(c.bpp, pitch, pitch >= WIDE_ROW)
+    return U_NW, kk, nt
 
 
 def unfilter_cases():
@@ -454,7 +483,7 @@ TOTAL_BYTES_CAP = 3 << 30
 
 
 def all_cases():
-    out = unfilter_cases() + RESUME_CASES + filter_cases() + filter_batch_cases() + scaled_batch_cases()
+    out = unfilter_cases() + [c for _, c in BOUND_EDGE_CASES] + RESUME_CASES + filter_cases() + filter_batch_cases() + scaled_batch_cases()
     out += wide_batch_cases(False) + wide_batch_cases(True)
     for k in BATCH_FORMATS:
         out += batch_cases(k)

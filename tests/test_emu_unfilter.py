@@ -5,6 +5,7 @@ compiler: the ROCm clang++ (the kernel is written with clang's vector extensions
 compiler-only barriers turned into meetings of the wave: tools/emu/prep_deflate.py).  Timing and memory ordering are not modelled;
 the `-m gpu` tests remain the parity tests proper."""
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -45,15 +46,19 @@ CASES = [
     ("gray8 one pixel", 1, 1, 1, 8, 64, [4]), ("gray8 five pixels", 5, 130, 1, 8, 64, _f(13, 130)), ("va8 paeth", 33, 20, 2, 8, 64, [2, 4]),
     ("gray16 mixed", 301, 70, 1, 16, 64, _f(14, 70)), ("gray8 wide", 3001, 140, 1, 8, 64, _f(15, 140)), ("va8 wide, pieces", 1100, 200, 2, 8, 32, _f(16, 61)),
     # one long piece (no None / Sub row behind the first: more bands than the workgroup has waves) of rows whose tile count is
-    # just above what `may_block` of unfilter_kernel asked for: a wave that waited for the first tile of its NEXT band in front of
-    # its last tile, while the three waves between waited in front of their staged tiles, waited for good (found by the
-    # production-size table of tests/scanline_cases.py: "rgb16 300x1300 up")
+    # just above what the first form of `band_may_wait` (csrc/geometry.hpp; then `may_block` of unfilter_kernel) asked for: a wave
+    # that waited for the first tile of its NEXT band in front of its last tile, while the three waves between waited in front of
+    # their staged tiles, waited for good (found by the production-size table of tests/scanline_cases.py: "rgb16 300x1300 up")
     ("rgb16 one long piece", 300, 330, 3, 16, 1000, [1] + [2] * 400), ("rgb8 one long piece", 300, 330, 3, 8, 1000, [1] + [4] * 400),
     ("gray8 one long piece", 900, 330, 1, 8, 1000, [1] + [3] * 400), ("va8 one long piece", 450, 330, 2, 8, 1000, [1] + [2] * 400),
     # and the edge of the bound that replaced it, `NW * (K + 1) + 1 < ntiles`: the last tile count that does not wait and the first that does
     ("rgb16 13 tiles", 330, 330, 3, 16, 1000, [1] + [4] * 400), ("rgb16 14 tiles", 360, 330, 3, 16, 1000, [1] + [4] * 400),
     ("rgb8 9 tiles", 460, 330, 3, 8, 1000, [1] + [3] * 400), ("rgb8 10 tiles", 520, 330, 3, 8, 1000, [1] + [2] * 400),
     ("gray8 21 tiles", 1040, 330, 1, 8, 1000, [1] + [4] * 400), ("va8 22 tiles", 550, 330, 2, 8, 1000, [1] + [4] * 400),
+    # the same edge for the line-aligned kernel, whose reach is one phase (`band_may_wait` of csrc/geometry.hpp, 2 NW + 1 < phases):
+    # 8 tiles of 128 bytes + 1 = 9 phases never wait across the band, 9 tiles + 1 = 10 phases are the first that do
+    ("rgba8 9 phases", 256, 330, 4, 8, 1000, [1] + [4] * 400), ("rgba8 10 phases", 257, 330, 4, 8, 1000, [1] + [4] * 400),
+    ("rgba16 9 phases", 128, 330, 4, 16, 1000, [1] + [4] * 400), ("rgba16 10 phases", 129, 330, 4, 16, 1000, [1] + [4] * 400),
 ]
 
 
@@ -62,7 +67,7 @@ def test_emulated_unfilter_matches_the_oracle(emu, tmp_path, case):
     name, w, h, channels, depth, piece_rows, filters = case
     bpp = channels * depth // 8
     pitch = w * bpp
-    rng = np.random.default_rng(abs(hash(name)) % (1 << 31))
+    rng = np.random.default_rng(zlib.crc32(name.encode()))       # (the same in every process, unlike hash())
     img = rng.integers(0, 256, (h, pitch), dtype=np.uint8)
     rows = bytearray(ph.orc_filter(img.reshape(-1), w, h, depth, channels, False))
     if filters is not None:                                 # (any filter byte over any payload is a valid input of the UNfilter)

@@ -138,6 +138,18 @@ def test_unfilter_at_size(gpu, c):
     _same(c, got, want)
 
 
+def test_unfilter_at_the_edge_of_the_wait_across_bands(gpu):
+    """the ten shapes on the two sides of `band_may_wait` (csrc/geometry.hpp), one call each: one long piece of more bands than
+    waves, the last step count at which a wave never waits for the first tile of its next band and the first at which it may"""
+    s = gpu.load()
+    assert len(sc.BOUND_EDGE_CASES) == 10
+    for _, c in sc.BOUND_EDGE_CASES:
+        rows = sc.unfilter_input(c)
+        want = _oracle_unfilter(c, rows)
+        got, = _unfilter(s, gpu, [c], [rows])
+        _same(c, got, want)
+
+
 @pytest.mark.parametrize("c", sc.SHORT_CASES, ids=[c.name for c in sc.SHORT_CASES])
 def test_unfilter_short_input_at_size(gpu, c):
     """`rows_len` cuts the stream inside a row, exactly at a row's end, inside the last piece: the rows that are whole are the

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import geometry as geo
 import pnghelp as ph
 import scanline_cases as sc
 
@@ -23,8 +24,8 @@ def test_the_mirrored_lines_are_still_in_the_sources():
         if name not in text:
             text[name] = open(os.path.join(CSRC, name)).read()
         assert line in text[name], (name, line)
-    # both `cut` lambdas (unfilter_kernel, unfilter_pk_kernel) start a piece on None / Sub rows only
-    assert text["unfilter.hip"].count("const unsigned long long m = __ballot(r < rows && ft <= 1);") == 2
+    # `piece_start`, which both kernels call, starts a piece on None / Sub rows only -- and is the only place that looks for one
+    assert text["unfilter.hip"].count("const unsigned long long m = __ballot(r < rows && ft <= 1);") == 1
 
 
 def test_sizes_agree_with_the_oracle_and_stay_under_the_cap():
@@ -75,7 +76,7 @@ def test_unfilter_case(c):
         assert (c.branch == "few") == (c.bpp == 4 and c.height >= sc.PK_FEW_HEIGHT), c.name
     _check_regime(c, rows)
     if c.regime == "rare" and not c.interlaced:
-        # a piece boundary whose next None / Sub row is 64 rows or more away: the ballot of `cut` goes round again -- and at least
+        # a piece boundary whose next None / Sub row is 64 rows or more away: the ballot of `piece_start` goes round again -- and at least
         # two pieces survive (a cut row exists behind the first boundary)
         t = sc.types_of(c, rows)[0]
         cuts = np.nonzero(t <= 1)[0]
@@ -126,6 +127,27 @@ def test_unfilter_table_reaches_every_path():
             assert c.height > 1024 and sc.WIDE_FLOOR <= piece <= sc.WIDE_CEIL and pieces >= 2
     # Adam7 at size: sub-byte, 3-byte, 8-byte
     assert {c.bpp if c.volume >= 8 else 0 for c in UNFILTER if c.interlaced} == {0, 3, 8}
+
+
+def test_bound_edge_cases():
+    """every pair lies on the two sides of `band_may_wait`, the first of it exactly at the edge, in one piece of more bands than waves"""
+    assert len(sc.BOUND_EDGE_CASES) == 10 and {c.kernel for _, c in sc.BOUND_EDGE_CASES} == {"u<6>", "u<3>", "u<4,1>", "u<4,2>", "pk<4>", "pk<8>"}
+    for steps, c in sc.BOUND_EDGE_CASES:
+        nw, reach, per_band = sc.band_steps(c)
+        assert per_band == steps, (c.name, per_band)
+        edge = nw * (reach + 1) + 1                              # (spelled out here once: the figure the names carry)
+        assert steps in (edge, edge + 1) and geo.band_may_wait(nw, reach, steps) == (steps == edge + 1), c.name
+        assert not geo.band_may_wait(nw, reach, edge) and geo.band_may_wait(nw, reach, edge + 1)
+        kernel, branch, piece, pieces = sc.case_plan(c)
+        assert (kernel, branch) == (c.kernel, c.branch) and pieces >= 2, c.name
+        rows = sc.unfilter_input(c)
+        t, = sc.types_of(c, rows)
+        assert t[0] == 1 and (t[1:] >= 2).all()                  # no row lets a second piece start: all of it is piece 0
+        assert c.height > nw * (sc.BAND if c.bpp not in (4, 8) else sc.PK_TILE_BYTES // c.bpp)
+        assert sc.oracle_unfilter(c, rows)[0] == 0
+    # the needed count is the one the kernels wait for: band 5 of four waves, its producer's second band
+    assert geo.band_steps_needed(5, 0, 4, 14, 2) == 14 + 2 + 1 and geo.band_steps_needed(5, 12, 4, 14, 2) == 14 + 13 + 1
+    assert geo.band_steps_needed(1, 3, 4, 10, 1) == 3 + 1 + 1 and geo.band_steps_needed(4, 9, 4, 10, 1) == 9 + 1
 
 
 def test_short_input_lengths():

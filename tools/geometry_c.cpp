@@ -13,6 +13,8 @@ void geo_unfilter_pieces(uint32_t k, uint64_t total_rows, uint32_t max_rows, uin
     out[0] = p.piece_rows; out[1] = p.pieces; out[2] = (uint32_t)p.rule;
 }
 int32_t geo_unfilter_wide_tiles(uint32_t k, uint64_t widest) { return unfilter_wide_tiles(k, widest); }
+uint32_t geo_band_steps_needed(uint32_t band, uint32_t step, uint32_t nw, uint32_t per_band, uint32_t reach) { return band_steps_needed(band, step, nw, per_band, reach); }
+int32_t geo_band_may_wait(uint32_t nw, uint32_t reach, uint32_t per_band) { return band_may_wait(nw, reach, per_band); }
 uint32_t geo_filter_blocks_x(uint32_t max_rows) { return filter_blocks_x(max_rows); }
 uint32_t geo_plane_blocks_x(uint64_t max_pixels, uint32_t cap) { return plane_blocks_x(max_pixels, cap); }
 uint32_t geo_blocks_for(uint64_t most, uint32_t per_block) { return blocks_for(most, per_block); }

@@ -296,10 +296,14 @@ int32_t spng_unfilter_resume_batch(spng_ctx *ctx, const spng_image_desc *descs, 
 
 /* ---- pixels: the step behind the decode path ----------------------------------------------------- */
 /* One image to unpack.  palette: indexed formats only, palette_count x 4 bytes (r, g, b, a): PLTE with the
- * tRNS alphas folded in, as PNG.Format keeps it.  key: the tRNS chroma key of a v / rgb / bgr format. */
+ * tRNS alphas folded in, as PNG.Format keeps it.  key: the chroma key of a v / rgb / bgr format as PNG.Format keeps it, compared with
+ * the samples in the order they lie in storage (PNG.RGBA.swift:318-323): (v), (r, g, b), and (b, g, r) for bgr8 -- a CgBI file's tRNS
+ * key, which is (r, g, b), REVERSED, as the reference does when it builds the format (PNG.Format.swift:427-430). */
 typedef struct spng_unpack_desc {
     const void *d_storage;                      /* PNG.Image.storage, S bytes                        */
-    void       *d_out;                          /* width * height RGBA quadruplets of `target` bits  */
+    void       *d_out;                          /* width * height RGBA quadruplets of `target` bits, at a multiple of T
+                                                   (target / 8 bytes: any address for UInt8, an even one for UInt16 -- as
+                                                   spng_pack_desc.d_pixels; SPNG_E_ARGUMENT otherwise).  d_storage: any address */
     const void *d_palette;
     uint32_t    width, height;
     uint32_t    palette_count;

@@ -81,7 +81,8 @@ int32_t spng_unpack_batch(spng_ctx *c, const spng_unpack_desc *descs, uint32_t c
         const spng_unpack_desc &d = descs[i];
         if (!valid_format(d.depth, d.channels) || !d.d_storage || !d.d_out || d.target != target ||
             (d.indexed && (d.channels != 1 || d.depth > 8 || (!d.d_palette && d.palette_count))) ||
-            d.layout > SPNG_TARGET_SCALAR || !valid_premultiply(d.premultiply, target, d.layout, SPNG_STRAIGHTEN_AS_U8))
+            d.layout > SPNG_TARGET_SCALAR || ((uintptr_t)d.d_out & (target / 8 - 1)) ||
+            !valid_premultiply(d.premultiply, target, d.layout, SPNG_STRAIGHTEN_AS_U8))
             return SPNG_E_ARGUMENT;
         UnpackJob j;
         memset(&j, 0, sizeof j);

@@ -79,6 +79,16 @@ def parse_png(data: bytes) -> Png:
     return Png(w, h, depth, color, inter, ios, b"".join(idat), chunks, palette, trns)
 
 
+def format_key(png: Png):
+    """the chroma key of the file's PNG.Format, in the order of the storage tuple -- what spng_unpack_desc.key and the oracle's
+    `unpack` take: tRNS as it stands for v and rgb formats, (b, g, r) for the bgr8 of a CgBI file (PNG.Format.swift:427-430);
+    None where the file has none"""
+    if not png.trns or png.color not in (0, 2):
+        return None
+    key = struct.unpack(">" + "H" * (1 if png.color == 0 else 3), png.trns[:2 if png.color == 0 else 6])
+    return key[::-1] if png.ios and png.color == 2 else key
+
+
 def unpack_rgba16(storage: np.ndarray, png: Png) -> np.ndarray:
     """PNG.Image.storage -> (H*W, 4) uint16 RGBA, as PNG.RGBA<UInt16>.unpack does."""
     n = png.width * png.height
@@ -124,6 +134,9 @@ def unpack_rgba16(storage: np.ndarray, png: Png) -> np.ndarray:
             raw = storage.reshape(n, ch).astype(np.uint32)
             s = raw * 257
         if png.ios:                                   # bgr8 / bgra8 (PNG.RGBA.swift:313,348)
+            # the key of a FILE: tRNS holds (r, g, b) (PNG.Transparency.swift:154-162); the reference turns it into the format's key
+            # (b, g, r) (PNG.Format.swift:427-430) and compares that with the storage tuple (PNG.RGBA.swift:318-323) -- the pixel
+            # whose (r, g, b) equals the tRNS key is the keyed one
             s = s.copy(); raw = raw.copy()
             s[:, [0, 2]] = s[:, [2, 0]]
             raw[:, [0, 2]] = raw[:, [2, 0]]

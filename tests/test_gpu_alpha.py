@@ -1,16 +1,20 @@
 """GPU checks of spng_alpha_batch / spng_alpha (premultiplied <-> straight alpha on arrays of RGBA<T> / VA<T> pixels) and of the
 fused forms: spng_unpack_desc.premultiply = SPNG_STRAIGHTEN*, spng_pack_desc.premultiply.
 
-Expected values come from `restate` below: PNG.premultiply / PNG.straighten (Sources/PNG/PNG.swift:55-117) and the
+Expected values come from `alpha` of oracle/pixels.py (`restate` here): PNG.premultiply / PNG.straighten (Sources/PNG/PNG.swift:55-117) and the
 (as: UInt8.self) forms (PNG.RGBA.swift:146-158, 192-206) written out in integers.  Where the reference traps (a > 0 and the quotient
 exceeds T.max) the documented answer of the device is T.max and a count in aux[0]."""
 import ctypes
 import json
+import sys
 
 import numpy as np
 import pytest
 
 import pnghelp as ph
+
+sys.path.insert(0, str(ph.ROOT / "oracle"))
+from pixels import alpha as restate  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -18,21 +22,6 @@ P, P8, S, S8 = 1, 2, 3, 4                  # SPNG_PREMULTIPLY, _AS_U8, SPNG_STRA
 RGBA, VA, SCALAR = 0, 1, 2
 TABLE = json.loads((ph.GOLDEN / "pngsuite.json").read_text())
 IOS = sorted(n for n in TABLE if n.startswith("ios/"))
-
-
-def restate(px, bits, op):
-    """px: (n, k) integers, alpha last -> ((n, k) int64 result, components the reference traps on)"""
-    px = np.asarray(px).astype(np.int64)
-    c, a, M, scale = px[:, :-1], px[:, -1:], (1 << bits) - 1, 1
-    if op in (P8, S8):
-        c, a, M, scale = c >> 8, a >> 8, 255, 257
-    if op in (P, P8):
-        out, trapped = (c * a + (M >> 1)) // M, 0                                   # PNG.swift:55-66
-    else:
-        q = (M * c + (a >> 1)) // np.maximum(a, 1)                                  # PNG.swift:101-117
-        trap = (a > 0) & (q > M)
-        out, trapped = np.where(a == 0, c, np.where(trap, M, q)), int(trap.sum())
-    return np.concatenate([out, a], axis=1) * scale, trapped
 
 
 def dtype_of(bits):

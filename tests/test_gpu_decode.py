@@ -433,9 +433,7 @@ def test_unpack_rgba_vs_reference_goldens(gpu, name):
     png = ph.parse_png((ph.GOLDEN / "pngsuite" / name).read_bytes())
     st, storage, _ = s.decode(png.idat, png.width, png.height, png.depth, png.channels, png.interlaced, png.fmt)
     assert st == 0
-    key = None
-    if png.trns and png.color in (0, 2):
-        key = struct.unpack(">" + "H" * (1 if png.color == 0 else 3), png.trns[:2 if png.color == 0 else 6])
+    key = ph.format_key(png)                                        # (a CgBI file's tRNS reversed: the bgr8 format's key is (b, g, r))
     kw = dict(indexed=png.color == 3, bgr=png.ios and png.color in (2, 6), palette=_palette_quads(png) if png.color == 3 else None,
               key=key)
     got16 = s.unpack(storage, png.width, png.height, png.depth, png.channels, target=16, **kw)
@@ -458,9 +456,7 @@ def test_unpack_premultiplied_vs_the_ios_goldens(gpu, name):
     png = ph.parse_png((ph.GOLDEN / "pngsuite" / "common" / name).read_bytes())
     st, storage, _ = s.decode(png.idat, png.width, png.height, png.depth, png.channels, png.interlaced, png.fmt)
     assert st == 0
-    key = None
-    if png.trns and png.color in (0, 2):
-        key = struct.unpack(">" + "H" * (1 if png.color == 0 else 3), png.trns[:2 if png.color == 0 else 6])
+    key = ph.format_key(png)                                        # (a CgBI file's tRNS reversed: the bgr8 format's key is (b, g, r))
     kw = dict(indexed=png.color == 3, palette=_palette_quads(png) if png.color == 3 else None, key=key)
     got = s.unpack(storage, png.width, png.height, png.depth, png.channels, target=16, premultiply=spng.PREMULTIPLY_AS_U8, **kw)
     assert hashlib.sha256(got).hexdigest() == TABLE["ios/" + name]["rgba16_sha256"], name
@@ -475,9 +471,7 @@ def test_unpack_va_and_premultiplied_targets(gpu, name):
     png = ph.parse_png((ph.GOLDEN / "pngsuite" / name).read_bytes())
     st, storage, _ = s.decode(png.idat, png.width, png.height, png.depth, png.channels, png.interlaced, png.fmt)
     assert st == 0
-    key = None
-    if png.trns and png.color in (0, 2):
-        key = struct.unpack(">" + "H" * (1 if png.color == 0 else 3), png.trns[:2 if png.color == 0 else 6])
+    key = ph.format_key(png)                                        # (a CgBI file's tRNS reversed: the bgr8 format's key is (b, g, r))
     kw = dict(indexed=png.color == 3, bgr=png.ios and png.color in (2, 6), palette=_palette_quads(png) if png.color == 3 else None,
               key=key)
     args = (storage, png.width, png.height, png.depth, png.channels)

@@ -112,6 +112,8 @@ def test_file_to_pixels_on_device(gpu):
         key = None
         if r.trns_len and r.color in (0, 2):
             key = struct.unpack(">" + "H" * (r.trns_len // 2), f[r.trns_off:r.trns_off + r.trns_len])
+            if r.ios and r.color == 2:
+                key = key[::-1]                                     # the bgr8 format's key is (b, g, r) (PNG.Format.swift:427-430)
         px = s.unpack(storage, r.width, r.height, r.depth, channels, indexed=r.color == 3, bgr=bool(r.ios) and r.color in (2, 6),
                       target=16, palette=pal, key=key)
         assert hashlib.sha256(px).hexdigest() == TABLE[name]["rgba16_sha256"], name

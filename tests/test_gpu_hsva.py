@@ -322,9 +322,7 @@ def test_mirror_unpack_and_pack(gpu, name, lossless):
     png = ph.parse_png((ph.GOLDEN / "pngsuite" / name).read_bytes())
     st, storage, _ = s.decode(png.idat, png.width, png.height, png.depth, png.channels, png.interlaced, png.fmt)
     assert st == 0
-    key = None
-    if png.trns and png.color in (0, 2):
-        key = struct.unpack(">" + "H" * (1 if png.color == 0 else 3), png.trns[:2 if png.color == 0 else 6])
+    key = ph.format_key(png)                                        # (a CgBI file's tRNS reversed: the bgr8 format's key is (b, g, r))
     indexed, bgr = png.color == 3, png.ios and png.color in (2, 6)
     fmt = (png.width, png.height, png.depth, png.channels)
     kw = dict(indexed=indexed, bgr=bgr, palette=_palette_quads(png) if indexed else None)

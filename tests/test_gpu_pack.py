@@ -11,6 +11,7 @@ import pnghelp as ph
 
 sys.path.insert(0, str(ph.ROOT / "oracle"))
 import pixels as orc_pixels  # noqa: E402
+import unpack_cases  # noqa: E402
 from test_oracle_pack import golden_case, repeats_a_colour  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -55,11 +56,13 @@ FORMATS = [(1, 1), (2, 1), (4, 1), (8, 1), (16, 1), (8, 2), (16, 2), (8, 3), (16
 @pytest.mark.parametrize("depth,channels", FORMATS)
 @pytest.mark.parametrize("bits", [8, 16])
 def test_pack_random_pixels_every_format(gpu, depth, channels, bits):
-    """random pixels of every colour target into every format (bgr too), sizes that leave 0-3 pixels behind the last quad"""
+    """random pixels of every colour target into every format (bgr too), sizes that leave 0-3 pixels behind the last quad, and those
+    of the case table (tests/unpack_cases.py): 255 / 256 / 257 quads, and full and partly filled last waves for the pixels of 3 and 6
+    bytes that leave through LDS"""
     s = gpu.load()
     rng = np.random.default_rng(depth * 100 + channels * 10 + bits)
     dt = np.uint8 if bits == 8 else np.uint16
-    for (w, h) in ((1, 1), (3, 1), (5, 3), (64, 9), (257, 31), (1023, 17)):
+    for (w, h) in [(1, 1), (3, 1), (5, 3), (64, 9), (257, 31), (1023, 17)] + [z for z in unpack_cases.PACK_SIZES if z not in unpack_cases.TAILS + unpack_cases.TURNS]:
         n = w * h
         for layout, k in ((orc_pixels.RGBA, 4), (orc_pixels.VA, 2), (orc_pixels.SCALAR, 1)):
             px = rng.integers(0, 1 << bits, (n, k), dtype=np.uint32).astype(dt)
@@ -113,9 +116,7 @@ def test_unpack_scalar_target(gpu, name):
     import struct
     s = gpu.load()
     png, storage, rgba, kw = golden_case(name)
-    key = None
-    if png.trns and png.color in (0, 2):
-        key = struct.unpack(">" + "H" * (1 if png.color == 0 else 3), png.trns[:2 if png.color == 0 else 6])
+    key = ph.format_key(png)                                        # (a CgBI file's tRNS reversed: the bgr8 format's key is (b, g, r))
     args = (storage.tobytes(), png.width, png.height, png.depth, png.channels)
     ukw = dict(indexed=kw["indexed"], bgr=kw["bgr"], palette=kw["palette"], key=key)
     got16 = np.frombuffer(s.unpack(*args, target=16, layout=gpu.TARGET_SCALAR, **ukw), dtype="<u2")

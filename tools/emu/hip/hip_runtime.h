@@ -35,6 +35,7 @@ typedef void *hipStream_t;
 static const hipError_t hipSuccess = 0, hipErrorInvalidValue = 1;
 struct dim3 { unsigned x, y, z; dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {} };
 inline hipError_t hipGetLastError() { return hipSuccess; }
+struct alignas(8) uint2 { unsigned x, y; };             // HIP's own vector type (the kernels write the ext_vector_type ones themselves)
 
 #define __device__
 #define __host__
@@ -347,6 +348,7 @@ inline unsigned long long atomicCAS(unsigned long long *p, unsigned long long ex
 }
 inline unsigned atomicMax(unsigned *p, unsigned v) { unsigned o = *p; if (v > o) *p = v; return o; }
 inline unsigned atomicMin(unsigned *p, unsigned v) { unsigned o = *p; if (v < o) *p = v; return o; }
+inline unsigned long long atomicMin(unsigned long long *p, unsigned long long v) { unsigned long long o = *p; if (v < o) *p = v; return o; }
 #ifndef __clang__
 template <class T> inline T __hip_atomic_fetch_min(T *p, T v, int, int) { T o = *p; if (v < o) *p = v; return o; }
 #endif

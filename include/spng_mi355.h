@@ -170,8 +170,8 @@ enum { SPNG_K_INFLATE = 0,          /* the serial inflate kernel (streams the pa
        SPNG_K_PINF_FIND = 8, SPNG_K_PINF_DECODE = 9, SPNG_K_PINF_RESOLVE = 11,   /* its stages */
        SPNG_K_DFL_SEARCH = 13, SPNG_K_DFL_PARSE = 14,   /* levels >= 8: the two kernels of a round (inside SPNG_K_DEFLATE) */
        SPNG_K_ALPHA = 15,           /* spng_alpha_batch */
-       SPNG_K_CENSUS = 16,          /* spng_census_batch: the counting kernel and the sort behind it */
-       SPNG_K_PACK_INDEXED = 17,    /* spng_pack_indexed_batch */
+       SPNG_K_CENSUS = 16,          /* spng_census_batch / spng_census_wide_batch: the counting kernel and the sort behind it */
+       SPNG_K_PACK_INDEXED = 17,    /* spng_pack_indexed_batch / spng_map_batch (the table's build and the lookups) */
        SPNG_K_HSVA = 18,            /* spng_hsva_batch */
        SPNG_K_LUMINANCE = 19,       /* spng_luminance_batch */
        SPNG_K_COUNT = 19 + 1 };     /* 20: one more than the highest id.  (Spelled as a sum because tests/test_hsva_ref.py holds the
@@ -532,6 +532,56 @@ int32_t spng_pack_indexed_batch(spng_ctx *ctx, const spng_pack_indexed_desc *des
 int32_t spng_pack_indexed(spng_ctx *ctx, const void *pixels, uint32_t w, uint32_t h, int source, int layout, int premultiply,
                           const uint32_t *keys, const uint8_t *indices, uint32_t map_count, int miss, void *storage,
                           spng_result *result);
+
+/* ---- pixels: colour tables without a ceiling ----------------------------------------------------------- */
+/* The reference lets a caller put ANY pure function between pixels and storage: the indexer closures above
+ * (PNG.RGBA.swift:409-423, PNG.VA.swift:334-350, PNG.Image.swift:767-782, 935-996) and whole colour targets of the caller's own
+ * (Snippets/PNG/CustomColor.swift).  A pure function of a UInt8 aggregate is a table; the two entries above stop at 65 536 keys and
+ * at one byte per result, these two do not: spng_census_wide_batch reports up to 2^24 distinct keys, the host evaluates the
+ * function once per key, spng_map_batch stores its result -- 1, 2, 4 or 8 bytes -- for every pixel.  A photographic RGBA image
+ * through a nearest-palette indexer, or the CustomColor tutorial's HSVA target (97 388 colours in its picture), is a census, one
+ * vectorised host function over the keys, and a map.
+ *
+ * spng_census_wide_batch: the desc, the key and the output contract of spng_census_batch, with cap = 1 ... SPNG_CENSUS_WIDE_CAP.
+ * Keys ascending with their 64-bit counts, both arrays untouched behind `written`; more than cap keys: SPNG_E_OUTPUT_CAPACITY with
+ * written = 0; a count of 0 is valid; the output is a function of the pixels alone, and for any input spng_census_batch accepts
+ * the bytes are the same.  Scratch of the context is sized by k = min(cap, count) per array, not by cap -- a caller who does not
+ * know the number of colours passes cap = min(n, 2^24) --: 16 bytes per slot of a table of 2 k slots rounded up to a power of two
+ * and 8 per element of a sort buffer of k rounded up to one, at most 80 bytes per key of k, plus 256 per array; spng_trim gives it
+ * back.  The call WAITS once, for the counting kernel, to size the sort behind it by the keys found and not by cap (as
+ * spng_deflate_batch waits for its probe kernel at levels >= 8); it is asynchronous from there on. */
+enum { SPNG_CENSUS_WIDE_CAP = 16777216 };           /* 2^24 */
+int32_t spng_census_wide_batch(spng_ctx *ctx, const spng_census_desc *descs, uint32_t count,
+                               spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous): n pixels; keys: min(cap, max(n, 1)) x uint32; counts: as many uint64, or NULL */
+int32_t spng_census_wide(spng_ctx *ctx, const void *pixels, uint64_t n, int bits, int layout, int premultiply, uint32_t cap,
+                         uint32_t *keys, uint64_t *counts, spng_result *result);
+
+typedef struct spng_map_desc {                      /* 64 bytes */
+    const void *d_pixels;                           /* `count` pixels, aligned to T */
+    void       *d_out;                              /* `count` values of value_bytes, aligned to value_bytes */
+    const void *d_keys;                             /* map_count x uint32, ASCENDING AND DISTINCT: the form the census writes */
+    const void *d_values;                           /* map_count values, aligned to value_bytes: the function's result for each key */
+    uint64_t    count;
+    uint32_t    map_count;                          /* 0 ... SPNG_CENSUS_WIDE_CAP */
+    uint8_t     source;                             /* 8 or 16: T = UInt8 / UInt16; all descs of a call share it */
+    uint8_t     layout, premultiply;                /* as in spng_pack_indexed_desc */
+    uint8_t     value_bytes;                        /* 1, 2, 4 or 8 */
+    uint8_t     miss[8];                            /* the first value_bytes bytes: written for a pixel whose key is not in d_keys */
+    uint8_t     reserved[8];                        /* zero */
+} spng_map_desc;
+/* Every pixel stores d_values[j] where d_keys[j] equals its key, and `miss` where none does.  Results: status SPNG_DONE, written =
+ * bytes written, consumed = pixels, aux[0] = pixels that missed.  With value_bytes == 1 and map_count <= 65536 the bytes are those of
+ * spng_pack_indexed_batch.  Keys that are not ascending and distinct are the caller's responsibility here (device memory is not
+ * looked at by the host): the order does not matter to this entry, and a key present twice resolves to its LOWEST position --
+ * deterministic, never a hang, never an access outside the arrays; the host-pointer form below sees such keys and returns
+ * SPNG_E_ARGUMENT.  Scratch of the context, for maps above 512 keys: 8 bytes per slot of a table of 2 x map_count slots rounded up
+ * to a power of two (at most 32 bytes per key); spng_trim gives it back. */
+int32_t spng_map_batch(spng_ctx *ctx, const spng_map_desc *descs, uint32_t count,
+                       spng_result *d_results, spng_result *h_results);
+/* host-pointer convenience (copies in / out, synchronous): n pixels; values, miss and out hold items of value_bytes */
+int32_t spng_map(spng_ctx *ctx, const void *pixels, uint64_t n, int source, int layout, int premultiply, const uint32_t *keys,
+                 const void *values, uint32_t map_count, int value_bytes, const void *miss, void *out, spng_result *result);
 
 /* ---- encode -------------------------------------------------------------------------------- */
 /* replaces PNG.Encoder.filter (PNG.Encoder.swift:132-204) + PNG.Image.collect

@@ -52,6 +52,11 @@ LUMINANCE_V8, LUMINANCE_VA8 = 1, 2                          # (the op is also th
 CENSUS_LDS_SLOTS, CENSUS_LDS_LIMIT = 2048, 512     # a workgroup's table; keys in it above which it is merged into the image's
 CENSUS_FINISH_LDS_KEYS = 4096                      # up to so many keys are sorted in LDS, more in the context's scratch
 PACK_INDEXED_LDS_KEYS = 512                        # maps of up to so many keys sit in an LDS hash table, larger ones are searched
+# thresholds of csrc/colour_tables.hip (tests/test_colour_tables_host.py compares them with the source's)
+CENSUS_WIDE_CAP = 1 << 24                          # keys of a wide census, and of a map
+CENSUS_WIDE_TILE = 4096                            # elements a workgroup sorts in LDS; every stride from here on is a launch of its own
+MAP_LDS_KEYS, MAP_LDS_SLOTS = 512, 2048            # maps of up to so many keys sit in an LDS hash table (of so many slots),
+MAP_MIN_SLOTS = 64                                 # larger ones in scratch: max(this, 2 x map_count rounded up to a power of two) slots
 CFG_INFLATE_MODE, CFG_SEGMENT_BYTES, CFG_TOKEN_BYTES, CFG_UNFILTER_PIECE_ROWS, CFG_RESOLVE_PARTS = 0, 1, 2, 3, 5          # (4: reserved)
 CFG_DEFLATE_BYTES, CFG_MULTI_GROUPS = 7, 8          # (6: reserved)
 CFG_BLOCK_CUT_BYTES = 9                            # parallel inflate: shortest run of segments without a block start that is cut (bytes; 0: 1 MiB)
@@ -64,7 +69,7 @@ EXPORTS = [
     "spng_profile_get", "spng_token_stats", "spng_cut_stats", "spng_configure", "spng_inflate_batch", "spng_inflate_resume_batch", "spng_unfilter_batch",
     "spng_unfilter_resume_batch", "spng_decode_batch",
     "spng_inflate", "spng_unfilter", "spng_decode", "spng_adler32", "spng_filter_batch", "spng_filter",
-    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_luminance_batch", "spng_luminance", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
+    "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_luminance_batch", "spng_luminance", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_census_wide_batch", "spng_census_wide", "spng_map_batch", "spng_map", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
 ]
 
@@ -152,6 +157,13 @@ class PackIndexedDesc(ctypes.Structure):
                 ("d_indices", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
                 ("map_count", ctypes.c_uint32), ("source", ctypes.c_uint8), ("layout", ctypes.c_uint8),
                 ("premultiply", ctypes.c_uint8), ("miss", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 8)]
+
+
+class MapDesc(ctypes.Structure):
+    _fields_ = [("d_pixels", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_keys", ctypes.c_void_p), ("d_values", ctypes.c_void_p),
+                ("count", ctypes.c_uint64), ("map_count", ctypes.c_uint32), ("source", ctypes.c_uint8), ("layout", ctypes.c_uint8),
+                ("premultiply", ctypes.c_uint8), ("value_bytes", ctypes.c_uint8), ("miss", ctypes.c_uint8 * 8),
+                ("reserved", ctypes.c_uint8 * 8)]
 
 
 class ChunkingDesc(ctypes.Structure):
@@ -292,6 +304,10 @@ def load_library():
     lib.spng_census.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32, vp, vp, rp]
     lib.spng_pack_indexed_batch.argtypes = [vp, vp, u32, vp, rp]
     lib.spng_pack_indexed.argtypes = [vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, u32, ctypes.c_int, vp, rp]
+    lib.spng_census_wide_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_census_wide.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32, vp, vp, rp]
+    lib.spng_map_batch.argtypes = [vp, vp, u32, vp, rp]
+    lib.spng_map.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, u32, ctypes.c_int, vp, vp, rp]
     lib.spng_deflate_bound.restype = u64
     lib.spng_deflate_bound.argtypes = [u64]
     lib.spng_deflate_batch.argtypes = [vp, ctypes.POINTER(StreamDesc), ctypes.POINTER(i32), u32, vp, rp]
@@ -369,6 +385,26 @@ def _cbuf(data):
 def pick(v, i):
     """an argument of a batch call that holds one value, or one per array: the value for array i"""
     return v[i] if isinstance(v, (list, tuple)) else v
+
+
+def census_wide_sort_launches(keys) -> int:
+    """launches of the sort of a wide census that found `keys` keys (between its gather and its write): one that sorts the tiles,
+    then per stage above a tile one per stride of at least a tile and one for the strides below"""
+    np_, launches, k = 1, 1, 2 * CENSUS_WIDE_TILE
+    while np_ < keys:
+        np_ <<= 1
+    while k <= np_:
+        launches += (k // 2 // CENSUS_WIDE_TILE).bit_length() + 1
+        k <<= 1
+    return launches
+
+
+def miss_bytes(miss, value_bytes) -> bytes:
+    """the `miss` of a map as the value_bytes bytes of spng_map_desc.miss: an int (little-endian) or bytes of that length"""
+    b = bytes(miss) if isinstance(miss, (bytes, bytearray)) else int(miss).to_bytes(value_bytes, "little")
+    if len(b) != value_bytes:
+        raise ValueError("a miss value of value_bytes bytes is needed")
+    return b
 
 
 def pixel_bytes(layout, bits) -> int:
@@ -680,7 +716,8 @@ class Session:
         indexer (indexed8 only): shaped like the reference's (init(packing:size:layout:metadata:indexer:), PNG.Image.swift:935-996):
         indexer(palette) returns a function of the UInt8 aggregate -- (r, g, b, a), (v, a) or v -- that returns the index.  Scalar
         and VA layouts tabulate it over all 256 / 65536 aggregates; the RGBA layout asks the device for the distinct colours of the
-        pixels (census, at most 65536: SpngError(E_OUTPUT_CAPACITY) above) and calls it once per colour."""
+        pixels (census, at most 65536: SpngError(E_OUTPUT_CAPACITY) above) and calls it once per colour.  Images of more colours:
+        map_colours with dtype uint8, whose function takes all keys at once."""
         if indexer is not None:
             if not indexed or depth != 8:
                 raise ValueError("an indexer needs the indexed8 format")
@@ -712,8 +749,8 @@ class Session:
                                                int(layout), _cbuf(palette) if palette else None, len(palette or b"") // 4, out))
         return bytes(out[:n])
 
-    def census_batch(self, arrays, bits, layout, cap=256, premultiply=0, counts=True, outs=None):
-        """spng_census_batch on device tensors: every tensor of `arrays` holds whole RGBA<T> / VA<T> / T pixels (T of `bits`
+    def census_batch(self, arrays, bits, layout, cap=256, premultiply=0, counts=True, outs=None, wide=False):
+        """spng_census_batch (wide: spng_census_wide_batch, see census_wide_batch) on device tensors: every tensor of `arrays` holds whole RGBA<T> / VA<T> / T pixels (T of `bits`
         bits; layout, cap and premultiply: one value, or one per array).  -> (list of (keys, counts) device tensors -- int32 /
         int64 bit patterns of the uint32 keys and uint64 counts, `cap` long, valid up to Result.written; or the (keys, counts) pairs of
         `outs`, of at least 4 * cap / 8 * cap bytes --, list[Result]).  Like every batch entry it runs on the context's stream: tensors
@@ -727,18 +764,112 @@ class Session:
             nbytes, per = a.numel() * a.element_size(), pixel_bytes(lay, bits)
             if nbytes % per:
                 raise ValueError("an array of whole pixels is needed")
+            room = min(cp, max(nbytes // per, 1)) if wide else cp           # (wide: no more keys than pixels)
             if given is not None:
                 k, c = given[i]
-                if k.numel() * k.element_size() < 4 * cp or (c is not None and c.numel() * c.element_size() < 8 * cp):
+                if k.numel() * k.element_size() < 4 * room or (c is not None and c.numel() * c.element_size() < 8 * room):
                     raise ValueError("outputs of cap keys and cap counts are needed")
             else:
-                k = t.empty(max(cp, 1), dtype=t.int32, device=self.tdev)
-                c = t.empty(max(cp, 1), dtype=t.int64, device=self.tdev) if counts else None
+                k = t.empty(max(room, 1), dtype=t.int32, device=self.tdev)
+                c = t.empty(max(room, 1), dtype=t.int64, device=self.tdev) if counts else None
             outs.append((k, c))
             descs[i] = CensusDesc(self._ptr(a), nbytes // per, self._ptr(k), self._ptr(c), cp, bits, lay, pick(premultiply, i))
         res = (Result * max(n, 1))()
-        _check(self.lib, self.lib.spng_census_batch(self.ctx, descs, n, None, res))
+        entry = self.lib.spng_census_wide_batch if wide else self.lib.spng_census_batch
+        _check(self.lib, entry(self.ctx, descs, n, None, res))
         return outs, list(res)[:n]
+
+    def census_wide_batch(self, arrays, bits, layout, cap=CENSUS_WIDE_CAP, premultiply=0, counts=True, outs=None):
+        """spng_census_wide_batch on device tensors: census_batch with cap up to CENSUS_WIDE_CAP (2^24).  The outputs hold
+        min(cap, pixels) keys and counts -- an array has no more keys than pixels, so the default cap asks for "all of them".  The
+        call waits once, for the counting kernel."""
+        return self.census_batch(arrays, bits, layout, cap, premultiply, counts, outs, wide=True)
+
+    def census_wide(self, pixels: bytes, bits, layout, cap=CENSUS_WIDE_CAP, premultiply=0):
+        """census without the ceiling of 65536 keys: -> (keys, counts) as numpy arrays (uint32 ascending, uint64).  More than `cap`
+        (at most 2^24) distinct keys raise SpngError(E_OUTPUT_CAPACITY)."""
+        import numpy as np
+        per = pixel_bytes(layout, bits)
+        if len(pixels) % per:
+            raise ValueError("whole pixels are needed")
+        n = len(pixels) // per
+        room = max(min(cap, n), 1)
+        keys, counts = np.empty(room, dtype=np.uint32), np.empty(room, dtype=np.uint64)
+        res = Result()
+        _check(self.lib, self.lib.spng_census_wide(self.ctx, _cbuf(pixels), n, bits, int(layout), int(premultiply), cap, keys.ctypes.data,
+                                                   counts.ctypes.data, ctypes.byref(res)))
+        raise_for(res.status)
+        return keys[:res.written], counts[:res.written]
+
+    def map_batch(self, arrays, source, layout, keys, values, value_bytes, miss=0, premultiply=0, outs=None):
+        """spng_map_batch on device tensors: every pixel of arrays[i] (whole RGBA<T> / VA<T> / T pixels, T of `source` bits) stores
+        values[i][j] -- items of value_bytes (1, 2, 4 or 8; one value, or one per array) bytes -- where keys[i][j] (uint32, ascending
+        and distinct, int32 bit patterns) is its key, and `miss` (an int or value_bytes bytes) where none is.  -> (list of uint8 output
+        tensors of pixels * value_bytes bytes, or `outs`; list[Result] with aux[0] = pixels that missed)"""
+        n = len(arrays)
+        descs = (MapDesc * max(n, 1))()
+        given, outs = outs, []
+        for i, a in enumerate(arrays):
+            lay, vb = pick(layout, i), pick(value_bytes, i)
+            nbytes, per = a.numel() * a.element_size(), pixel_bytes(lay, source)
+            if nbytes % per:
+                raise ValueError("an array of whole pixels is needed")
+            o = given[i] if given is not None else self.empty(nbytes // per * vb)
+            outs.append(o)
+            k, v = keys[i], values[i]
+            mc = k.numel() if k is not None else 0
+            descs[i] = MapDesc(self._ptr(a), self._ptr(o), self._ptr(k) if mc else None, self._ptr(v) if mc else None, nbytes // per, mc,
+                               source, lay, pick(premultiply, i), vb, (ctypes.c_uint8 * 8)(*miss_bytes(pick(miss, i), vb)))
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_map_batch(self.ctx, descs, n, None, res))
+        return outs, list(res)[:n]
+
+    def map(self, pixels: bytes, source, layout, keys, values, miss=0, premultiply=0):
+        """One value per pixel: values[j] -- a numpy array whose items have 1, 2, 4 or 8 bytes -- where keys[j] (ascending, distinct)
+        is the pixel's key, `miss` (an int or bytes of one item) where none is.  -> (numpy array of values' dtype, pixels that missed)"""
+        import numpy as np
+        per = pixel_bytes(layout, source)
+        if len(pixels) % per:
+            raise ValueError("whole pixels are needed")
+        values = np.ascontiguousarray(values)
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        vb = values.dtype.itemsize
+        if vb not in (1, 2, 4, 8) or values.ndim != 1:
+            raise ValueError("values of 1, 2, 4 or 8 bytes each are needed")
+        if len(keys) != len(values):
+            raise ValueError("one value per key is needed")
+        n = len(pixels) // per
+        out = np.empty(max(n, 1), dtype=values.dtype)
+        res = Result()
+        _check(self.lib, self.lib.spng_map(self.ctx, _cbuf(pixels), n, source, int(layout), int(premultiply), keys.ctypes.data if len(keys) else None,
+                                           values.ctypes.data if len(keys) else None, len(keys), vb, _cbuf(miss_bytes(miss, vb)),
+                                           out.ctypes.data, ctypes.byref(res)))
+        raise_for(res.status)
+        return out[:n], int(res.aux[0])
+
+    def map_colours(self, pixels: bytes, bits, layout, fn, dtype, premultiply=0, miss=0):
+        """Any pure function of a pixel's UInt8 aggregate, applied to every pixel on the device: an indexer closure
+        (PNG.RGBA.swift:409-423, PNG.VA.swift:334-350, PNG.Image.swift:767-782) or a colour target of the caller's own
+        (Snippets/PNG/CustomColor.swift), as a table.  A wide census (cap = min(pixels, 2^24)) finds the distinct keys; fn(keys) is
+        called ONCE, with the ascending uint32 numpy array of them (r | g << 8 | b << 16 | a << 24, v | a << 8 or v), and returns
+        an array of `dtype` -- 1, 2, 4 or 8 bytes per item, structured dtypes included --, one item per key; the map stores it for
+        every pixel.  -> numpy array of dtype, one item per pixel.  With dtype uint8 this is pack(indexer=) for images of more than
+        65536 colours (vectorised: a million Python calls is not an interface).  `miss` is never stored: every key is in the table."""
+        import numpy as np
+        dtype = np.dtype(dtype)
+        if dtype.itemsize not in (1, 2, 4, 8):
+            raise ValueError("a dtype of 1, 2, 4 or 8 bytes is needed")
+        per = pixel_bytes(layout, bits)
+        if len(pixels) % per:
+            raise ValueError("whole pixels are needed")
+        n = len(pixels) // per
+        keys, _ = self.census_wide(pixels, bits, layout, cap=max(min(n, CENSUS_WIDE_CAP), 1), premultiply=premultiply)
+        keys = np.asarray(keys, dtype=np.uint32)
+        values = np.ascontiguousarray(np.asarray(fn(keys), dtype=dtype))
+        if values.shape != keys.shape:
+            raise ValueError("fn returns one item per key")
+        out, _ = self.map(pixels, bits, layout, keys, values.view("V%d" % dtype.itemsize), miss=miss, premultiply=premultiply)
+        return np.asarray(out).view(dtype)
 
     def census(self, pixels: bytes, bits, layout, cap=256, premultiply=0):
         """The distinct UInt8 aggregates ("keys": r | g << 8 | b << 16 | a << 24, v | a << 8 or v) of [PNG.RGBA<T>] / [PNG.VA<T>] /

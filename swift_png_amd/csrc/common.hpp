@@ -183,6 +183,20 @@ struct PackIndexedJob {
     uint8_t        layout, premultiply, miss, pad;
 };
 
+// One array of pixels mapped through a table from keys to values of 1, 2, 4 or 8 bytes (colour_tables.hip, map_build_kernel + map_kernel)
+struct MapJob {
+    const void    *pixels;
+    void          *out;           // one value per pixel
+    const uint32_t *keys;         // map_count keys, ascending and distinct
+    const void    *values;
+    spng_result   *result;        // filled in by the host; the kernel adds the pixels that missed to aux[0]
+    uint64_t       count;         // pixels
+    uint64_t       miss;          // the value of a pixel whose key is not in the map (its low value_bytes bytes)
+    uint64_t       table_off;     // slots != 0: where the map's hash table starts in the call's scratch, in slots
+    uint32_t       map_count, slots, slot_bits;      // slots == 0: the table is built in LDS by every workgroup
+    uint8_t        layout, premultiply, value_bytes, pad;
+};
+
 struct InflateJob {
     const uint8_t *src;
     uint8_t       *dst;
@@ -436,6 +450,12 @@ uint32_t census_slots(uint32_t cap);                       // slots of an image'
 uint32_t census_sort_elems(uint32_t cap);
 hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
 hipError_t launch_pack_indexed(const PackIndexedJob *d_jobs, uint32_t count, uint32_t blocks_x, int source, hipStream_t stream);
+// colour_tables.hip (the counting stage of the wide census is census_kernel: launch_census_count, indexing.hip)
+hipError_t launch_census_count(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream);
+hipError_t launch_census_wide_finish(const CensusJob *d_jobs, uint32_t count, uint32_t most_slots, uint32_t most_keys, hipStream_t stream);
+uint32_t map_slots(uint32_t map_count);                    // slots of a map's table in scratch; 0: it sits in LDS
+hipError_t launch_map(const MapJob *d_jobs, uint32_t count, unsigned long long *d_scratch, uint32_t build_blocks_x, uint32_t blocks_x,
+                      int source, hipStream_t stream);
 size_t lex_chunk_bytes();
 size_t lex_walk_bytes();
 hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed *d_out, void *d_table, const uint64_t *d_table_at,

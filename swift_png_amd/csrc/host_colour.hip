@@ -401,4 +401,147 @@ int32_t spng_pack_indexed(spng_ctx *c, const void *pixels, uint32_t w, uint32_t 
     return SPNG_DONE;
 }
 
+// ---- colour tables without a ceiling (colour_tables.hip) -----------------------------------------
+
+// what a census of `count` pixels at `cap` can find at most: its table and its sort buffer are sized by this, not by cap
+static uint32_t census_wide_keys(const spng_census_desc &d) { return (uint32_t)std::min<uint64_t>(d.cap, d.count ? d.count : 1); }
+
+int32_t spng_census_wide_batch(spng_ctx *c, const spng_census_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    const int bits = descs[0].bits;
+    if (bits != 8 && bits != 16) return SPNG_E_ARGUMENT;
+    // the scratch: the ctrl blocks of all arrays first -- one copy brings them to the host --, their {tags, counts} behind them
+    // -- one block to zero --, the sort buffers last
+    uint64_t zeroed = 256ull * count, sorts = 0, most = 1;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_census_desc &d = descs[i];
+        if (d.bits != bits || d.layout > SPNG_TARGET_SCALAR || !valid_premultiply(d.premultiply, bits, d.layout, SPNG_PREMULTIPLY_AS_U8) ||
+            d.cap < 1 || d.cap > SPNG_CENSUS_WIDE_CAP || !d.d_keys || ((uintptr_t)d.d_keys & 3) || ((uintptr_t)d.d_counts & 7) ||
+            (d.count && !d.d_pixels) || ((uintptr_t)d.d_pixels & (bits / 8 - 1)) || d.count > (~0ull >> 4) || !all_zero(d.reserved))
+            return SPNG_E_ARGUMENT;
+        zeroed += 16ull * census_slots(census_wide_keys(d));
+        sorts += 8ull * census_sort_elems(census_wide_keys(d));
+        most = d.count > most ? d.count : most;
+    }
+    if (int32_t st = c->grow(c->d_census, c->census_cap, zeroed + sorts, 0)) return st;
+    if (int32_t st = c->reserve(count * (sizeof(CensusJob) + sizeof(spng_result)) + 1024)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(CensusJob)), rslot = a.take(count * sizeof(spng_result));
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    char *z = (char *)c->d_census + 256ull * count, *srt = (char *)c->d_census + zeroed;
+    uint32_t most_slots = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_census_desc &d = descs[i];
+        CensusJob j;
+        memset(&j, 0, sizeof j);
+        j.pixels = d.d_pixels; j.count = d.count; j.keys = (uint32_t *)d.d_keys; j.out_counts = (uint64_t *)d.d_counts;
+        j.cap = d.cap; j.slots = census_slots(census_wide_keys(d));
+        for (j.slot_bits = 0; (1u << j.slot_bits) < j.slots; ++j.slot_bits) {}
+        j.ctrl = (uint32_t *)((char *)c->d_census + 256ull * i); j.tags = (unsigned long long *)z; j.counts = j.tags + j.slots;
+        z += 16ull * j.slots;
+        j.sort = (unsigned long long *)srt; srt += 8ull * census_sort_elems(census_wide_keys(d));
+        j.result = dr + i; j.layout = d.layout; j.premultiply = d.premultiply;
+        a.host<CensusJob>(jslot)[i] = j;
+        most_slots = j.slots > most_slots ? j.slots : most_slots;
+    }
+    HIP_TRY(hipMemsetAsync(c->d_census, 0, zeroed, c->stream));
+    if (int32_t st = c->upload(0, a.off)) return st;
+    { Timed t(c, SPNG_K_CENSUS); HIP_TRY(launch_census_count(a.dev<CensusJob>(jslot), count, census_blocks_x(count, most), bits, c->stream)); }
+    // the one wait: the stages behind are sized by the keys found, not by cap
+    std::vector<uint32_t> ctrl(64ull * count);
+    HIP_TRY(hipMemcpyAsync(ctrl.data(), c->d_census, 256ull * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t most_keys = 0;
+    for (uint32_t i = 0; i < count; ++i)
+        if (!ctrl[64ull * i + 1] && ctrl[64ull * i] <= descs[i].cap) most_keys = std::max(most_keys, ctrl[64ull * i]);
+    { Timed t(c, SPNG_K_CENSUS); HIP_TRY(launch_census_wide_finish(a.dev<CensusJob>(jslot), count, most_slots, most_keys, c->stream)); }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+int32_t spng_census_wide(spng_ctx *c, const void *pixels, uint64_t n, int bits, int layout, int premultiply, uint32_t cap,
+                         uint32_t *keys, uint64_t *counts, spng_result *result)
+{
+    if (!c || (n && !pixels) || !keys || !result || (bits != 8 && bits != 16) || layout < 0 || layout > SPNG_TARGET_SCALAR ||
+        premultiply < 0 || premultiply > 255 || cap < 1 || cap > SPNG_CENSUS_WIDE_CAP || n > (~0ull >> 4)) return SPNG_E_ARGUMENT;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t most = (size_t)std::min<uint64_t>(cap, n ? n : 1);           // (no more keys than pixels)
+    DevBuf dpx, dk, dc;
+    HIP_TRY(dpx.alloc_from(pixels, n * pixel_bytes(layout, bits), c->stream));
+    HIP_TRY(dk.alloc(most * 4)); HIP_TRY(dc.alloc(most * 8));
+    spng_census_desc d{};
+    d.d_pixels = dpx.p; d.count = n; d.d_keys = dk.p; d.d_counts = counts ? dc.p : nullptr; d.cap = cap;
+    d.bits = (uint8_t)bits; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply;
+    if (int32_t st = spng_census_wide_batch(c, &d, 1, nullptr, result)) return st;
+    if (result->status == SPNG_DONE) {
+        HIP_TRY(dk.copy_to(keys, result->written * 4));
+        if (counts) HIP_TRY(dc.copy_to(counts, result->written * 8));
+    }
+    return SPNG_DONE;
+}
+
+static bool valid_value_bytes(int v) { return v == 1 || v == 2 || v == 4 || v == 8; }
+
+int32_t spng_map_batch(spng_ctx *c, const spng_map_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    uint64_t table_slots = 0;                                   // of the maps that do not sit in LDS, one behind the other
+    uint32_t most_keys = 0;
+    return result_batch<MapJob>(c, descs, count, d_results, h_results,
+        [&](const spng_map_desc &d, MapJob &j, spng_result &r, uint64_t &extent) {
+            const int source = descs[0].source;
+            const uintptr_t align = (uintptr_t)d.value_bytes - 1;
+            if ((source != 8 && source != 16) || d.source != source || d.layout > SPNG_TARGET_SCALAR ||
+                !valid_premultiply(d.premultiply, source, d.layout, SPNG_PREMULTIPLY_AS_U8) || !valid_value_bytes(d.value_bytes) ||
+                d.map_count > SPNG_CENSUS_WIDE_CAP || (d.map_count && (!d.d_keys || !d.d_values)) || ((uintptr_t)d.d_keys & 3) ||
+                ((uintptr_t)d.d_values & align) || ((uintptr_t)d.d_out & align) || (d.count && (!d.d_pixels || !d.d_out)) ||
+                ((uintptr_t)d.d_pixels & (source / 8 - 1)) || d.count > (~0ull >> 4) || !all_zero(d.reserved)) return false;
+            j.pixels = d.d_pixels; j.out = d.d_out; j.keys = (const uint32_t *)d.d_keys; j.values = d.d_values;
+            j.count = d.count; j.map_count = d.map_count; j.layout = d.layout; j.premultiply = d.premultiply; j.value_bytes = d.value_bytes;
+            memcpy(&j.miss, d.miss, d.value_bytes);             // (little-endian, like the values)
+            j.slots = map_slots(d.map_count);
+            if (j.slots) {
+                for (j.slot_bits = 0; (1u << j.slot_bits) < j.slots; ++j.slot_bits) {}
+                j.table_off = table_slots; table_slots += j.slots;
+                most_keys = d.map_count > most_keys ? d.map_count : most_keys;
+            }
+            r.written = d.count * d.value_bytes; r.consumed = extent = d.count;   // (aux[0]: the kernel adds the pixels that missed)
+            return true;
+        },
+        [&](const MapJob *d_jobs, uint32_t n, uint64_t most) {
+            if (table_slots) {
+                if (c->grow(c->d_census, c->census_cap, 8 * table_slots, 0)) return hipErrorOutOfMemory;     // (the text: spng_last_error_string)
+                const hipError_t e = hipMemsetAsync(c->d_census, 0, 8 * table_slots, c->stream);
+                if (e != hipSuccess) return e;
+            }
+            Timed t(c, SPNG_K_PACK_INDEXED);                    // (four pixels per thread, four keys per thread of the build)
+            return launch_map(d_jobs, n, (unsigned long long *)c->d_census, table_slots ? blocks_for(most_keys, 1024) : 0,
+                              blocks_for(most, 4096), descs[0].source, c->stream);
+        });
+}
+
+int32_t spng_map(spng_ctx *c, const void *pixels, uint64_t n, int source, int layout, int premultiply, const uint32_t *keys,
+                 const void *values, uint32_t map_count, int value_bytes, const void *miss, void *out, spng_result *result)
+{
+    if (!c || !result || (n && (!pixels || !out)) || (source != 8 && source != 16) || layout < 0 || layout > SPNG_TARGET_SCALAR ||
+        premultiply < 0 || premultiply > 255 || !valid_value_bytes(value_bytes) || !miss || map_count > SPNG_CENSUS_WIDE_CAP ||
+        (map_count && (!keys || !values)) || n > (~0ull >> 4)) return SPNG_E_ARGUMENT;
+    for (uint32_t i = 1; i < map_count; ++i) if (keys[i] <= keys[i - 1]) return SPNG_E_ARGUMENT;   // ascending and distinct
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t obytes = n * (uint64_t)value_bytes;
+    DevBuf dpx, dout, dk, dv;
+    HIP_TRY(dpx.alloc_from(pixels, n * pixel_bytes(layout, source), c->stream)); HIP_TRY(dout.alloc(obytes));
+    HIP_TRY(dk.alloc_from(keys, (size_t)map_count * 4, c->stream)); HIP_TRY(dv.alloc_from(values, (size_t)map_count * value_bytes, c->stream));
+    spng_map_desc d{};
+    d.d_pixels = dpx.p; d.d_out = dout.p; d.d_keys = map_count ? dk.p : nullptr; d.d_values = map_count ? dv.p : nullptr;
+    d.count = n; d.map_count = map_count;
+    d.source = (uint8_t)source; d.layout = (uint8_t)layout; d.premultiply = (uint8_t)premultiply; d.value_bytes = (uint8_t)value_bytes;
+    memcpy(d.miss, miss, value_bytes);
+    if (int32_t st = spng_map_batch(c, &d, 1, nullptr, result)) return st;
+    HIP_TRY(dout.copy_to(out, obytes));
+    return SPNG_DONE;
+}
+
 }  // extern "C"

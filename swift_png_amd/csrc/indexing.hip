@@ -13,12 +13,9 @@
 //
 // Both kernels are HBM-bound by design: four pixels per lane, 16-byte loads where the pixels are aligned, one dword of four indices
 // out where the storage is.
-#include "alpha.hpp"
+#include "indexing.hpp"                                        // (the key of a pixel: quad_keys, index_hash)
 
 namespace spng {
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 
 // ---- thresholds (mirrored in swift_png_amd/__init__.py; tests/test_indexing_host.py compares the two) -----------------------------
 static constexpr uint32_t CENSUS_LDS_SLOTS = 2048;              // a workgroup's private table: 64-bit slots, open addressing
@@ -28,60 +25,6 @@ static constexpr uint32_t CENSUS_MIN_SLOTS = 64;                // the image's t
 static constexpr uint32_t CENSUS_FINISH_LDS_KEYS = 4096;        // up to so many keys (rounded up to a power of two) are sorted in LDS
 static constexpr uint32_t PACK_INDEXED_LDS_KEYS = 512;          // maps of up to so many keys are looked up in an LDS hash table,
 static constexpr uint32_t PACK_INDEXED_LDS_SLOTS = 2048;        // (of so many slots), larger ones by binary search over d_keys
-
-__device__ __forceinline__ uint32_t index_hash(uint32_t key) { return key * 0x9E3779B1u; }   // (the TOP bits are the slot)
-
-// The keys of the (up to four) pixels i0 .. i0 + m of an array of RGBA<T> (LAYOUT 0), VA<T> (1) or T (2).  vec: the array is aligned
-// to a whole quad (at most 16 bytes): one or two vector loads.  Keys behind m are 0 and not to be used.
-template <typename T, int LAYOUT>
-__device__ __forceinline__ void quad_keys(const T *in, uint64_t i0, uint32_t m, bool vec, uint32_t premultiply, uint32_t (&key)[4])
-{
-    constexpr uint32_t TB = sizeof(T) * 8, NC1 = LAYOUT == 0 ? 4 : LAYOUT == 1 ? 2 : 1, ND = NC1 * sizeof(T);   // dwords per quad
-    constexpr uint32_t MASK = TB == 8 ? 0xffu : 0xffffu;
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // the quad's bytes in memory order
-    const T *p = in + i0 * NC1;
-    if (vec && m == 4) {
-        if (ND == 1) w[0] = *(const uint32_t *)p;
-        else if (ND == 2) { const v2u v = *(const v2u *)p; w[0] = v[0]; w[1] = v[1]; }
-        else {
-#pragma unroll
-            for (uint32_t d = 0; d < ND; d += 4) {
-                const v4u v = *(const v4u *)((const uint32_t *)p + d);
-                w[d] = v[0]; w[d + 1] = v[1]; w[d + 2] = v[2]; w[d + 3] = v[3];
-            }
-        }
-    } else {
-#pragma unroll
-        for (uint32_t e = 0; e < 4 * NC1; ++e)
-            if (e < m * NC1) w[(e * sizeof(T)) >> 2] |= (uint32_t)p[e] << 8 * ((e * sizeof(T)) & 3);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        uint32_t c[4];
-#pragma unroll
-        for (uint32_t z = 0; z < NC1; ++z) {
-            const uint32_t off = (k * NC1 + z) * sizeof(T);
-            c[z] = (w[off >> 2] >> 8 * (off & 3)) & MASK;
-        }
-        uint32_t none = 0;
-        if (LAYOUT == 0) {
-            if (premultiply) { uint32_t rgb[3] = {c[0], c[1], c[2]}; alpha_pixel_op<TB, 3>(premultiply, rgb, c[3], none); c[0] = rgb[0]; c[1] = rgb[1]; c[2] = rgb[2]; }
-            key[k] = (c[0] >> (TB - 8)) | (c[1] >> (TB - 8)) << 8 | (c[2] >> (TB - 8)) << 16 | (c[3] >> (TB - 8)) << 24;
-        } else if (LAYOUT == 1) {
-            if (premultiply) { uint32_t v[1] = {c[0]}; alpha_pixel_op<TB, 1>(premultiply, v, c[1], none); c[0] = v[0]; }
-            key[k] = (c[0] >> (TB - 8)) | (c[1] >> (TB - 8)) << 8;
-        } else {
-            key[k] = c[0] >> (TB - 8);
-        }
-    }
-}
-
-template <typename T, int LAYOUT>
-__device__ __forceinline__ bool quad_aligned(const void *pixels)
-{
-    constexpr uint32_t QB = 4 * (LAYOUT == 0 ? 4 : LAYOUT == 1 ? 2 : 1) * sizeof(T);
-    return ((uintptr_t)pixels & ((QB < 16 ? QB : 16) - 1)) == 0;
-}
 
 // ---- census -------------------------------------------------------------------------------------------------------------------
 // The image's table (context scratch, zeroed by the host in front of every call): `slots` tags -- 0: empty, else key << 32 | 1, so
@@ -367,14 +310,20 @@ uint32_t census_sort_elems(uint32_t cap)
     return s;
 }
 
-hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream)
+// the counting stage alone (spng_census_wide_batch finishes with the launches of colour_tables.hip)
+hipError_t launch_census_count(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream)
 {
-    if (!count) return hipSuccess;
-    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
         const dim3 grid(blocks_x ? blocks_x : 1, ny);
         if (bits == 8) census_kernel<uint8_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
         else census_kernel<uint16_t><<<grid, 256, 0, stream>>>(d_jobs + y0);
     });
+}
+
+hipError_t launch_census(const CensusJob *d_jobs, uint32_t count, uint32_t blocks_x, int bits, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    const hipError_t e = launch_census_count(d_jobs, count, blocks_x, bits, stream);
     if (e != hipSuccess) return e;
     census_finish_kernel<<<count, 1024, 0, stream>>>(d_jobs);
     return hipGetLastError();

@@ -270,6 +270,25 @@ typedef struct spng_lexed {
  * IHDR layout, and the IDAT loop (PNG.Image.swift:385-389) -- for whole files already in HBM. */
 int32_t spng_lex_batch(spng_ctx *ctx, const spng_file_desc *files, uint32_t count,
                        spng_lexed *d_infos, spng_lexed *h_infos);
+/* Files that arrive in pieces: signature() and chunk() retried on truncatedSignature / truncatedChunkHeader / truncatedChunkBody until
+ * the bytes are there -- waitSignature / waitChunk of Snippets/PNG/OnlineDecoding.swift -- with the loop's state kept on the device.
+ * files[i].d_png / len: ALL bytes of the file received so far (the caller appends to its device buffer, as for
+ * spng_inflate_resume_batch); d_idat / idat_cap: the IDAT payloads so far, kept between calls.  d_states[i]: spng_lex_state_bytes()
+ * bytes of device memory per file, zero-filled before the first push and left alone afterwards (as for spng_deflate_resume_batch; a
+ * call with d_infos only stays asynchronous).  After every call infos[i] is byte for byte what spng_lex_batch reports for the same
+ * prefix as a whole file, and d_idat[0 .. idat_len) holds the same bytes; behind idat_len the buffer is unspecified (the chunk in
+ * progress is copied ahead of its checksum).  The three truncation statuses are the "wait" answers.  Every other status but
+ * SPNG_DONE is final: later calls repeat it and read nothing; behind IEND further bytes are ignored.  SPNG_E_ARGUMENT in a file's
+ * status (the host does not look into device memory): a null state, a state whose fields contradict each other, a len smaller than
+ * what the state has consumed.  Over all pushes of a file every byte of a chunk's type + data goes through the CRC once and every
+ * IDAT byte is copied once, however the pushes cut the file (the chunk the input ends in is summed as far as it has arrived; only
+ * its 8-byte header is read again); a chunk whose new bytes exceed 1 MiB is summed in pieces of 1 MiB by a wave each. */
+uint64_t spng_lex_state_bytes(void);
+int32_t spng_lex_resume_batch(spng_ctx *ctx, const spng_file_desc *files, void *const *d_states, uint32_t count,
+                              spng_lexed *d_infos, spng_lexed *h_infos);
+/* The most recent spng_lex_resume_batch, summed over its files: bytes that went through the CRC, IDAT bytes copied, chunk headers
+ * walked.  Waits for the context's stream; any pointer may be NULL. */
+int32_t spng_lex_resume_stats(spng_ctx *ctx, uint64_t *summed, uint64_t *copied, uint64_t *headers);
 /* One zlib stream to cut into IDAT chunks of chunk_bytes payload bytes (the last one shorter). */
 typedef struct spng_chunking_desc {
     const void *d_stream; uint64_t len;

@@ -71,6 +71,7 @@ EXPORTS = [
     "spng_inflate", "spng_unfilter", "spng_decode", "spng_adler32", "spng_filter_batch", "spng_filter",
     "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_luminance_batch", "spng_luminance", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_census_wide_batch", "spng_census_wide", "spng_map_batch", "spng_map", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
+    "spng_lex_state_bytes", "spng_lex_resume_batch", "spng_lex_resume_stats",
 ]
 
 
@@ -284,6 +285,9 @@ def load_library():
     lib.spng_adler32.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
     lib.spng_filter.argtypes = [vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, rp]
     lib.spng_lex_batch.argtypes = [vp, ctypes.POINTER(FileDesc), u32, vp, ctypes.POINTER(Lexed)]
+    lib.spng_lex_state_bytes.restype = u64
+    lib.spng_lex_resume_batch.argtypes = [vp, ctypes.POINTER(FileDesc), ctypes.POINTER(vp), u32, vp, ctypes.POINTER(Lexed)]
+    lib.spng_lex_resume_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.spng_write_idat_batch.argtypes = [vp, ctypes.POINTER(ChunkingDesc), u32, vp, rp]
     lib.spng_crc32.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
     lib.spng_unpack_batch.argtypes = [vp, vp, u32]
@@ -672,6 +676,35 @@ class Session:
         infos = (Lexed * n)()
         _check(self.lib, self.lib.spng_lex_batch(self.ctx, descs, n, None, infos))
         return list(infos), [bytes(b[:r.idat_len].cpu().numpy()) for b, r in zip(d_idat, infos)]
+
+    def lex_states(self, count=1):
+        """`count` states for lex_resume_batch: spng_lex_state_bytes() zero bytes of device memory each, one per file, kept by the
+        caller between the pushes of that file"""
+        t = self.torch
+        return [t.zeros(int(self.lib.spng_lex_state_bytes()), dtype=t.uint8, device=self.tdev) for _ in range(count)]
+
+    def lex_resume_batch(self, files, states):
+        """One push of files that arrive in pieces (spng_lex_resume_batch).  files: per file (d_png, length, d_idat) -- device tensors
+        with ALL bytes of the file so far (`length` of them) and the IDAT payloads so far (its size is idat_cap); states: per file
+        a tensor of lex_states(), or None (that file answers SPNG_E_ARGUMENT).  -> list[Lexed]: what lex_batch reports for the
+        same prefixes as whole files; d_idat[:idat_len] holds the verified payloads."""
+        n = len(files)
+        if n == 0:
+            _check(self.lib, self.lib.spng_lex_resume_batch(self.ctx, None, None, 0, None, None))
+            return []
+        descs = (FileDesc * n)()
+        for i, (png, length, idat) in enumerate(files):
+            descs[i] = FileDesc(self._ptr(png), int(length), self._ptr(idat), idat.numel() if idat is not None else 0)
+        sp = (ctypes.c_void_p * n)(*[s.data_ptr() if s is not None else None for s in states])
+        infos = (Lexed * n)()
+        _check(self.lib, self.lib.spng_lex_resume_batch(self.ctx, descs, sp, n, None, infos))
+        return list(infos)
+
+    def lex_resume_stats(self):
+        """(bytes summed by the CRC, IDAT bytes copied, chunk headers walked) of the most recent lex_resume_batch, over its files"""
+        a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(self.lib, self.lib.spng_lex_resume_stats(self.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
 
     def write_idat(self, stream: bytes, chunk_bytes: int) -> bytes:
         """The IDAT chunks (length, type, data, CRC-32 each) of a zlib stream cut every chunk_bytes bytes."""

@@ -135,6 +135,7 @@ void spng_destroy(spng_ctx *c)
     for (auto &sl : c->slabs) { if (sl.h) (void)hipHostFree(sl.h); if (sl.ev) (void)hipEventDestroy(sl.ev); }
     for (auto b : c->batch_buffers()) if (*b.p) (void)hipFree(*b.p);
     if (c->h_pool_used) (void)hipHostFree(c->h_pool_used);
+    if (c->h_lex_stats) (void)hipHostFree(c->h_lex_stats);
     if (c->pool_ev) (void)hipEventDestroy(c->pool_ev);
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
     if (c->stream_out) { (void)hipStreamSynchronize(c->stream_out); (void)hipStreamDestroy(c->stream_out); }

@@ -19,6 +19,7 @@
 // bad type in chunk 5).  A file with more chunks than its list holds is walked on by its own wave the serial way.
 #include "common.hpp"
 #include "crc32.hpp"
+#include "geometry.hpp"
 
 namespace spng {
 
@@ -192,6 +193,292 @@ __global__ void lex_finish_kernel(spng_lexed *__restrict__ out, const LexChunk *
     out[i] = r;
 }
 
+// ---- files that arrive in pieces (spng_lex_resume_batch) --------------------------------------------------------------------
+// The reference's OnlineDecoding tutorial (Snippets/PNG/OnlineDecoding.swift) retries signature() and chunk() on truncatedSignature /
+// truncatedChunkHeader / truncatedChunkBody until the bytes are there.  Here the loop's state lives on the device between the pushes:
+// the chunk in progress, what of it has been summed and copied, the running CRC.  The same three kernels as above, started at the
+// state's chunk: `lexr_walk_kernel` lists what is NEW with this push -- the chunks that became complete, and of the chunk the input
+// ends in the bytes that arrived --, in pieces of LEX_PIECE_BYTES (geometry.hpp); `lexr_piece_kernel` sums and copies a piece per wave,
+// the first piece of a chunk from the state's running CRC; `lexr_finish_kernel` folds the pieces of a chunk (crc(A || B) = crc(A) *
+// x^(8 |B|) + crc(B), the algebra of crc_partial_kernel / crc32_fold), lets the first failure in file order decide and writes the
+// state back.  After every push the answer is what the whole-file kernels above give for the same prefix.
+static constexpr uint32_t LEX_MAGIC = 0x5258454cu, LEX_NONE = 0xffffffffu;
+// between two pushes of a file; zero-filled in front of the first one
+struct LexState {
+    uint32_t magic, started;                    // LEX_MAGIC once a push has been seen; the signature has been checked
+    uint64_t off;                               // the header of the chunk in progress
+    uint64_t idat_len;                          // IDAT bytes whose chunks' checksums have been verified
+    uint64_t summed, copied;                    // of the chunk in progress: bytes of type + data that are in `crc`, payload bytes copied
+    uint32_t crc, chunks;                       // ... the CRC-32 over them (a finished value, as wave_crc32 takes it); chunks lexed in full
+    uint32_t ihdr_at, plte_at, trns_at, cgbi_at;    // the chunk that set the fields of `last` (LEX_NONE: none has)
+    uint32_t final, pad;                        // `last` is the result for good: SPNG_DONE or an error
+    spng_lexed last;                            // the previous answer: IHDR fields, PLTE / tRNS places
+};
+// a listed piece: bytes [lo, hi) of a chunk's type + data to sum, bytes [clo, chi) of its payload to copy
+struct LexPiece {
+    uint64_t off, idat_off, lo, hi, clo, chi;
+    uint32_t length, declared, computed, crc_in;    // computed: the first piece's from crc_in on, a raw (zero-initialised, un-finalised) one of the others
+    uint32_t chunk, pieces, complete, next_multi;   // pieces: in a chunk's first piece, how many it has (0 in the others); next_multi: the next chunk of several
+};
+struct LexRWalk {
+    uint32_t listed, stop_index; int32_t stop_status; uint32_t skip;        // skip: the walk's result stands as it is, the state too
+    uint32_t started, pad;                      // the signature has been seen
+    uint64_t stop_aux, stop_off, stop_idat;
+    uint32_t bad, first_multi, ihdr_at, plte_at, trns_at, cgbi_at;
+    uint32_t tail, tail_crc;                    // the chunk in progress: its first piece in the list (LEX_NONE: tail_crc is its CRC so far)
+    uint64_t tail_summed, tail_copied;
+    uint64_t n_summed, n_copied, n_headers;     // this push: bytes through the CRC, IDAT bytes copied, headers walked (spng_lex_resume_stats)
+};
+
+__global__ __launch_bounds__(64) void lexr_walk_kernel(const spng_file_desc *__restrict__ files, void *const *__restrict__ states,
+                                                       spng_lexed *__restrict__ out, LexPiece *__restrict__ table,
+                                                       const uint64_t *__restrict__ table_at, LexRWalk *__restrict__ walks)
+{
+    __shared__ uint32_t tab[CRC_TAB];
+    const int lane = threadIdx.x;
+    const spng_file_desc f = files[blockIdx.x];
+    const gbyte *p = (const gbyte *)uni64((uint64_t)f.d_png);
+    const uint64_t n = uni64(f.len);
+    gbyte *idat = (gbyte *)uni64((uint64_t)f.d_idat);
+    const uint64_t cap = uni64(f.idat_cap);
+    LexPiece *list = table + uni64(table_at[blockIdx.x]);
+    const uint32_t list_cap = (uint32_t)(uni64(table_at[blockIdx.x + 1]) - uni64(table_at[blockIdx.x]));
+    const LexState *sp = (const LexState *)uni64((uint64_t)states[blockIdx.x]);
+    spng_lexed r;
+    memset(&r, 0, sizeof r);
+    LexRWalk w;
+    memset(&w, 0, sizeof w);
+    w.stop_status = SPNG_DONE; w.bad = w.first_multi = w.tail = LEX_NONE;
+    w.ihdr_at = w.plte_at = w.trns_at = w.cgbi_at = LEX_NONE;
+    uint64_t off = 8, idat_len = 0, sum_from = 0, copy_from = 0;
+    uint32_t index = 0, crc_in = 0;
+    bool started = false, refuse = sp == nullptr;
+    // the state: what the previous pushes left.  The host never looks into it, so what is wrong with it is this file's result
+    if (!refuse && UNI(sp->magic) != 0) {
+        const LexState s = *sp;
+        const bool is_final = UNI(s.final) != 0;
+        refuse = UNI(s.magic) != LEX_MAGIC || UNI(s.final) > 1 || UNI(s.started) > 1;
+        started = UNI(s.started) != 0; off = uni64(s.off); idat_len = uni64(s.idat_len); sum_from = uni64(s.summed); copy_from = uni64(s.copied);
+        crc_in = UNI(s.crc); index = UNI(s.chunks);
+        if (!refuse && is_final && (s.last.status != SPNG_DONE || n >= off)) {
+            // terminal and sticky: the answer again, nothing read (behind IEND: further bytes are ignored)
+            w.skip = 1;
+            if (lane == 0) { out[blockIdx.x] = s.last; walks[blockIdx.x] = w; }
+            return;
+        }
+        // fields that contradict each other, or fewer bytes than the state has consumed
+        refuse = refuse || is_final || (started ? off < 8 : (off | idat_len | sum_from | index) != 0);
+        refuse = refuse || off > n || sum_from > n || idat_len > cap;      // (nothing below may wrap, nothing may be copied behind the buffer)
+        refuse = refuse || (sum_from ? sum_from < 4 || copy_from + 4 > sum_from : (copy_from | crc_in) != 0);
+        refuse = refuse || (s.ihdr_at != LEX_NONE && s.ihdr_at >= index) || (s.plte_at != LEX_NONE && s.plte_at >= index);
+        refuse = refuse || (s.trns_at != LEX_NONE && s.trns_at >= index) || (s.cgbi_at != LEX_NONE && s.cgbi_at >= index);
+        refuse = refuse || n < (started ? off + (sum_from ? 4 + sum_from : 0) : 0);
+        if (!started) off = 8;
+        r = s.last; r.status = 0; r.chunks = 0; r.aux[0] = r.aux[1] = 0; r.idat_len = r.consumed = 0;
+        w.ihdr_at = s.ihdr_at; w.plte_at = s.plte_at; w.trns_at = s.trns_at; w.cgbi_at = s.cgbi_at;
+    }
+    // (the chunk in progress: its header is read again, and has to allow what the state says of it)
+    if (!refuse && sum_from && (uint64_t)be32(p + off) + 4 < sum_from) refuse = true;
+    if (UB(refuse)) {
+        memset(&r, 0, sizeof r);
+        r.status = SPNG_E_ARGUMENT; w.skip = 1;
+        if (lane == 0) { out[blockIdx.x] = r; walks[blockIdx.x] = w; }
+        return;
+    }
+    bool tabled = false;
+    uint32_t listed = 0, last_multi = LEX_NONE;
+    uint64_t n_summed = 0, n_copied = 0, n_headers = 0;
+    // signature() (:44-56)
+    if (!started) {
+        if (n < 8) w.stop_status = SPNG_E_TRUNCATED_SIGNATURE;
+        else {
+            const uint64_t sig = (uint64_t)be32(p) << 32 | be32(p + 4);
+            if (sig != 0x89504e470d0a1a0aull) { w.stop_status = SPNG_E_SIGNATURE; w.stop_aux = sig; }
+            started = true;
+        }
+    }
+    while (w.stop_status == SPNG_DONE) {
+        // chunk() (:71-108), the checks of lex_walk_kernel in its order
+        if (off + 8 > n) { w.stop_status = SPNG_E_TRUNCATED_CHUNK_HEADER; break; }
+        n_headers += 1;
+        const uint32_t length = be32(p + off), name = be32(p + off + 4);
+        if (!valid_type(name)) { w.stop_status = SPNG_E_CHUNK_TYPE; w.stop_aux = name; break; }
+        const uint64_t bytes = (uint64_t)length + 4;
+        const bool complete = off + 8 + bytes <= n;
+        const uint64_t avail = n - off - 4 < bytes ? n - off - 4 : bytes;     // bytes of type + data that are there (at least the type)
+        const uint64_t fresh = avail - sum_from;
+        const gbyte *data = p + off + 8;
+        const bool copies = name == 0x49444154 && idat_len + length <= cap;
+        const uint64_t chi = copies ? avail - 4 : copy_from;
+        w.tail_crc = crc_in;
+        if (complete && name == 0x49444154 && !copies) {
+            // (the reference's order: the checksum first)
+            if (!tabled) { crc_table(tab, lane); tabled = true; }
+            const uint32_t declared = be32(data + length), computed = wave_crc32(tab, p + off + 4 + sum_from, fresh, crc_in, lane);
+            n_summed += fresh;
+            if (declared != computed) { w.stop_status = SPNG_E_CHUNK_CHECKSUM; w.stop_aux = (uint64_t)declared << 32 | computed; }
+            else w.stop_status = SPNG_E_OUTPUT_CAPACITY;
+            break;
+        }
+        const uint64_t q = lex_resume_pieces(fresh, complete);
+        if (q && listed + q <= list_cap) {
+            const uint32_t declared = complete ? be32(data + length) : 0;
+            for (uint64_t j = lane; j < q; j += 64) {
+                LexPiece c;
+                c.off = off; c.idat_off = idat_len;
+                c.lo = sum_from + j * LEX_PIECE_BYTES; c.hi = c.lo + LEX_PIECE_BYTES < avail ? c.lo + LEX_PIECE_BYTES : avail;
+                c.clo = j ? c.lo - 4 : copy_from; c.chi = copies ? c.hi - 4 : c.clo;
+                c.length = length; c.declared = declared; c.computed = 0; c.crc_in = crc_in;
+                c.chunk = index; c.pieces = j ? 0 : (uint32_t)q; c.complete = complete; c.next_multi = LEX_NONE;
+                list[listed + j] = c;
+            }
+            if (q > 1) {
+                if (last_multi == LEX_NONE) w.first_multi = listed;
+                else if (lane == 0) list[last_multi].next_multi = listed;
+                last_multi = listed;
+            }
+            if (!complete) w.tail = listed;
+            listed += (uint32_t)q;
+            n_summed += fresh; n_copied += chi - copy_from;
+        } else if (q) {
+            // the list is full: this wave sums and copies the chunk itself
+            if (!tabled) { crc_table(tab, lane); tabled = true; }
+            const uint32_t computed = wave_crc32(tab, p + off + 4 + sum_from, fresh, crc_in, lane);
+            n_summed += fresh;
+            if (complete) {
+                const uint32_t declared = be32(data + length);
+                if (declared != computed) { w.stop_status = SPNG_E_CHUNK_CHECKSUM; w.stop_aux = (uint64_t)declared << 32 | computed; break; }
+            }
+            copy_bytes(idat + idat_len + copy_from, data + copy_from, chi - copy_from, lane);
+            n_copied += chi - copy_from;
+            w.tail_crc = computed;
+        }
+        if (!complete) {
+            w.stop_status = SPNG_E_TRUNCATED_CHUNK_BODY; w.stop_aux = bytes;
+            w.tail_summed = avail; w.tail_copied = chi;
+            break;
+        }
+        if (name == 0x43674249) w.cgbi_at = w.cgbi_at == LEX_NONE ? index : w.cgbi_at;
+        else if (name == 0x49484452 && length >= 13) {
+            r.width = be32(data); r.height = be32(data + 4);
+            r.depth = data[8]; r.color = data[9]; r.compression = data[10]; r.filter = data[11]; r.interlace = data[12];
+            w.ihdr_at = index;
+        } else if (name == 0x504c5445) { r.plte_off = off + 8; r.plte_len = length; w.plte_at = index; }
+        else if (name == 0x74524e53) { r.trns_off = off + 8; r.trns_len = length; w.trns_at = index; }
+        else if (name == 0x49444154) idat_len += length;
+        index += 1;
+        off += 8 + bytes;
+        sum_from = copy_from = 0; crc_in = 0;
+        if (name == 0x49454e44) break;                         // IEND
+    }
+    w.listed = listed; w.started = started;
+    w.stop_index = index; w.stop_off = off; w.stop_idat = idat_len;
+    w.n_summed = n_summed; w.n_copied = n_copied; w.n_headers = n_headers;
+    if (lane == 0) { out[blockIdx.x] = r; walks[blockIdx.x] = w; }
+}
+
+__global__ __launch_bounds__(64) void lexr_piece_kernel(const spng_file_desc *__restrict__ files, LexPiece *__restrict__ table,
+                                                        const uint64_t *__restrict__ table_at, LexRWalk *__restrict__ walks)
+{
+    __shared__ uint32_t tab[CRC_TAB];
+    const int lane = threadIdx.x;
+    const uint32_t file = blockIdx.y;
+    const uint32_t listed = UNI(walks[file].listed);
+    if (blockIdx.x >= listed || UNI(walks[file].skip)) return;
+    const spng_file_desc f = files[file];
+    const gbyte *p = (const gbyte *)uni64((uint64_t)f.d_png);
+    gbyte *idat = (gbyte *)uni64((uint64_t)f.d_idat);
+    LexPiece *list = table + uni64(table_at[file]);
+    crc_table(tab, lane);
+    for (uint32_t k = blockIdx.x; k < listed; k += gridDim.x) {
+        const uint64_t off = uni64(list[k].off), lo = uni64(list[k].lo), hi = uni64(list[k].hi);
+        const uint64_t clo = uni64(list[k].clo), chi = uni64(list[k].chi);
+        const uint32_t pieces = UNI(list[k].pieces);
+        uint32_t computed;
+        if (pieces) computed = wave_crc32(tab, p + off + 4 + lo, hi - lo, UNI(list[k].crc_in), lane);
+        else {
+            // (as crc_partial_kernel: the standard CRC of the piece with its conditioning undone)
+            const uint32_t std_crc = wave_crc32(tab, p + off + 4 + lo, hi - lo, 0, lane);
+            computed = std_crc ^ 0xffffffffu ^ multmodp(xpow8(hi - lo), 0xffffffffu);
+        }
+        // (the payload is copied ahead of the chunk's checksum: idat_len moves on only once that has been verified)
+        if (chi > clo) copy_bytes(idat + uni64(list[k].idat_off) + clo, p + off + 8 + clo, chi - clo, lane);
+        const uint32_t declared = UNI(list[k].declared);
+        const bool decides = pieces == 1 && UNI(list[k].complete) != 0;     // (chunks of several pieces: the finish folds and compares)
+        if (lane == 0) {
+            list[k].computed = computed;
+            if (decides && computed != declared) atomicMin(&walks[file].bad, k);
+        }
+    }
+}
+
+__global__ void lexr_finish_kernel(spng_lexed *__restrict__ out, LexPiece *__restrict__ table, const uint64_t *__restrict__ table_at,
+                                   const LexRWalk *__restrict__ walks, const spng_file_desc *__restrict__ files, void *const *__restrict__ states,
+                                   unsigned long long *__restrict__ stats, uint32_t count)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    // the call's counters: a wave adds up its files', an atomic per wave (one per file on one address: a call over 8192 small files
+    // 0.43 ms instead of 0.20).  Every lane of the wave arrives here
+    unsigned long long sums[3] = {0, 0, 0};
+    if (i < count) { sums[0] = walks[i].n_summed; sums[1] = walks[i].n_copied; sums[2] = walks[i].n_headers; }
+    for (int k = 0; k < 3; ++k) {
+        if (__ballot(sums[k] != 0) == 0) continue;
+        unsigned long long total = sums[k];
+#pragma unroll
+        for (int m = 32; m; m >>= 1) {
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)total, m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(total >> 32), m);
+            total += (unsigned long long)hi << 32 | lo;
+        }
+        if ((threadIdx.x & 63) == 0) atomicAdd(stats + k, total);
+    }
+    if (i >= count) return;
+    const LexRWalk w = walks[i];
+    if (w.skip) return;
+    LexPiece *list = table + table_at[i];
+    // the chunks of several pieces: folded, and compared if they are complete
+    uint32_t bad = w.bad;
+    for (uint32_t e = w.first_multi; e != LEX_NONE; e = list[e].next_multi) {
+        uint32_t c = list[e].computed ^ 0xffffffffu;
+        for (uint32_t j = 1; j < list[e].pieces; ++j) c = multmodp(xpow8(list[e + j].hi - list[e + j].lo), c) ^ list[e + j].computed;
+        list[e].computed = c ^ 0xffffffffu;
+        if (list[e].complete && list[e].computed != list[e].declared && e < bad) bad = e;
+    }
+    spng_lexed r = out[i];
+    uint32_t upto = w.stop_index;                              // chunks lexed in full
+    r.status = w.stop_status;
+    if (w.stop_status == SPNG_E_CHUNK_CHECKSUM) { r.aux[0] = w.stop_aux >> 32; r.aux[1] = (uint32_t)w.stop_aux; }
+    else r.aux[0] = w.stop_aux;
+    r.consumed = w.stop_off; r.idat_len = w.stop_idat;
+    if (bad != LEX_NONE) {
+        // a checksum failed in front of whatever stopped the walk
+        const LexPiece c = list[bad];
+        upto = c.chunk;
+        r.status = SPNG_E_CHUNK_CHECKSUM; r.aux[0] = c.declared; r.aux[1] = c.computed;
+        r.consumed = c.off; r.idat_len = c.idat_off;
+    }
+    r.chunks = upto;
+    // what lies behind the first failure was never seen by the reference's loop
+    if (w.ihdr_at >= upto) { r.width = r.height = 0; r.depth = r.color = r.compression = r.filter = r.interlace = 0; }
+    if (w.plte_at >= upto) { r.plte_off = 0; r.plte_len = 0; }
+    if (w.trns_at >= upto) { r.trns_off = 0; r.trns_len = 0; }
+    r.ios = w.cgbi_at != LEX_NONE && w.cgbi_at < upto ? 1 : 0;
+    if (r.consumed > files[i].len) r.consumed = files[i].len;
+    out[i] = r;
+    // the state: the three truncations wait for more; everything else is final, written once
+    LexState s;
+    memset(&s, 0, sizeof s);
+    const bool waits = r.status == SPNG_E_TRUNCATED_SIGNATURE || r.status == SPNG_E_TRUNCATED_CHUNK_HEADER || r.status == SPNG_E_TRUNCATED_CHUNK_BODY;
+    s.magic = LEX_MAGIC; s.started = w.started; s.final = waits ? 0 : 1;
+    s.off = s.started ? w.stop_off : 0; s.idat_len = w.stop_idat; s.chunks = w.stop_index;
+    if (r.status == SPNG_E_TRUNCATED_CHUNK_BODY) {
+        s.summed = w.tail_summed; s.copied = w.tail_copied;
+        s.crc = w.tail != LEX_NONE ? list[w.tail].computed : w.tail_crc;
+    }
+    s.ihdr_at = w.ihdr_at; s.plte_at = w.plte_at; s.trns_at = w.trns_at; s.cgbi_at = w.cgbi_at;
+    s.last = r;
+    *(LexState *)states[i] = s;
+}
+
 // PNG.BytestreamDestination.format(type: .IDAT, data:) for every piece of a stream (:66-88)
 __global__ __launch_bounds__(64) void write_idat_kernel(const spng_chunking_desc *__restrict__ descs, spng_result *__restrict__ results)
 {
@@ -264,6 +551,27 @@ hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed 
     });
     if (e != hipSuccess) return e;
     lex_finish_kernel<<<(count + 63) / 64, 64, 0, stream>>>(d_out, (const LexChunk *)d_table, d_table_at, (const LexWalk *)d_walks, d_files, count);
+    return hipGetLastError();
+}
+size_t lex_state_bytes() { return sizeof(LexState); }
+size_t lex_piece_bytes() { return sizeof(LexPiece); }
+size_t lex_rwalk_bytes() { return sizeof(LexRWalk); }
+hipError_t launch_lex_resume(const spng_file_desc *d_files, void *const *d_states, uint32_t count, spng_lexed *d_out, void *d_table,
+                             const uint64_t *d_table_at, void *d_walks, uint32_t max_listed, uint64_t *d_stats, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    lexr_walk_kernel<<<count, 64, 0, stream>>>(d_files, d_states, d_out, (LexPiece *)d_table, d_table_at, (LexRWalk *)d_walks);
+    // (the grid of launch_lex: a wave strides over its file's pieces)
+    uint32_t bx = max_listed < 1 ? 1 : max_listed;
+    uint32_t want = (8192 + count - 1) / count;
+    if (want < 4) want = 4;
+    if (bx > want) bx = want;
+    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        lexr_piece_kernel<<<dim3(bx, ny), 64, 0, stream>>>(d_files + y0, (LexPiece *)d_table, d_table_at + y0, (LexRWalk *)d_walks + y0);
+    });
+    if (e != hipSuccess) return e;
+    lexr_finish_kernel<<<(count + 63) / 64, 64, 0, stream>>>(d_out, (LexPiece *)d_table, d_table_at, (const LexRWalk *)d_walks, d_files, d_states,
+                                                                 (unsigned long long *)d_stats, count);
     return hipGetLastError();
 }
 hipError_t launch_write_idat(const spng_chunking_desc *d_descs, uint32_t count, uint32_t blocks_x, spng_result *d_results, hipStream_t stream)

@@ -460,6 +460,11 @@ size_t lex_chunk_bytes();
 size_t lex_walk_bytes();
 hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed *d_out, void *d_table, const uint64_t *d_table_at,
                       void *d_walks, uint32_t max_listed, hipStream_t stream);
+size_t lex_state_bytes();
+size_t lex_piece_bytes();
+size_t lex_rwalk_bytes();
+hipError_t launch_lex_resume(const spng_file_desc *d_files, void *const *d_states, uint32_t count, spng_lexed *d_out, void *d_table,
+                             const uint64_t *d_table_at, void *d_walks, uint32_t max_listed, uint64_t *d_stats, hipStream_t stream);
 hipError_t launch_write_idat(const spng_chunking_desc *d_descs, uint32_t count, uint32_t blocks_x, spng_result *d_results, hipStream_t stream);
 hipError_t launch_crc_partial(const uint8_t *d, uint64_t n, uint64_t piece, uint32_t *d_partial, uint32_t pieces, hipStream_t stream);
 uint32_t crc32_fold(const uint32_t *partial, uint64_t pieces, uint64_t n, uint64_t piece);

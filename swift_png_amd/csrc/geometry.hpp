@@ -127,6 +127,19 @@ inline uint32_t write_idat_blocks_x(uint64_t most_pieces) { return (uint32_t)std
 // list of len / 2048 + 64 entries (at most 8192) is plenty, and a file with more is finished by its own wave
 inline uint64_t lex_listed(uint64_t len) { return std::min<uint64_t>(std::min(len / 2048 + 64, len / 12 + 1), 8192); }
 
+// lexr_piece_kernel (files that arrive in pieces): the bytes of a chunk's type + data that are new with a push are summed in pieces of
+// LEX_PIECE_BYTES, a wave each -- a file that is one huge IDAT pushed in large parts must not wait for one wave.  A chunk that became
+// complete takes a piece even when nothing of it is left to sum (only its checksum field arrived): somebody has to compare.
+constexpr uint64_t LEX_PIECE_BYTES = 1u << 20;
+constexpr uint64_t lex_resume_pieces(uint64_t new_bytes, bool complete)
+{
+    return new_bytes ? (new_bytes + LEX_PIECE_BYTES - 1) / LEX_PIECE_BYTES : complete ? 1 : 0;
+}
+// its list for a file of which `len` bytes have arrived: an entry per piece.  The host does not look into the device-side state, so
+// the list is sized as if every byte were new: the chunks lex_listed allows and a piece more per LEX_PIECE_BYTES.  Chunks whose
+// pieces do not fit are summed by the walking wave itself.
+inline uint64_t lex_resume_listed(uint64_t len) { return lex_listed(len) + len / LEX_PIECE_BYTES; }
+
 // ---- inflate: segment length -------------------------------------------------------------------------------------
 // configured: SPNG_CFG_SEGMENT_BYTES, or (0) by the batch's compressed bytes `total` and the compressed bytes per DEFLATE block
 // the last batch showed (block_bytes; 0: not known).

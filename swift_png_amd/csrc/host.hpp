@@ -73,6 +73,7 @@ struct spng_ctx {
     uint64_t pool_pages_planned = 0, pool_src_bytes = 0, pool_src_pending = 0;   // (source bytes of the batch planned / of the one whose counters are on their way)
     double   block_bytes = 0;        // compressed bytes per DEFLATE block in the last batch (0: not known)
     hipEvent_t pool_ev = nullptr; bool pool_pending = false;
+    uint64_t *h_lex_stats = nullptr;                 // pinned: {bytes summed, IDAT bytes copied, headers walked} of the last spng_lex_resume_batch
     hipEvent_t ev_dfl[4] = {nullptr, nullptr, nullptr, nullptr};    // level >= 8 rounds: searched[parity], parsed[parity]
     // second stream (second_stream()): the parts of a stream's resolve beside its first, a deflate round's search beside the parse
     hipStream_t stream2 = nullptr;

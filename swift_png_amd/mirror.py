@@ -441,7 +441,6 @@ class PNG:
             device (SPNG_IMAGE_OVERDRAW).  The inflate goes on where the previous chunk stopped
             (spng_inflate_resume_batch); the scanlines that became complete with this chunk -- and only those -- are defiltered
             and assigned (spng_unfilter_resume_batch, PNG.Decoder.swift:88-94, 121-135)."""
-            from . import raise_for, E_EXTRANEOUS_IMAGE_DATA
             if not self._continue:
                 raise DecodingError(E_EXTRANEOUS_COMPRESSED_DATA)     # PNG.Decoder.swift:51-55
             s = self._s
@@ -453,7 +452,17 @@ class PNG:
                 self._d_idat = grown
             if data:
                 self._d_idat[self._n_idat:need] = s.to_device(bytes(data))
-            self._n_idat = need
+            self.push_device(self._d_idat, need, overdraw)
+
+        def push_device(self, d_idat, length: int, overdraw: bool = False):
+            """push(data:overdraw:) for IDAT bytes that are on the device already: d_idat holds ALL IDAT bytes so far, `length` of
+            them -- the buffer spng_lex_resume_batch fills, at its idat_len (PNG.decode_online); what lies behind the previous
+            push's length is the data of this one."""
+            from . import raise_for, E_EXTRANEOUS_IMAGE_DATA
+            if not self._continue:
+                raise DecodingError(E_EXTRANEOUS_COMPRESSED_DATA)     # PNG.Decoder.swift:51-55
+            s = self._s
+            self._d_idat, self._n_idat = d_idat, int(length)
             res, state = s.inflate_resume(self._d_idat, self._n_idat, self._d_rows, self.standard, self._state)
             status = res.status
             # PNG.Decoder.swift:142-147: anything left in the inflator after the last row
@@ -478,3 +487,65 @@ class PNG:
             """push(ancillary: IEND) (:137-142)."""
             if self._continue:
                 raise DecodingError(E_INCOMPLETE_DATASTREAM)
+
+    @staticmethod
+    def decode_online(pieces, overdraw=False, capture=None, session=None):
+        """decodeOnline of the reference's tutorial (Snippets/PNG/OnlineDecoding.swift:102-216) from the bytes of a file as they arrive:
+        every piece of `pieces` is appended to a device buffer and lexed there (spng_lex_resume_batch: waitSignature / waitChunk --
+        the truncation statuses are the tutorial's "try again"; every byte is summed and copied once whatever the pieces are); the
+        context is made once IHDR and the first IDAT are in; the IDAT bytes whose chunks' checksums have been verified go to
+        PNG.Context.push on the device, chunk by chunk; capture(context) is called after every IDAT chunk, as the tutorial writes
+        its snapshots, however many of them a piece completes; at IEND, push(ancillary:).  Lexing errors are raised once
+        they are final, and for a file that ends early.  -> (context, the last Lexed, PLTE bytes, tRNS bytes); the palette and the
+        transparency are read by the host at the offsets reported, as for whole files."""
+        from . import (DONE, E_TRUNCATED_CHUNK_BODY, E_TRUNCATED_CHUNK_HEADER, E_TRUNCATED_SIGNATURE, FORMAT_IOS, FORMAT_ZLIB, LexingError,
+                       load, raise_for)
+        s = session or load()
+        waits = (E_TRUNCATED_SIGNATURE, E_TRUNCATED_CHUNK_HEADER, E_TRUNCATED_CHUNK_BODY)
+        (state,) = s.lex_states(1)
+        d_png, d_idat, n_png, pushed = s.empty(1 << 16), s.empty(1 << 16), 0, 0
+        context, info, head = None, None, bytearray()
+        for piece in pieces:
+            piece = bytes(piece)
+            if not piece:
+                continue
+            need = n_png + len(piece)
+            if d_png.numel() < need:
+                # (both buffers whole: the payload of the chunk in progress is copied ahead of idat_len)
+                grown, grown_idat = s.empty(2 * need), s.empty(2 * need)
+                grown[:n_png] = d_png[:n_png]
+                grown_idat[:d_idat.numel()] = d_idat
+                d_png, d_idat = grown, grown_idat
+            d_png[n_png:need] = s.to_device(piece)
+            n_png = need
+            if context is None:
+                head += piece                            # (what the host reads PLTE / tRNS from: they stand in front of the first IDAT)
+            # waitChunk: a chunk at a time, as the tutorial lexes -- the lexer is asked for the bytes up to the end of the chunk in
+            # progress (its place and length are in the last answer), so that a piece that completes several IDAT chunks still shows
+            # the image after each of them.  Every byte is summed and copied once all the same: the state goes on where it stopped.
+            while True:
+                upto = n_png
+                if info is not None and info.status == E_TRUNCATED_CHUNK_BODY:
+                    upto = min(n_png, info.consumed + 8 + info.aux[0])
+                elif info is not None and info.status == E_TRUNCATED_CHUNK_HEADER:
+                    upto = min(n_png, info.consumed + 8)
+                (info,) = s.lex_resume_batch([(d_png, upto, d_idat)], [state])
+                if info.status != DONE and info.status not in waits:
+                    raise_for(info.status, (info.aux[0], info.aux[1]))
+                if context is None and (info.idat_len or info.status == DONE):
+                    channels = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[info.color]
+                    context = PNG.Context((info.width, info.height), info.depth, channels, bool(info.interlace),
+                                          FORMAT_IOS if info.ios else FORMAT_ZLIB, session=s)
+                if info.idat_len > pushed:
+                    context.push_device(d_idat, info.idat_len, overdraw)
+                    pushed = info.idat_len
+                    if capture is not None:
+                        capture(context)
+                if info.status == DONE:
+                    context.push_ancillary_iend()
+                    plte = bytes(head[info.plte_off:info.plte_off + info.plte_len])
+                    trns = bytes(head[info.trns_off:info.trns_off + info.trns_len])
+                    return context, info, plte, trns
+                if upto == n_png:
+                    break
+        raise LexingError(info.status if info is not None else E_TRUNCATED_SIGNATURE, (info.aux[0], 0) if info is not None else (0, 0))

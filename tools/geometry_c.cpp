@@ -21,6 +21,8 @@ uint32_t geo_blocks_for(uint64_t most, uint32_t per_block) { return blocks_for(m
 uint32_t geo_census_blocks_x(uint32_t count, uint64_t most) { return census_blocks_x(count, most); }
 uint32_t geo_write_idat_blocks_x(uint64_t most_pieces) { return write_idat_blocks_x(most_pieces); }
 uint64_t geo_lex_listed(uint64_t len) { return lex_listed(len); }
+uint64_t geo_lex_resume_pieces(uint64_t new_bytes, int32_t complete) { return lex_resume_pieces(new_bytes, complete != 0); }
+uint64_t geo_lex_resume_listed(uint64_t len) { return lex_resume_listed(len); }
 uint64_t geo_inflate_segment_bytes(uint64_t configured, uint64_t total, double block_bytes) { return inflate_segment_bytes(configured, total, block_bytes); }
 void geo_search_chunks(uint64_t streams, uint32_t out[2])
 {
@@ -35,7 +37,7 @@ int64_t geo_constant(const char *name)
     C(PIECE_SCALE_ROWS); C(PIECE_FLOOR); C(WIDE_ROW); C(WIDE_SCALE_ROWS); C(WIDE_FLOOR); C(WIDE_CEIL);
     C(PK_BAND_BYTES); C(PK_SCALE_ROWS); C(PK_FILL_ROWS); C(PK_FLOOR_BANDS); C(PK_FEW_HEIGHT); C(PK_FEW_ROWS); C(PK_FEW_MIN); C(PK_FEW_MAX);
     C(FILTER_ROWS_PER_BLOCK); C(FILTER_BLOCKS_MAX); C(SCATTER_BLOCKS_MAX); C(OVERDRAW_BLOCKS_MAX); C(SMALL_BLOCK_BYTES);
-    C(SEARCH_ROUND_POSITIONS);
+    C(SEARCH_ROUND_POSITIONS); C(LEX_PIECE_BYTES);
     C(PieceRule::configured); C(PieceRule::scaled); C(PieceRule::floor128); C(PieceRule::wide); C(PieceRule::rr); C(PieceRule::floor4);
     C(PieceRule::few);
 #undef C

@@ -54,12 +54,12 @@ __device__ __forceinline__ void copy_bytes(gbyte *dst, const gbyte *src, uint64_
     for (uint64_t i = units * 16 + lane; i < n; i += 64) dst[i] = src[i];
 }
 
-// CRC-32 over a chunk's type code and data (BytestreamSource.chunk, :95-103); idat_to: where the payload goes (IDAT chunks), or null
-__device__ __forceinline__ uint32_t chunk_crc32(const uint32_t *tab, const gbyte *type_and_data, uint32_t length, int lane, gbyte *idat_to)
+// CRC-32 over a chunk's type code and data (BytestreamSource.chunk, :95-103; BytestreamDestination.format, :75-83)
+__device__ __forceinline__ uint32_t chunk_crc32(const uint32_t *tab, uint32_t name, const gbyte *data, uint64_t length, int lane)
 {
     uint32_t c = 0xffffffffu;
-    for (int b = 0; b < 4; ++b) c = tab[(c ^ UNI(type_and_data[b])) & 0xff] ^ (c >> 8);
-    return wave_crc32(tab, type_and_data + 4, length, c ^ 0xffffffffu, lane, idat_to);
+    for (int b = 0; b < 4; ++b) c = tab[(c ^ (name >> (8 * (3 - b)))) & 0xff] ^ (c >> 8);
+    return wave_crc32(tab, data, length, c ^ 0xffffffffu, lane);
 }
 
 __global__ __launch_bounds__(64) void lex_walk_kernel(const spng_file_desc *__restrict__ files, spng_lexed *__restrict__ out,
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(64) void lex_chunk_kernel(const spng_file_desc *__r
         // (the copy stays a pass of its own: consecutive lanes, consecutive 16-byte units.  Copied by the lanes that sum them -- a
         // piece per lane, 2^k bytes apart -- the payloads of 64 KiB chunks cost a line per lane and store: 256 4K files lexed in 10.0
         // instead of 6.9 ms)
-        const uint32_t computed = chunk_crc32(tab, p + off + 4, length, lane, nullptr);
+        const uint32_t computed = chunk_crc32(tab, name, p + off + 8, length, lane);
         if (declared != computed) {
             if (lane == 0) { list[k].computed = computed; atomicMin(&walks[file].bad_crc, k); }
         } else if (name == 0x49444154) copy_bytes(idat + uni64(list[k].idat_off), p + off + 8, length, lane);
@@ -397,9 +397,7 @@ __global__ __launch_bounds__(64) void lexr_piece_kernel(const spng_file_desc *__
         uint32_t computed;
         if (pieces) computed = wave_crc32(tab, p + off + 4 + lo, hi - lo, UNI(list[k].crc_in), lane);
         else {
-            // (as crc_partial_kernel: the standard CRC of the piece with its conditioning undone)
-            const uint32_t std_crc = wave_crc32(tab, p + off + 4 + lo, hi - lo, 0, lane);
-            computed = std_crc ^ 0xffffffffu ^ multmodp(xpow8(hi - lo), 0xffffffffu);
+            computed = crc32_conditioning(wave_crc32(tab, p + off + 4 + lo, hi - lo, 0, lane), hi - lo);       // (a raw one, as crc_partial_kernel's)
         }
         // (the payload is copied ahead of the chunk's checksum: idat_len moves on only once that has been verified)
         if (chi > clo) copy_bytes(idat + uni64(list[k].idat_off) + clo, p + off + 8 + clo, chi - clo, lane);
@@ -503,10 +501,7 @@ __global__ __launch_bounds__(64) void write_idat_kernel(const spng_chunking_desc
         if (lane < 4) o[lane] = (uint8_t)(len >> (8 * (3 - lane)));
         if (lane < 4) o[4 + lane] = (uint8_t)(0x49444154u >> (8 * (3 - lane)));
         for (uint64_t i = lane; i < len; i += 64) o[8 + i] = src[lo + i];
-        // CRC over the type code and the data
-        uint32_t crc = 0;
-        for (int b = 0; b < 4; ++b) crc = tab[((crc ^ 0xffffffffu) ^ (0x49444154u >> (8 * (3 - b)))) & 0xff] ^ ((crc ^ 0xffffffffu) >> 8) ^ 0xffffffffu;
-        crc = wave_crc32(tab, src + lo, len, crc, lane);
+        const uint32_t crc = chunk_crc32(tab, 0x49444154u, src + lo, len, lane);
         if (lane < 4) o[8 + len + lane] = (uint8_t)(crc >> (8 * (3 - lane)));
     }
 }
@@ -518,9 +513,8 @@ __global__ __launch_bounds__(64) void crc_partial_kernel(const uint8_t *__restri
     const int lane = threadIdx.x;
     crc_table(tab, lane);
     const uint64_t lo = (uint64_t)blockIdx.x * piece, len = n - lo < piece ? n - lo : piece;
-    // wave_crc32 with crc = 0 returns the standard CRC of the piece; undo its conditioning to get the raw one
     const uint32_t std_crc = wave_crc32(tab, (const gbyte *)data + lo, len, 0, lane);
-    if (lane == 0) partial[blockIdx.x] = std_crc ^ 0xffffffffu ^ multmodp(xpow8(len), 0xffffffffu);
+    if (lane == 0) partial[blockIdx.x] = crc32_conditioning(std_crc, len);
 }
 
 uint32_t crc32_fold(const uint32_t *partial, uint64_t pieces, uint64_t n, uint64_t piece)
@@ -530,7 +524,7 @@ uint32_t crc32_fold(const uint32_t *partial, uint64_t pieces, uint64_t n, uint64
         const uint64_t len = n - k * piece < piece ? n - k * piece : piece;
         c = multmodp(xpow8(len), c) ^ partial[k];
     }
-    return c ^ multmodp(xpow8(n), 0xffffffffu) ^ 0xffffffffu;
+    return crc32_conditioning(c, n);
 }
 
 size_t lex_chunk_bytes() { return sizeof(LexChunk); }
@@ -540,12 +534,7 @@ hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed 
 {
     if (!count) return hipSuccess;
     lex_walk_kernel<<<count, 64, 0, stream>>>(d_files, d_out, (LexChunk *)d_table, d_table_at, (LexWalk *)d_walks);
-    uint32_t bx = max_listed < 1 ? 1 : max_listed;
-    // (enough waves to fill the chip; a wave strides over its file's chunks -- four waves per file at least: a batch of small
-    // files is as slow as its file with the most chunks)
-    uint32_t want = (8192 + count - 1) / count;
-    if (want < 4) want = 4;
-    if (bx > want) bx = want < 1 ? 1 : want;
+    const uint32_t bx = lex_piece_blocks_x(count, max_listed);
     const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
         lex_chunk_kernel<<<dim3(bx, ny), 64, 0, stream>>>(d_files + y0, (LexChunk *)d_table, d_table_at + y0, (LexWalk *)d_walks + y0);
     });
@@ -561,11 +550,7 @@ hipError_t launch_lex_resume(const spng_file_desc *d_files, void *const *d_state
 {
     if (!count) return hipSuccess;
     lexr_walk_kernel<<<count, 64, 0, stream>>>(d_files, d_states, d_out, (LexPiece *)d_table, d_table_at, (LexRWalk *)d_walks);
-    // (the grid of launch_lex: a wave strides over its file's pieces)
-    uint32_t bx = max_listed < 1 ? 1 : max_listed;
-    uint32_t want = (8192 + count - 1) / count;
-    if (want < 4) want = 4;
-    if (bx > want) bx = want;
+    const uint32_t bx = lex_piece_blocks_x(count, max_listed);
     const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
         lexr_piece_kernel<<<dim3(bx, ny), 64, 0, stream>>>(d_files + y0, (LexPiece *)d_table, d_table_at + y0, (LexRWalk *)d_walks + y0);
     });

@@ -29,6 +29,11 @@ __host__ __device__ inline uint32_t xpow8(uint64_t n)
     return r;
 }
 
+// The standard CRC-32 of n bytes and their raw (zero-initialised, un-finalised) one differ by the conditioning -- the initial value
+// shifted past the bytes, and the final xor --, so one turns into the other by the same mask.  Raw values of pieces fold into that of
+// the whole: crc(A || B) = crc(A) * x^(8 |B|) + crc(B) (crc32_fold, lex_finish_kernel)
+__host__ __device__ inline uint32_t crc32_conditioning(uint32_t crc, uint64_t n) { return crc ^ 0xffffffffu ^ multmodp(xpow8(n), 0xffffffffu); }
+
 // Four 256-entry tables for slicing-by-4 (tab[0] is the plain byte table; tab[k][i] = the CRC register after byte i
 // and k zero bytes): four independent LDS lookups per input dword instead of four dependent ones.
 static constexpr int CRC_TAB = 4 * 256;
@@ -112,6 +117,5 @@ __device__ __forceinline__ uint32_t wave_crc32(const uint32_t *tab, const gbyte 
     }
     return UNI(c) ^ 0xffffffffu;
 }
-
 
 }  // namespace spng

@@ -139,6 +139,14 @@ constexpr uint64_t lex_resume_pieces(uint64_t new_bytes, bool complete)
 // the list is sized as if every byte were new: the chunks lex_listed allows and a piece more per LEX_PIECE_BYTES.  Chunks whose
 // pieces do not fit are summed by the walking wave itself.
 inline uint64_t lex_resume_listed(uint64_t len) { return lex_listed(len) + len / LEX_PIECE_BYTES; }
+// lex_chunk_kernel's and lexr_piece_kernel's workgroups along x (y: the files): enough waves to fill the chip; a wave strides over its
+// file's list -- four waves per file at least: a batch of small files is as slow as its file with the most chunks.  max_listed: the
+// longest list of the call
+inline uint32_t lex_piece_blocks_x(uint32_t count, uint32_t max_listed)
+{
+    const uint32_t want = std::max((8192 + count - 1) / count, 4u);
+    return std::min(std::max(max_listed, 1u), want);
+}
 
 // ---- inflate: segment length -------------------------------------------------------------------------------------
 // configured: SPNG_CFG_SEGMENT_BYTES, or (0) by the batch's compressed bytes `total` and the compressed bytes per DEFLATE block

@@ -35,6 +35,7 @@ def _load():
                             ("geo_census_blocks_x", _u32, (_u32, _u64)),
                             ("geo_write_idat_blocks_x", _u32, (_u64,)),
                             ("geo_lex_listed", _u64, (_u64,)),
+                            ("geo_lex_piece_blocks_x", _u32, (_u32, _u32)),
                             ("geo_inflate_segment_bytes", _u64, (_u64, _u64, ctypes.c_double)),
                             ("geo_search_chunks", None, (_u64, ctypes.POINTER(_u32))),
                             ("geo_constant", ctypes.c_int64, (ctypes.c_char_p,))):
@@ -85,4 +86,5 @@ blocks_for = _lib.geo_blocks_for
 census_blocks_x = _lib.geo_census_blocks_x
 write_idat_blocks_x = _lib.geo_write_idat_blocks_x
 lex_listed = _lib.geo_lex_listed
+lex_piece_blocks_x = _lib.geo_lex_piece_blocks_x
 inflate_segment_bytes = _lib.geo_inflate_segment_bytes

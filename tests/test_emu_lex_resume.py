@@ -1,8 +1,9 @@
-"""The resumable chunk lexer of csrc/chunks.hip (spng_lex_resume_batch: lexr_walk -> lexr_piece -> lexr_finish), as written, run on the CPU by
-the wave emulator of tools/emu over files that arrive push by push: tools/emu/emu_lex_resume.cpp.  The yardstick is the whole-file
-lexer of the same source on the same prefix -- after every push the result is the same byte for byte and the IDAT bytes in front of
-idat_len are the same (the driver's `same` column) --, the statuses are also stated here, and the counters hold "every byte once":
-over all pushes of a file each byte of type + data is summed once, each IDAT byte copied once, however the pushes cut the file.
+"""The chunk lexers of csrc/chunks.hip, as written, run on the CPU by the wave emulator of tools/emu: the resumable one
+(spng_lex_resume_batch: lexr_walk -> lexr_piece -> lexr_finish) over files that arrive push by push, and the whole-file one
+(spng_lex_batch: lex_walk -> lex_chunk -> lex_finish) over prefixes: tools/emu/emu_lex_resume.cpp.  The yardstick is tests/lex_ref.py, the reference's loop in plain Python, on the same prefix with the
+same idat_cap -- after every push every field of the result and the IDAT bytes in front of idat_len are its, and the padding is
+zero (the `same` column of a Row) --, the statuses are also stated here, and the counters hold "every byte once": over all pushes of a file each byte of type
++ data is summed once, each IDAT byte copied once, however the pushes cut the file.
 Twice: a plain build, and one with -fsanitize=address,undefined -- a CPU program of its own, run as a subprocess, nothing preloaded;
 every push hands the kernels a copy of exactly the prefix, so a read behind the bytes that have arrived is seen."""
 import struct
@@ -15,6 +16,7 @@ import pytest
 
 import emu_build
 import pnghelp as ph
+from lex_ref import lex_ref
 
 SANITIZE = ("-fsanitize=address,undefined", "-fno-sanitize=alignment", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g",
             "-DEMU_UCONTEXT")
@@ -24,8 +26,8 @@ ENV = {"ASAN_OPTIONS": "detect_stack_use_after_return=0:detect_leaks=0", "UBSAN_
 WAITS = (E_TRUNCATED_SIGNATURE, E_TRUNCATED_CHUNK_HEADER, E_TRUNCATED_CHUNK_BODY)
 SIG = b"\x89PNG\r\n\x1a\n"
 MAGIC = b"LEXR"                                             # the first word of a state somebody has written (csrc/chunks.hip: LEX_MAGIC)
-Row = namedtuple("Row", "status chunks aux0 aux1 width height depth color interlace ios idat_len plte_off plte_len trns_off trns_len consumed "
-                        "summed copied headers same")
+Row = namedtuple("Row", "status chunks aux0 aux1 width height depth color compression filter interlace ios idat_len plte_off plte_len trns_off "
+                        "trns_len consumed pad0 pad1 summed copied headers same")
 
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
@@ -47,19 +49,35 @@ def payload(n, seed):
 
 
 def run(emu, tmp_path, data, script, timeout=900):
-    """-> (the Row of every push, the `total` lines: (summed, copied, headers, pushes))"""
+    """-> (the Row of every push and every whole, the `total` lines: (summed, copied, headers, pushes)).  Row.same: all 18 fields of the
+    result are those of lex_ref on the same prefix with the same idat_cap, so are the IDAT bytes in front of idat_len, and the two
+    padding bytes of spng_lexed are zero"""
     (tmp_path / "f.png").write_bytes(data)
     (tmp_path / "s.txt").write_text("\n".join(script) + "\n")
-    r = subprocess.run([str(emu), str(tmp_path / "f.png"), str(tmp_path / "s.txt")], capture_output=True, text=True, timeout=timeout, env=ENV)
+    r = subprocess.run([str(emu), str(tmp_path / "f.png"), str(tmp_path / "s.txt"), str(tmp_path / "idat")], capture_output=True, text=True,
+                       timeout=timeout, env=ENV)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lexed = [s.split() for s in script if s.startswith(("push", "whole", "cap", "flip"))]
+    idats, pos = (tmp_path / "idat").read_bytes(), 0
+    data, cap = bytearray(data), len(data)
     rows, totals = [], []
     for line in r.stdout.splitlines():
         v = line.split()
         if len(v) == 4:
             totals.append(tuple(int(x) for x in v))
-        else:
-            rows.append(Row(*[int(x, 16) if k in (2, 3) else int(x) for k, x in enumerate(v)]))
-    assert len(rows) == sum(s.startswith("push") for s in script) and len(totals) == sum(s == "total" for s in script)
+            continue
+        while lexed[0][0] in ("cap", "flip"):
+            cmd, *args = lexed.pop(0)
+            if cmd == "cap":
+                cap = int(args[0])
+            else:
+                data[int(args[0])] ^= int(args[1])
+        got = [int(x, 16) if k in (2, 3) else int(x) for k, x in enumerate(v)]
+        want, want_idat = lex_ref(bytes(data[:int(lexed.pop(0)[1])]), cap)
+        rows.append(Row(*got, same=tuple(got[:18]) == tuple(want) and got[18:20] == [0, 0] and idats[pos:pos + got[12]] == want_idat))
+        pos += got[12]
+    assert pos == len(idats) and not [c for c in lexed if c[0] in ("push", "whole")]
+    assert len(rows) == sum(s.startswith(("push", "whole")) for s in script) and len(totals) == sum(s == "total" for s in script)
     return rows, totals
 
 
@@ -136,7 +154,7 @@ def test_a_chunk_of_several_pieces_is_folded(emu, tmp_path):
     assert rows[1].idat_len == rows[2].idat_len == len(body)
     every_byte_once(data, totals[0])
     every_byte_once(data, totals[1])
-    # a wrong byte in the last piece is found by the fold, with the checksum the whole-file lexer computes
+    # a wrong byte in the last piece is found by the fold
     bad = bytearray(data); bad[at + 8 + len(body) - 5] ^= 1
     rows, _ = run(emu, tmp_path, bytes(bad), ["reset", f"push {at + 8 + (1 << 20) + 3}", f"push {len(data)}"])
     assert rows[1].status == E_CHUNK_CHECKSUM and rows[1].same and rows[1].aux1 == zlib.crc32(bytes(bad[at + 4:at + 8 + len(body)]))
@@ -207,7 +225,7 @@ def test_damage(emu, tmp_path):
         assert (r.status, r.aux0, r.consumed) == (E_SIGNATURE, struct.unpack(">Q", data[:8])[0], 8)
     assert rows[1].same and rows[2].same
 
-    # idat_cap exceeded by the second IDAT: SPNG_E_OUTPUT_CAPACITY once it is complete -- its checksum first, as the whole-file lexer
+    # idat_cap exceeded by the second IDAT: SPNG_E_OUTPUT_CAPACITY once it is complete -- its checksum first
     for broken in (False, True):
         data = bytearray(good)
         if broken:
@@ -246,3 +264,57 @@ def test_arguments_that_only_the_device_sees(emu, tmp_path):
     # states nobody wrote: a wrong magic word, a chunk in progress behind a signature nobody has seen
     rows, _ = run(emu, tmp_path, good, ["reset", "poke 0 7", f"push {n}", "reset"] + [f"poke {k} {v}" for k, v in enumerate(MAGIC)] + ["poke 24 9", f"push {n}", "reset", f"push {n}"])
     assert [r.status for r in rows] == [E_ARGUMENT, E_ARGUMENT, DONE]
+
+
+def test_whole_files_every_prefix(emu, tmp_path):
+    """the whole-file entry on every prefix of a small file, with a list that holds everything and one of two entries"""
+    data = (ph.GOLDEN / "pngsuite" / "common" / "basn0g01.png").read_bytes()
+    n = len(data)
+    for pre in ([], ["list 2"]):
+        rows, _ = run(emu, tmp_path, data, pre + [f"whole {c}" for c in range(n + 1)])
+        assert all(r.same for r in rows), [c for c, r in enumerate(rows) if not r.same]
+        assert all(r.status in WAITS for r in rows[:n]) and rows[n].status == DONE and rows[n].consumed == n
+        assert all((r.summed, r.copied, r.headers) == (0, 0, 0) for r in rows)       # (no counter is added for whole files)
+
+
+def test_whole_files_long_chunks_list_overflow_and_idat_cap(emu, tmp_path):
+    """a chunk of 2.5 MiB, more chunks than the list holds, idat_cap: from the whole-file entry"""
+    body = payload(5 << 19, 2)
+    data = SIG + IHDR + chunk(b"IDAT", body) + IEND
+    at = 8 + len(IHDR)
+    rows, _ = run(emu, tmp_path, data, [f"whole {len(data)}", f"flip {at + 8 + len(body) - 5} 1", f"whole {len(data)}", f"whole {len(data) - 13}"])
+    assert [r.status for r in rows] == [DONE, E_CHUNK_CHECKSUM, E_TRUNCATED_CHUNK_BODY] and all(r.same for r in rows)
+    bad = bytearray(data); bad[at + 8 + len(body) - 5] ^= 1
+    assert rows[0].idat_len == len(body) and rows[1].aux1 == zlib.crc32(bytes(bad[at + 4:at + 8 + len(body)])) and rows[1].idat_len == 0
+    # 200 IDAT chunks of one byte: lex_listed gives 65 entries
+    data = SIG + IHDR + b"".join(chunk(b"IDAT", bytes([k])) for k in range(200)) + IEND
+    rows, _ = run(emu, tmp_path, data, [f"whole {len(data)}", f"flip {8 + len(IHDR) + 150 * 13 + 8} 4", f"whole {len(data)}"])
+    assert all(r.same for r in rows) and (rows[0].status, rows[0].chunks, rows[0].idat_len) == (DONE, 202, 200)
+    assert (rows[1].status, rows[1].chunks, rows[1].idat_len) == (E_CHUNK_CHECKSUM, 151, 150)
+    # idat_cap one byte short of the second IDAT: capacity, and with that chunk's checksum wrong the checksum
+    body = payload(3000, 3)
+    good = SIG + IHDR + chunk(b"IDAT", body) + chunk(b"IDAT", body[:100]) + IEND
+    for listed in (None, 1):
+        pre = [] if listed is None else [f"list {listed}"]
+        rows, _ = run(emu, tmp_path, good, pre + ["cap 3099", f"whole {len(good)}", f"flip {at + 12 + 3000 + 8 + 3} 2", f"whole {len(good)}", "cap 3100",
+                                                  f"whole {len(good)}"])
+        assert [r.status for r in rows] == [E_OUTPUT_CAPACITY, E_CHUNK_CHECKSUM, E_CHUNK_CHECKSUM] and all(r.same for r in rows), listed
+        assert all((r.chunks, r.idat_len, r.consumed) == (2, 3000, at + 12 + 3000) for r in rows)
+
+
+def test_what_lies_behind_the_first_failure_is_not_reported(emu, tmp_path):
+    """CgBI, IHDR, PLTE, tRNS, IDAT, IEND with the checksum of each chunk wrong in turn, as a whole file and in two pushes: the walk has
+    noted the fields of all of them by the time a wave finds the checksum; the answer holds those in front of the failure only"""
+    cs = [chunk(b"CgBI", b"\0\0\0\1"), IHDR, chunk(b"PLTE", b"abcdef"), chunk(b"tRNS", b"xy"), chunk(b"IDAT", payload(50, 5)), IEND]
+    data = SIG + b"".join(cs)
+    n, script, at = len(data), [], 8
+    for c in cs:
+        script += [f"flip {at + 8} 16", f"whole {n}", "reset", f"push {at + 9}", f"push {n}", f"flip {at + 8} 16"]
+        at += len(c)
+    rows, _ = run(emu, tmp_path, data, script[:-6] + [f"whole {n}"])      # (IEND has no data to damage: lexed whole instead)
+    assert all(r.same for r in rows), [k for k, r in enumerate(rows) if not r.same]
+    for k in range(5):
+        for r in (rows[3 * k], rows[3 * k + 2]):
+            assert (r.status, r.chunks) == (E_CHUNK_CHECKSUM, k), k
+            assert (r.ios, r.width, r.plte_len, r.trns_len, r.idat_len) == (int(k > 0), 32 * (k > 1), 6 * (k > 2), 2 * (k > 3), 0), k
+    assert (rows[-1].status, rows[-1].chunks, rows[-1].ios, rows[-1].width, rows[-1].plte_len, rows[-1].trns_len, rows[-1].idat_len) == (DONE, 6, 1, 32, 6, 2, 50)

@@ -1,6 +1,6 @@
 """GPU parity for files that arrive in pieces (spng_lex_resume_batch; waitSignature / waitChunk of the reference's OnlineDecoding
-tutorial, Snippets/PNG/OnlineDecoding.swift): after every push the result and the IDAT bytes in front of idat_len are what
-spng_lex_batch -- the whole-file kernels, the differential yardstick -- gives for the same prefix, byte for byte; over all pushes of
+tutorial, Snippets/PNG/OnlineDecoding.swift): after every push every field of the result and the IDAT bytes in front of idat_len are
+what tests/lex_ref.py -- the reference's loop in plain Python -- gives for the same prefix; over all pushes of
 a file every byte of type + data is summed once and every IDAT byte copied once (spng_lex_resume_stats: counters, not clocks); and
 the tutorial end to end, from file bytes in pieces of 4096 to the images the reference wrote after every IDAT chunk
 (tests/golden/online.json)."""
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import pnghelp as ph
+from lex_ref import lex_ref, of_struct
 
 pytestmark = pytest.mark.gpu
 TABLE = json.loads((ph.GOLDEN / "pngsuite.json").read_text())
@@ -46,10 +47,11 @@ def chunks_of(data):
 class Batch:
     """files on the device, their IDAT buffers and states; a push is one call for all of them"""
 
-    def __init__(self, s, files):
+    def __init__(self, s, files, caps=None):
         self.s, self.files = s, files
+        self.caps = [max(len(f), 1) for f in files] if caps is None else caps      # idat_cap: the size of the IDAT buffer
         self.d_png = [s.to_device(f) for f in files]
-        self.d_idat = [s.empty(len(f)) for f in files]
+        self.d_idat = [s.empty(cap) for cap in self.caps]
         self.states = s.lex_states(len(files))
         self.summed = self.copied = self.headers = self.pushes = 0
 
@@ -61,12 +63,12 @@ class Batch:
         return infos
 
     def push_and_compare(self, lens):
-        """... and the whole-file lexer on the same prefixes says the same, byte for byte"""
+        """... and lex_ref on the same prefixes says the same: every field, the padding zero, the IDAT bytes in front of idat_len"""
         infos = self.push(lens)
-        want, idats = self.s.lex_batch([f[:n] for f, n in zip(self.files, lens)])
-        for k, (got, w, idat) in enumerate(zip(infos, want, idats)):
-            assert bytes(got) == bytes(w), (k, lens[k], got.status, w.status, got.chunks, w.chunks)
-            assert bytes(self.d_idat[k][:got.idat_len].cpu().numpy()) == idat, (k, lens[k])
+        for k, (got, f, n) in enumerate(zip(infos, self.files, lens)):
+            want, idat = lex_ref(f[:n], self.caps[k])
+            assert of_struct(got) == want and bytes(got.pad) == b"\0\0", (k, n, of_struct(got), want)
+            assert bytes(self.d_idat[k][:got.idat_len].cpu().numpy()) == idat, (k, n)
         return infos
 
     def every_byte_once(self):
@@ -192,6 +194,21 @@ def test_a_batch_whose_files_are_at_different_stages(gpu):
     infos = b.push_and_compare([n, n, n, n, len(typed), n, n + 8])
     assert [r.status for r in infos] == [0, 0, 0, gpu.E_CHUNK_CHECKSUM, gpu.E_CHUNK_TYPE, 0, 0]
     assert all(r.idat_len == 3100 for r in infos[:3])
+
+
+def test_idat_cap_one_byte_short_of_the_second_idat(gpu):
+    """SPNG_E_OUTPUT_CAPACITY once the chunk is complete, and with its checksum wrong the checksum: the reference's order"""
+    s = gpu.load()
+    body = payload(3000, 3)
+    good = SIG + IHDR + chunk(b"IDAT", body) + chunk(b"IDAT", body[:100]) + IEND
+    at, n = 8 + len(IHDR), len(good)
+    bad = bytearray(good); bad[at + 12 + 3000 + 8 + 3] ^= 2
+    b = Batch(s, [good, bytes(bad), good, bytes(bad)], [3099, 3099, 3099, 3099])
+    infos = b.push_and_compare([at + 12 + 3000 + 8 + 60, at + 12 + 3000 + 8 + 60, n, n])
+    assert [r.status for r in infos] == [gpu.E_TRUNCATED_CHUNK_BODY, gpu.E_TRUNCATED_CHUNK_BODY, gpu.E_OUTPUT_CAPACITY, gpu.E_CHUNK_CHECKSUM]
+    infos = b.push_and_compare([n] * 4)
+    assert [r.status for r in infos] == [gpu.E_OUTPUT_CAPACITY, gpu.E_CHUNK_CHECKSUM] * 2
+    assert all((r.chunks, r.idat_len, r.consumed) == (2, 3000, at + 12 + 3000) for r in infos)
 
 
 def test_no_files_and_null_arrays(gpu):

@@ -26,6 +26,14 @@ def test_the_arithmetic_is_what_it_was_written_inline():
     assert {r[6] for r in GOLDEN["unfilter_pieces"]} == set(geo.RULES)
 
 
+def test_the_grid_of_the_lexer_sum_and_copy_launch():
+    """8192 / count waves per file, rounded up, four at least, and no more than the longest list (one where there is none): the values
+    the rule gave when it stood inline in the launchers of both lexer entries"""
+    want = {1: (1, 1, 3, 5000), 4: (1, 1, 3, 2048), 2048: (1, 1, 3, 4), 8192: (1, 1, 3, 4), 8193: (1, 1, 3, 4)}
+    for count, row in want.items():
+        assert tuple(geo.lex_piece_blocks_x(count, m) for m in (0, 1, 3, 5000)) == row, count
+
+
 def test_bench_one_block_counts_the_segments_the_library_cuts():
     sys.path.insert(0, str(ph.ROOT))
     import bench_one_block as bob

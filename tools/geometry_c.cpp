@@ -23,6 +23,7 @@ uint32_t geo_write_idat_blocks_x(uint64_t most_pieces) { return write_idat_block
 uint64_t geo_lex_listed(uint64_t len) { return lex_listed(len); }
 uint64_t geo_lex_resume_pieces(uint64_t new_bytes, int32_t complete) { return lex_resume_pieces(new_bytes, complete != 0); }
 uint64_t geo_lex_resume_listed(uint64_t len) { return lex_resume_listed(len); }
+uint32_t geo_lex_piece_blocks_x(uint32_t count, uint32_t max_listed) { return lex_piece_blocks_x(count, max_listed); }
 uint64_t geo_inflate_segment_bytes(uint64_t configured, uint64_t total, double block_bytes) { return inflate_segment_bytes(configured, total, block_bytes); }
 void geo_search_chunks(uint64_t streams, uint32_t out[2])
 {

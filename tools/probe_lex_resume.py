@@ -1,9 +1,9 @@
-"""Times the resumable chunk lexer beside the whole-file one (profiles/r14_lex_resume.md):
+"""Times the resumable chunk lexer beside the whole-file one (profiles/r14_lex_resume.md, profiles/r16_one_lexer.md):
 
-    python tools/probe_lex_resume.py [--large 256] [--small 8192] [--pieces 1,4,64] [--whole-only] [--package DIR] [--out FILE]
+    python tools/probe_lex_resume.py [--large 256] [--small 8192] [--huge 64] [--pieces 1,4,64] [--whole-only] [--package DIR] [--out FILE]
 
-Two workloads: `large` copies of a file shaped like a 4K image's (30 MiB of IDAT in chunks of 64 KiB) and `small` files of one 2 KiB
-IDAT, every file in device memory of its own.  Per workload: SPNG_K_LEX milliseconds (HIP events around the launches, spng_profile)
+Three workloads: `large` copies of a file shaped like a 4K image's (30 MiB of IDAT in chunks of 64 KiB), `small` files of one 2 KiB
+IDAT, and one file that is a single IDAT of `huge` MiB (0: left out), every file in device memory of its own.  Per workload: SPNG_K_LEX milliseconds (HIP events around the launches, spng_profile)
 of spng_lex_batch once on the whole files; of spng_lex_resume_batch summed over the pushes when the files arrive in 1, 4 and 64 equal
 pieces; and of spng_lex_batch on every growing prefix -- what a host had to do before, O(n k).  The counters of
 spng_lex_resume_stats are printed beside the times: bytes summed and copied over all pushes do not depend on the pieces.
@@ -33,6 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--large", type=int, default=256)
     ap.add_argument("--small", type=int, default=8192)
+    ap.add_argument("--huge", type=int, default=64)
     ap.add_argument("--pieces", default="1,4,64")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--whole-only", action="store_true")
@@ -57,7 +58,10 @@ def main():
             best = ms if best is None or ms < best else best
         return best
 
-    for label, count, data in (("4K-image files", args.large, make_file(30 << 20, 1 << 16, 1)), ("small files", args.small, make_file(2048, 2048, 2))):
+    for label, count, data in (("4K-image files", args.large, make_file(30 << 20, 1 << 16, 1)), ("small files", args.small, make_file(2048, 2048, 2)),
+                               ("file of one IDAT", 1 if args.huge else 0, make_file(args.huge << 20, max(args.huge << 20, 1), 3))):
+        if not count:
+            continue
         n = len(data)
         png = s.to_device(data).repeat(count)                   # a copy per file
         idat = torch.empty(count * n, dtype=torch.uint8, device=s.tdev)

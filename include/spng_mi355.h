@@ -302,6 +302,70 @@ int32_t spng_write_idat_batch(spng_ctx *ctx, const spng_chunking_desc *descs, ui
 /* CRC-32 of a host buffer computed on the device (swift-hash CRC32 as used by chunk()) */
 int32_t spng_crc32(spng_ctx *ctx, const void *data, uint64_t n, uint32_t *out);
 
+/* ---- files: whole PNG files written on the device ------------------------------------------------------ */
+/* An ancillary chunk the caller hands over as it is: the writer frames it (length, type, CRC-32) and neither interprets nor
+ * reorders it.  type: the four characters big-endian ('g' << 24 | 'A' << 16 | 'M' << 8 | 'A'); data: `len` HOST bytes. */
+typedef struct spng_blob {
+    uint32_t    type;
+    uint32_t    len;
+    const void *data;
+} spng_blob;
+/* One PNG file to write: signature, the head PNG.Image.compress writes in front of the image data, the zlib stream cut into IDAT
+ * chunks, IEND.  The head, in the order of Sources/PNG/PNG.Image.swift:589-656:
+ *   CgBI (bgr8: [48, 0, 32, 6], bgra8: [48, 0, 32, 2]; PNG.Image.swift:416-423), IHDR (PNG.Header.serialized, Parsing/PNG.Header.swift:133-145),
+ *   the blobs of `before` (the reference's cHRM gAMA sRGB iCCP sBIT), PLTE, bKGD, tRNS (PNG.Layout.palette / .background /
+ *   .transparency, Formats/PNG.Layout.swift:60-194), the blobs of `after` (hIST pHYs tIME iTXt sPLT and application chunks).
+ * The format is named as in spng_unpack_desc: depth, channels, indexed, bgr.  palette: palette_count x (r, g, b, a) HOST bytes --
+ * an indexed format's palette with its alphas (PLTE holds the colours; tRNS the alphas up to the last one that is not 255 and is
+ * absent when all are), or the suggested palette of a colour format (PLTE only when it is not empty; the alphas are ignored).
+ * key / fill: as PNG.Format holds them -- one field for the grey formats, (r, g, b), and (b, g, r) for bgr8 / bgra8, which the layout
+ * turns back (PNG.Format.swift:427-430, PNG.Layout.swift:120-121, 176-178); fields of the 8-bit formats are at most 255 and are
+ * widened to 16-bit big-endian ones; an indexed format's fill is fill[0], a palette index.
+ * The stream: d_stream[0 .. n) with n = stream_len, or -- d_stream_result given -- n = d_stream_result->written, read on the
+ * device: the slot spng_encode_batch / spng_deflate_batch wrote with d_results, so that nothing waits between the two calls.
+ * stream_cap: a host-known bound on n (the capacity of d_stream; spng_deflate_bound is the natural value); it sizes the launch.  With
+ * a host length it may be 0 (= stream_len). */
+typedef struct spng_png_desc {
+    const void        *d_stream;  uint64_t stream_len;
+    const spng_result *d_stream_result;         /* device pointer, or NULL: stream_len holds.  Must not lie in the call's d_results */
+    uint64_t           stream_cap;
+    void              *d_out;     uint64_t out_cap;     /* spng_file_bound(desc, n) bytes are written */
+    uint64_t           chunk_bytes;             /* payload bytes of every IDAT but the last: 1 ... 0x7fffffff.  The reference cuts at twice
+                                                   the capacity its output buffer got (LZ77.DeflatorOut.swift:15-24, 121): an allocator
+                                                   fact, 65544 at the default hint on Linux, 8200 at hint 4096 */
+    uint32_t           width, height;
+    uint8_t            depth, channels, indexed, bgr, interlaced, has_key, has_fill, reserved;   /* reserved: zero */
+    uint16_t           key[3], fill[3];
+    uint32_t           palette_count;
+    const uint8_t     *palette;
+    const spng_blob   *before;    uint32_t before_count;
+    const spng_blob   *after;     uint32_t after_count;
+} spng_png_desc;
+/* The exact size of the file for a stream of stream_len bytes: 8 + head + stream_len + 12 ceil(stream_len / chunk_bytes) + 12 --
+ * with spng_deflate_bound the capacity to allocate.  0: a desc spng_write_file_batch refuses, or stream_len == 0. */
+uint64_t spng_file_bound(const spng_png_desc *desc, uint64_t stream_len);
+/* replaces PNG.Image.compress(stream:level:hint:) behind its encoder (Sources/PNG/PNG.Image.swift:576-668): signature(), the format(type:data:)
+ * of every chunk (Lexing/PNG.BytestreamDestination.swift:44-88) and the IDAT loop -- every chunk but the last carries chunk_bytes
+ * bytes, and none is empty (the last pull() of an exhausted stream returns nil, LZ77.DeflatorBuffers.swift:142-151).  Lengths, types
+ * and CRC-32s of the head are laid down on the host and uploaded with the job table; payloads move and are summed on the device, a
+ * chunk longer than 1 MiB in pieces of 1 MiB by a wave each.  Refused with SPNG_E_ARGUMENT (the call; nothing is launched): a blob
+ * whose type is CgBI IHDR PLTE bKGD tRNS IDAT IEND or one spng_lex_batch would not accept (PNG.Chunk.swift:69-88), a palette count
+ * outside what the format allows (PNG.Format.swift:274-309), a width or height of 0, chunk_bytes outside 1 ... 0x7fffffff, a depth /
+ * channels / flag combination that is no PNG.Format, a key where the format has none, a field its format does not hold.
+ * Results per file: SPNG_DONE with written = file bytes, consumed = stream bytes, aux[0] = IDAT chunks.  SPNG_E_OUTPUT_CAPACITY
+ * with written = the bytes needed, nothing written.  A source result whose status is not SPNG_DONE: that status and its aux,
+ * written = consumed = 0, nothing written.  SPNG_E_ARGUMENT: n == 0 (no zlib stream is empty) or n > stream_cap.
+ * With d_results only the call stays asynchronous. */
+int32_t spng_write_file_batch(spng_ctx *ctx, const spng_png_desc *descs, uint32_t count,
+                              spng_result *d_results, spng_result *h_results);
+/* replaces PNG.Image.compress(stream:level:hint:) from storage (PNG.Image.swift:576-668): spng_encode_batch over `images`, then the
+ * writer over `files` reading the encoder's results on the device -- no host wait between them, one optional read-back.  images[i]:
+ * as for spng_encode_batch (d_idat / idat_len: where the stream goes and its capacity).  files[i]: d_out, out_cap, chunk_bytes,
+ * indexed, bgr, palette, key, fill and the blobs; its stream fields, width, height, depth, channels and interlaced are taken from
+ * images[i] (bgr must agree with images[i].format == SPNG_FORMAT_IOS).  Formats, sizes, interlacing and standards may be mixed. */
+int32_t spng_compress_batch(spng_ctx *ctx, const spng_image_desc *images, const spng_png_desc *files, int32_t level, uint32_t count,
+                            spng_result *d_results, spng_result *h_results);
+
 /* A stream that arrives in pieces (PNG.Context.push(data:) per IDAT chunk): defilters and assigns the
  * scanlines that became complete between h_prev_len[i] and h_now_len[i] inflated bytes -- what PNG.Decoder.row / pass keep
  * track of (Sources/PNG/Decoding/PNG.Decoder.swift:20-21, 88-94, 121-135) -- each row once, with the defiltered row above it

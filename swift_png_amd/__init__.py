@@ -72,6 +72,7 @@ EXPORTS = [
     "spng_lex_batch", "spng_write_idat_batch", "spng_crc32", "spng_unpack_batch", "spng_unpack", "spng_unpack_as", "spng_pack_batch", "spng_pack_as", "spng_alpha_batch", "spng_alpha", "spng_hsva_batch", "spng_hsva", "spng_luminance_batch", "spng_luminance", "spng_census_batch", "spng_census", "spng_pack_indexed_batch", "spng_pack_indexed", "spng_census_wide_batch", "spng_census_wide", "spng_map_batch", "spng_map", "spng_deflate_bound", "spng_deflate_batch", "spng_deflate", "spng_deflate_window", "spng_encode_batch",
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
     "spng_lex_state_bytes", "spng_lex_resume_batch", "spng_lex_resume_stats",
+    "spng_file_bound", "spng_write_file_batch", "spng_compress_batch",
 ]
 
 
@@ -170,6 +171,56 @@ class MapDesc(ctypes.Structure):
 class ChunkingDesc(ctypes.Structure):
     _fields_ = [("d_stream", ctypes.c_void_p), ("len", ctypes.c_uint64), ("d_out", ctypes.c_void_p),
                 ("out_cap", ctypes.c_uint64), ("chunk_bytes", ctypes.c_uint64)]
+
+
+class Blob(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_uint32), ("len", ctypes.c_uint32), ("data", ctypes.c_void_p)]
+
+
+class PngDesc(ctypes.Structure):
+    _fields_ = [("d_stream", ctypes.c_void_p), ("stream_len", ctypes.c_uint64), ("d_stream_result", ctypes.c_void_p),
+                ("stream_cap", ctypes.c_uint64), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_uint64), ("chunk_bytes", ctypes.c_uint64),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("depth", ctypes.c_uint8), ("channels", ctypes.c_uint8),
+                ("indexed", ctypes.c_uint8), ("bgr", ctypes.c_uint8), ("interlaced", ctypes.c_uint8), ("has_key", ctypes.c_uint8),
+                ("has_fill", ctypes.c_uint8), ("reserved", ctypes.c_uint8), ("key", ctypes.c_uint16 * 3), ("fill", ctypes.c_uint16 * 3),
+                ("palette_count", ctypes.c_uint32), ("palette", ctypes.c_void_p), ("before", ctypes.POINTER(Blob)),
+                ("before_count", ctypes.c_uint32), ("after", ctypes.POINTER(Blob)), ("after_count", ctypes.c_uint32)]
+
+
+def png_desc(size, depth, channels, indexed=False, bgr=False, interlaced=False, palette=None, key=None, fill=None, before=(), after=(),
+             chunk_bytes=65544):
+    """A spng_png_desc without its device fields, and what keeps its host arrays alive: -> (PngDesc, keep).  palette: bytes or rows of
+    (r, g, b, a); key / fill: as PNG.Format holds them -- an int for the grey formats (an indexed format's fill: a palette index),
+    (r, g, b), and (b, g, r) for bgr8 / bgra8; before / after: (type, payload) pairs with four-byte types."""
+    d, keep = PngDesc(), []
+    d.chunk_bytes = int(chunk_bytes)
+    d.width, d.height, d.depth, d.channels = int(size[0]), int(size[1]), int(depth), int(channels)
+    d.indexed, d.bgr, d.interlaced = int(bool(indexed)), int(bool(bgr)), int(bool(interlaced))
+    for name, v in (("key", key), ("fill", fill)):
+        if v is not None:
+            v = [int(v)] if isinstance(v, int) else [int(x) for x in v]
+            setattr(d, "has_" + name, 1)
+            setattr(d, name, (ctypes.c_uint16 * 3)(*(v + [0, 0])[:3]))
+    if palette is not None and len(palette):
+        raw = bytes(palette) if isinstance(palette, (bytes, bytearray, memoryview)) else bytes(x for p in palette for x in p)
+        buf = _cbuf(raw)
+        keep.append(buf)
+        d.palette_count, d.palette = len(raw) // 4, ctypes.addressof(buf)
+    for name, blobs in (("before", before), ("after", after)):
+        blobs = list(blobs)
+        if not blobs:
+            continue
+        arr = (Blob * len(blobs))()
+        for k, (kind, payload) in enumerate(blobs):
+            kind, buf = bytes(kind), _cbuf(payload)
+            if len(kind) != 4:
+                raise SpngError(E_ARGUMENT)
+            keep.append(buf)
+            arr[k] = Blob(int.from_bytes(kind, "big"), len(bytes(payload)), ctypes.addressof(buf))
+        keep.append(arr)
+        setattr(d, name, arr)
+        setattr(d, name + "_count", len(blobs))
+    return d, keep
 
 
 # ---- error mirror --------------------------------------------------------------------------------
@@ -290,6 +341,10 @@ def load_library():
     lib.spng_lex_resume_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.spng_write_idat_batch.argtypes = [vp, ctypes.POINTER(ChunkingDesc), u32, vp, rp]
     lib.spng_crc32.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
+    lib.spng_file_bound.restype = u64
+    lib.spng_file_bound.argtypes = [ctypes.POINTER(PngDesc), u64]
+    lib.spng_write_file_batch.argtypes = [vp, ctypes.POINTER(PngDesc), u32, vp, rp]
+    lib.spng_compress_batch.argtypes = [vp, ctypes.POINTER(ImageDesc), ctypes.POINTER(PngDesc), i32, u32, vp, rp]
     lib.spng_unpack_batch.argtypes = [vp, vp, u32]
     lib.spng_unpack.argtypes = [vp, vp, u32, u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 vp, u32, vp, vp]
@@ -716,6 +771,63 @@ class Session:
         _check(self.lib, self.lib.spng_write_idat_batch(self.ctx, d, 1, None, res))
         raise_for(res[0].status)
         return bytes(dst[:res[0].written].cpu().numpy())
+
+    def write_file_batch(self, descs, d_results=None, wait=True):
+        """spng_write_file_batch over PngDesc records whose device fields are filled in.  wait: -> list[Result]; else the results stay
+        in the device tensor d_results and the call returns once the kernels are enqueued"""
+        n = len(descs)
+        arr = descs if isinstance(descs, ctypes.Array) else (PngDesc * n)(*descs)
+        res = (Result * n)() if wait else None
+        _check(self.lib, self.lib.spng_write_file_batch(self.ctx, arr, n, self._ptr(d_results) if d_results is not None else None, res))
+        return list(res) if wait else None
+
+    def write_file(self, stream: bytes, size, depth, channels, chunk_bytes=65544, **fmt) -> bytes:
+        """The PNG file around a zlib stream: signature, the head PNG.Image.compress(stream:level:hint:) writes for the format (png_desc:
+        indexed, bgr, interlaced, palette, key, fill, before, after), the stream in IDAT chunks of chunk_bytes, IEND."""
+        d, keep = png_desc(size, depth, channels, chunk_bytes=chunk_bytes, **fmt)
+        cap = int(self.lib.spng_file_bound(ctypes.byref(d), len(stream)))
+        src, dst = self.to_device(stream), self.empty(cap)
+        d.d_stream, d.stream_len, d.d_out, d.out_cap = src.data_ptr() if len(stream) else dst.data_ptr(), len(stream), dst.data_ptr(), cap
+        (res,) = self.write_file_batch([d])
+        raise_for(res.status, (res.aux[0], res.aux[1]))
+        if res.status != DONE:
+            raise SpngError(res.status)
+        return bytes(dst[:res.written].cpu().numpy())
+
+    def compress_batch(self, images, level=9):
+        """PNG.Image.compress(stream:level:hint:) from storage for a batch, one call of spng_compress_batch: images: dicts of
+        storage (bytes, or a uint8 device tensor: the pixels stay on the device), size, depth, channels and what png_desc takes (indexed, bgr, interlaced, palette, key, fill, before, after,
+        chunk_bytes).  -> list of file bytes"""
+        n = len(images)
+        idescs, fdescs, keep, outs = (ImageDesc * n)(), (PngDesc * n)(), [], []
+        for i, im in enumerate(images):
+            im = dict(im)
+            storage, size, depth, channels = im.pop("storage"), im.pop("size"), im.pop("depth"), im.pop("channels")
+            interlaced, bgr = bool(im.get("interlaced", False)), bool(im.get("bgr", False))
+            u = inflated_size(size[0], size[1], depth, channels, interlaced)
+            bound = int(self.lib.spng_deflate_bound(u))
+            d, k = png_desc(size, depth, channels, **im)
+            d_storage = storage if self.torch.is_tensor(storage) else self.to_device(bytes(storage))
+            d_rows, d_idat = self.empty(u), self.empty(bound)
+            cap = int(self.lib.spng_file_bound(ctypes.byref(d), bound))
+            d_out = self.empty(cap)
+            d.d_out, d.out_cap = d_out.data_ptr(), cap
+            idescs[i] = self.image_desc(d_idat, d_rows, d_storage, size[0], size[1], depth, channels, interlaced, FORMAT_IOS if bgr else FORMAT_ZLIB,
+                                        rows_cap=u)
+            fdescs[i] = d
+            keep += [k, d_storage, d_rows, d_idat]
+            outs.append(d_out)
+        res = (Result * n)()
+        _check(self.lib, self.lib.spng_compress_batch(self.ctx, idescs, fdescs, int(level), n, None, res))
+        for r in res:
+            raise_for(r.status, (r.aux[0], r.aux[1]))
+            if r.status != DONE:
+                raise SpngError(r.status)
+        return [bytes(o[:r.written].cpu().numpy()) for o, r in zip(outs, res)]
+
+    def compress(self, storage: bytes, size, depth, channels, level=9, **fmt) -> bytes:
+        """One image: storage in, the bytes of its PNG file out"""
+        return self.compress_batch([dict(fmt, storage=storage, size=size, depth=depth, channels=channels)], level)[0]
 
     def crc32(self, data: bytes) -> int:
         out = ctypes.c_uint32(0)

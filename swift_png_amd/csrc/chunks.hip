@@ -506,6 +506,127 @@ __global__ __launch_bounds__(64) void write_idat_kernel(const spng_chunking_desc
     }
 }
 
+// ---- whole files (spng_write_file_batch) ------------------------------------------------------------------------------------
+// PNG.Image.compress(stream:level:hint:) behind its encoder (PNG.Image.swift:576-668): signature ‖ head ‖ IDAT chunks ‖ IEND.  The head
+// -- everything between the signature and the first IDAT -- arrives finished from the host (file_head.hpp).  The stream's length is a
+// host value or the `written` of a spng_result the deflater left in device memory, so no launch depends on it: the grid is sized by
+// the stream's capacity, a wave strides over the units of its file (geometry.hpp: a unit is a piece of at most FILE_PIECE_BYTES of a
+// chunk) and the waves without a unit leave.  `wfile_body_kernel`: a unit is copied -- 16-byte stores aligned on the DESTINATION, whose
+// offset against the source changes from chunk to chunk (8 + head + k (c + 12) + 8 against k c), unaligned 16-byte loads, the bytes
+// in front of the first and behind the last aligned unit by the lanes they belong to -- and summed from the source by wave_crc32; a
+// chunk of one piece is finished there, the raw sums of a longer one go to `wfile_finish_kernel`, a thread per chunk, which folds
+// them (crc(A || B) = crc(A) * x^(8 |B|) + crc(B): every piece but the last is FILE_PIECE_BYTES long, one constant of CRC_POW).
+__device__ __forceinline__ void copy_dst_aligned(gbyte *dst, const gbyte *src, uint64_t n, int lane)
+{
+    typedef uint32_t c4 __attribute__((vector_size(16)));
+    struct __attribute__((packed)) P16 { c4 v; };
+    typedef P16 __attribute__((address_space(1))) gP16;
+    typedef c4 __attribute__((address_space(1))) gA16;
+    const uint64_t lead = (16 - ((uint64_t)dst & 15)) & 15, head = lead < n ? lead : n;
+    if ((uint64_t)lane < head) dst[lane] = src[lane];
+    const uint64_t units = (n - head) / 16;
+    // (eight loads in flight per lane: a piece of 1 MiB is one wave's, and a load a step left it waiting on memory 1024 times)
+    uint64_t u = lane;
+    for (; u + 7 * 64 < units; u += 8 * 64) {
+        c4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = ((const gP16 *)(src + head + (u + 64 * k) * 16))->v;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) *(gA16 *)(dst + head + (u + 64 * k) * 16) = v[k];
+    }
+    for (; u < units; u += 64) *(gA16 *)(dst + head + u * 16) = ((const gP16 *)(src + head + u * 16))->v;
+    const uint64_t done = head + units * 16;
+    if ((uint64_t)lane < n - done) dst[done + lane] = src[done + lane];
+}
+
+// what a file's result says before anything is written: the length, the chunks, the bytes needed
+struct FilePlan { int32_t status; uint64_t n, chunks, need, aux0, aux1; };
+__device__ __forceinline__ FilePlan wfile_plan(const FileJob &j)
+{
+    FilePlan p;
+    p.status = SPNG_DONE; p.n = uni64(j.len); p.chunks = p.need = p.aux0 = p.aux1 = 0;
+    const spng_result *sr = (const spng_result *)uni64((uint64_t)j.src_result);
+    if (sr) {
+        p.status = (int32_t)UNI(sr->status); p.n = uni64(sr->written);
+        if (p.status != SPNG_DONE) { p.aux0 = uni64(sr->aux[0]); p.aux1 = uni64(sr->aux[1]); return p; }
+    }
+    // (no zlib stream is empty; a length behind the capacity the launch and the scratch were sized by is nobody's stream)
+    if (p.n == 0 || p.n > uni64(j.stream_cap)) { p.status = SPNG_E_ARGUMENT; return p; }
+    p.chunks = file_chunks(p.n, uni64(j.chunk_bytes));
+    p.need = 8 + uni64(j.head_len) + p.n + 12 * p.chunks + 12;
+    if (p.need > uni64(j.out_cap)) p.status = SPNG_E_OUTPUT_CAPACITY;
+    return p;
+}
+
+__global__ __launch_bounds__(64) void wfile_body_kernel(const FileJob *__restrict__ jobs, spng_result *__restrict__ results)
+{
+    __shared__ uint32_t tab[CRC_TAB];
+    const int lane = threadIdx.x;
+    const FileJob j = jobs[blockIdx.y];
+    const FilePlan p = wfile_plan(j);
+    if (blockIdx.x == 0 && lane == 0) {
+        spng_result &res = results[blockIdx.y];
+        res.status = p.status; res.reserved = 0;
+        res.written = p.status == SPNG_DONE || p.status == SPNG_E_OUTPUT_CAPACITY ? p.need : 0;
+        res.consumed = p.status == SPNG_DONE ? p.n : 0;
+        res.aux[0] = p.status == SPNG_DONE ? p.chunks : p.aux0; res.aux[1] = p.aux1;
+    }
+    if (p.status != SPNG_DONE) return;
+    const uint64_t c = uni64(j.chunk_bytes), head_len = uni64(j.head_len);
+    const uint64_t per = file_pieces(c), full = (p.chunks - 1) * per, units = full + file_pieces(p.n - (p.chunks - 1) * c);
+    if (blockIdx.x >= units) return;
+    const gbyte *stream = (const gbyte *)uni64((uint64_t)j.stream);
+    gbyte *out = (gbyte *)uni64((uint64_t)j.out);
+    uint32_t *partial = (uint32_t *)uni64((uint64_t)j.partial);
+    if (blockIdx.x == 0) {
+        // signature() and the head in front of the chunks, format(type: .IEND) behind them (BytestreamDestination.swift:44-88)
+        if (lane < 8) out[lane] = (uint8_t)(0x89504e470d0a1a0aull >> (8 * (7 - lane)));
+        copy_dst_aligned(out + 8, (const gbyte *)uni64((uint64_t)j.head), head_len, lane);
+        if (lane < 12) out[p.need - 12 + lane] = (uint8_t)(lane < 4 ? 0 : (0x49454e44ae426082ull >> (8 * (11 - lane))));
+    }
+    crc_table(tab, lane);
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint64_t k = u < full ? u / per : p.chunks - 1, piece = u < full ? u % per : u - full;
+        const uint64_t clen = k == p.chunks - 1 ? p.n - k * c : c;
+        const uint64_t lo = piece * FILE_PIECE_BYTES, len = clen - lo < FILE_PIECE_BYTES ? clen - lo : FILE_PIECE_BYTES;
+        const gbyte *src = stream + k * c + lo;
+        gbyte *o = out + 8 + head_len + k * (c + 12);
+        copy_dst_aligned(o + 8 + lo, src, len, lane);
+        if (piece == 0 && lane < 8) o[lane] = (uint8_t)(((uint64_t)clen << 32 | 0x49444154u) >> (8 * (7 - lane)));
+        if (clen <= FILE_PIECE_BYTES) {
+            const uint32_t crc = chunk_crc32(tab, 0x49444154u, src, len, lane);
+            if (lane < 4) o[8 + clen + lane] = (uint8_t)(crc >> (8 * (3 - lane)));
+        } else {
+            // raw sums: the first piece's over the type and its bytes
+            const uint32_t raw = piece == 0 ? crc32_conditioning(chunk_crc32(tab, 0x49444154u, src, len, lane), len + 4)
+                                            : crc32_conditioning(wave_crc32(tab, src, len, 0, lane), len);
+            if (lane == 0) partial[u] = raw;
+        }
+    }
+}
+
+// the chunks of several pieces: folded and written, a thread per chunk
+__global__ void wfile_finish_kernel(const FileJob *__restrict__ jobs, const spng_result *__restrict__ results)
+{
+    const FileJob j = jobs[blockIdx.y];
+    const spng_result r = results[blockIdx.y];
+    if (r.status != SPNG_DONE || j.chunk_bytes <= FILE_PIECE_BYTES) return;
+    const uint64_t c = j.chunk_bytes, n = r.consumed, chunks = r.aux[0], per = file_pieces(c);
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < chunks; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t clen = k == chunks - 1 ? n - k * c : c;
+        if (clen <= FILE_PIECE_BYTES) continue;                // (finished by the wave that copied it)
+        const uint64_t pieces = file_pieces(clen);
+        const uint32_t *part = j.partial + k * per;
+        uint32_t crc = part[0];
+        for (uint64_t q = 1; q < pieces; ++q)
+            crc = multmodp(q + 1 < pieces ? CRC_POW.v[20] : xpow8(clen - q * FILE_PIECE_BYTES), crc) ^ part[q];
+        crc = crc32_conditioning(crc, clen + 4);
+        uint8_t *o = j.out + 8 + j.head_len + k * (c + 12) + 8 + clen;
+        for (int b = 0; b < 4; ++b) o[b] = (uint8_t)(crc >> (8 * (3 - b)));
+    }
+}
+static_assert(FILE_PIECE_BYTES == 1ull << 20, "wfile_finish_kernel shifts by CRC_POW.v[20]");
+
 // raw (zero-initialised, un-finalised) CRC of 1 MiB pieces: the host folds them (spng_crc32)
 __global__ __launch_bounds__(64) void crc_partial_kernel(const uint8_t *__restrict__ data, uint64_t n, uint64_t piece, uint32_t *__restrict__ partial)
 {
@@ -564,6 +685,19 @@ hipError_t launch_write_idat(const spng_chunking_desc *d_descs, uint32_t count, 
     if (!count) return hipSuccess;
     return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
         write_idat_kernel<<<dim3(blocks_x ? blocks_x : 1, ny), 64, 0, stream>>>(d_descs + y0, d_results + y0);
+    });
+}
+hipError_t launch_write_file(const FileJob *d_jobs, uint32_t count, uint32_t blocks_x, uint64_t finish_chunks, spng_result *d_results,
+                             hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        wfile_body_kernel<<<dim3(blocks_x ? blocks_x : 1, ny), 64, 0, stream>>>(d_jobs + y0, d_results + y0);
+    });
+    if (e != hipSuccess || !finish_chunks) return e;
+    const uint32_t fx = (uint32_t)std::min<uint64_t>((finish_chunks + 63) / 64, 1024);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        wfile_finish_kernel<<<dim3(fx, ny), 64, 0, stream>>>(d_jobs + y0, d_results + y0);
     });
 }
 hipError_t launch_crc_partial(const uint8_t *d, uint64_t n, uint64_t piece, uint32_t *d_partial, uint32_t pieces, hipStream_t stream)

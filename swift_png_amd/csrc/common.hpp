@@ -197,6 +197,16 @@ struct MapJob {
     uint8_t        layout, premultiply, value_bytes, pad;
 };
 
+// One PNG file to write (chunks.hip, wfile_body_kernel + wfile_finish_kernel)
+struct FileJob {
+    const uint8_t *head;          // device copy of the bytes between the signature and the first IDAT (file_head.hpp)
+    const uint8_t *stream;
+    const spng_result *src_result;    // device: the stream's status and length (written), or null: len
+    uint8_t       *out;
+    uint32_t      *partial;       // chunks of several pieces: a raw CRC per unit of the file (null when chunk_bytes allows none)
+    uint64_t       head_len, len, stream_cap, out_cap, chunk_bytes;
+};
+
 struct InflateJob {
     const uint8_t *src;
     uint8_t       *dst;
@@ -466,6 +476,9 @@ size_t lex_rwalk_bytes();
 hipError_t launch_lex_resume(const spng_file_desc *d_files, void *const *d_states, uint32_t count, spng_lexed *d_out, void *d_table,
                              const uint64_t *d_table_at, void *d_walks, uint32_t max_listed, uint64_t *d_stats, hipStream_t stream);
 hipError_t launch_write_idat(const spng_chunking_desc *d_descs, uint32_t count, uint32_t blocks_x, spng_result *d_results, hipStream_t stream);
+// finish_chunks: the most chunks of several pieces a file of the launch can have (0: none can, nothing to fold)
+hipError_t launch_write_file(const FileJob *d_jobs, uint32_t count, uint32_t blocks_x, uint64_t finish_chunks, spng_result *d_results,
+                             hipStream_t stream);
 hipError_t launch_crc_partial(const uint8_t *d, uint64_t n, uint64_t piece, uint32_t *d_partial, uint32_t pieces, hipStream_t stream);
 uint32_t crc32_fold(const uint32_t *partial, uint64_t pieces, uint64_t n, uint64_t piece);
 hipError_t launch_filter(const FilterJob *d_jobs, uint32_t count, uint32_t max_rows, hipStream_t stream);

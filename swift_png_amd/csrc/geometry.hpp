@@ -148,6 +148,24 @@ inline uint32_t lex_piece_blocks_x(uint32_t count, uint32_t max_listed)
     return std::min(std::max(max_listed, 1u), want);
 }
 
+// wfile_body_kernel (whole files written on the device): a stream of n bytes is cut into IDAT chunks of c bytes, the last one shorter,
+// and every chunk into pieces of FILE_PIECE_BYTES that a wave each copies and sums -- a file written as one IDAT must not sit on one
+// wave.  A unit is a piece: the units of a stream are those of its full chunks, chunk after chunk, then those of the last.
+constexpr uint64_t FILE_PIECE_BYTES = LEX_PIECE_BYTES;
+constexpr uint64_t file_pieces(uint64_t chunk_len) { return (chunk_len + FILE_PIECE_BYTES - 1) / FILE_PIECE_BYTES; }
+constexpr uint64_t file_chunks(uint64_t n, uint64_t c) { return n ? (n + c - 1) / c : 0; }
+constexpr uint64_t file_units(uint64_t n, uint64_t c)
+{
+    return n ? (file_chunks(n, c) - 1) * file_pieces(c) + file_pieces(n - (file_chunks(n, c) - 1) * c) : 0;
+}
+// The length may exist on the device only, so the grid is sized by the host-known capacity of the stream (file_units is monotonic in
+// n) and surplus workgroups leave; a wave strides over its file's units, as lex_piece_blocks_x has it.  count: files of the launch;
+// most_units: the most units any of them can have
+inline uint32_t file_blocks_x(uint32_t count, uint64_t most_units)
+{
+    return lex_piece_blocks_x(count, (uint32_t)std::min<uint64_t>(most_units, 1u << 20));
+}
+
 // ---- inflate: segment length -------------------------------------------------------------------------------------
 // configured: SPNG_CFG_SEGMENT_BYTES, or (0) by the batch's compressed bytes `total` and the compressed bytes per DEFLATE block
 // the last batch showed (block_bytes; 0: not known).

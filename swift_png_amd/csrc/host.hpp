@@ -65,6 +65,7 @@ struct spng_ctx {
     uint64_t sym_failed = 0;                        // a symbol scratch of this size could not be had (forgotten by spng_trim)
     void *d_win = nullptr;  size_t win_cap = 0;
     void *d_census = nullptr; size_t census_cap = 0; // spng_census_batch: the images' hash tables and sort buffers
+    void *d_file = nullptr;  size_t file_cap = 0;    // spng_compress_batch: the encoder's results, which the writer reads on the device
     // token pool of the pipeline (pinflate2.hip): halfwords a compressed byte turned into in the last batch (learned,
     // so that the next batch of the same kind takes one pass), and the pinned word the page counter is read back into
     double   pool_ratio = 0;
@@ -94,10 +95,10 @@ struct spng_ctx {
 
     // the buffers a batch sizes (spng_trim gives them back to the device; d_ws, the job tables', stays)
     struct Buf { void **p; size_t *cap; };
-    std::array<Buf, 7> batch_buffers()
+    std::array<Buf, 8> batch_buffers()
     {
         return {{{&d_graph, &graph_cap}, {&d_log, &log_cap}, {&d_tok, &tok_cap}, {&d_sym, &sym_cap}, {&d_win, &win_cap}, {&d_multi, &multi_cap},
-                 {&d_census, &census_cap}}};
+                 {&d_census, &census_cap}, {&d_file, &file_cap}}};
     }
     // Makes a device buffer of the context hold `need` bytes.  Only when it has to grow: waits for the stream (kernels in
     // flight may still read the old one), frees it and allocates need + slack.  A failed allocation is an error -- or, `failed`

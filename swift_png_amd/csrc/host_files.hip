@@ -1,7 +1,56 @@
-// host_files.hip -- host side of the file stages: the entries of the C ABI that lex PNG files into chunks, write IDAT chunks and
-// compute CRC-32.
+// host_files.hip -- host side of the file stages: the entries of the C ABI that lex PNG files into chunks, write IDAT chunks and whole
+// files, and compute CRC-32.
 #include "host.hpp"
 #include "geometry.hpp"
+#include "file_head.hpp"
+
+// The writer over descs[0, count): heads built on the host (file_head.hpp) and uploaded through the call's arena with the job table.
+// The caller holds the context's lock.
+static int32_t write_files(spng_ctx *c, const spng_png_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    std::vector<uint8_t> heads;
+    std::vector<uint64_t> head_at(count, 0), head_len(count, 0), part_at(count + 1, 0);
+    uint64_t most_units = 1, finish_chunks = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_png_desc &d = descs[i];
+        if (!d.d_stream || !d.d_out || (!d.d_stream_result && d.stream_cap && d.stream_cap < d.stream_len)) return SPNG_E_ARGUMENT;
+        while (heads.size() % 16) heads.push_back(0);          // (every head at a multiple of 16 of the arena)
+        head_at[i] = heads.size();
+        if (int32_t st = file_head(d, heads)) return st;
+        head_len[i] = heads.size() - head_at[i];
+        const uint64_t cap = d.d_stream_result || d.stream_cap ? d.stream_cap : d.stream_len;
+        const uint64_t units = file_units(cap, d.chunk_bytes);
+        most_units = units > most_units ? units : most_units;
+        // raw sums for the chunks of several pieces: a word per unit the capacity allows
+        part_at[i + 1] = part_at[i] + (d.chunk_bytes > FILE_PIECE_BYTES && cap > FILE_PIECE_BYTES ? units : 0);
+        if (part_at[i + 1] > part_at[i]) finish_chunks = std::max(finish_chunks, file_chunks(cap, d.chunk_bytes));
+    }
+    if (int32_t st = c->reserve(count * (sizeof(FileJob) + sizeof(spng_result)) + heads.size() + 4 * part_at[count] + 4096)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(FileJob));
+    const size_t hslot = a.take(heads.size());
+    const size_t upload = a.off;
+    const size_t rslot = a.take(count * sizeof(spng_result));
+    const size_t pslot = a.take(4 * part_at[count]);
+    if (!heads.empty()) memcpy(a.host<uint8_t>(hslot), heads.data(), heads.size());
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_png_desc &d = descs[i];
+        FileJob j{};
+        j.head = a.dev<uint8_t>(hslot) + head_at[i]; j.head_len = head_len[i];
+        j.stream = (const uint8_t *)d.d_stream; j.src_result = d.d_stream_result; j.len = d.d_stream_result ? 0 : d.stream_len;
+        j.stream_cap = d.d_stream_result || d.stream_cap ? d.stream_cap : d.stream_len;
+        j.out = (uint8_t *)d.d_out; j.out_cap = d.out_cap; j.chunk_bytes = d.chunk_bytes;
+        j.partial = part_at[i + 1] > part_at[i] ? a.dev<uint32_t>(pslot) + part_at[i] : nullptr;
+        a.host<FileJob>(jslot)[i] = j;
+    }
+    if (int32_t st = c->upload(0, upload)) return st;
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    {
+        Timed t(c, SPNG_K_LEX);
+        HIP_TRY(launch_write_file(a.dev<FileJob>(jslot), count, file_blocks_x(count, most_units), finish_chunks, dr, c->stream));
+    }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
 
 // Both lexer entries.  d_states: a state per file (files that arrive in pieces: the call's counters go to c->h_lex_stats), or null:
 // whole files
@@ -110,6 +159,48 @@ int32_t spng_write_idat_batch(spng_ctx *c, const spng_chunking_desc *descs, uint
     spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
     { Timed t(c, SPNG_K_LEX); HIP_TRY(launch_write_idat(a.dev<spng_chunking_desc>(dslot), count, write_idat_blocks_x(most), dr, c->stream)); }
     return read_back(c, h_results, dr, count * sizeof(spng_result));
+}
+
+uint64_t spng_file_bound(const spng_png_desc *desc, uint64_t stream_len) { return desc ? file_bound(*desc, stream_len) : 0; }
+
+int32_t spng_write_file_batch(spng_ctx *c, const spng_png_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    return write_files(c, descs, count, d_results, h_results);
+}
+
+int32_t spng_compress_batch(spng_ctx *c, const spng_image_desc *images, const spng_png_desc *files, int32_t level, uint32_t count,
+                            spng_result *d_results, spng_result *h_results)
+{
+    if (!c || ((!images || !files) && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    // the files with the stream fields and the header fields of their images; refused before anything is launched
+    std::vector<spng_png_desc> fd(files, files + count);
+    std::vector<uint8_t> scratch;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_image_desc &im = images[i];
+        spng_png_desc &d = fd[i];
+        if ((im.format == SPNG_FORMAT_IOS) != (d.bgr != 0) || im.format > SPNG_FORMAT_IOS || !im.d_idat || !d.d_out) return SPNG_E_ARGUMENT;
+        d.width = im.width; d.height = im.height; d.depth = im.depth; d.channels = im.channels; d.interlaced = im.interlaced;
+        d.d_stream = im.d_idat; d.stream_len = 0; d.stream_cap = im.idat_len;
+        scratch.clear();
+        if (int32_t st = file_head(d, scratch)) return st;
+    }
+    // the encoder's results stay on the device, in a buffer of the context (the job tables of the calls below take the arena in turn)
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (int32_t st = c->grow(c->d_file, c->file_cap, count * sizeof(spng_result), 4096)) return st;
+    }
+    spng_result *enc = (spng_result *)c->d_file;
+    for (uint32_t i = 0; i < count; ++i) fd[i].d_stream_result = enc + i;
+    // PNG.Encoder.pull end to end, then the chunks around its stream: one launch chain, no host wait in between
+    if (int32_t st = spng_encode_batch(c, images, level, count, enc, nullptr)) return st;
+    std::lock_guard<std::mutex> g(c->mu);
+    return write_files(c, fd.data(), count, d_results, h_results);
 }
 
 int32_t spng_crc32(spng_ctx *c, const void *data, uint64_t n, uint32_t *out)

@@ -400,6 +400,19 @@ class PNG:
             self._cursor += len(data)
             return data
 
+    @staticmethod
+    def compress(storage, size, depth, channels, indexed=False, bgr=False, interlaced=False, palette=None, key=None, fill=None,
+                 before=(), after=(), level=9, chunk_bytes=65544, session=None) -> bytes:
+        """PNG.Image.compress(stream:level:hint:) from storage (Sources/PNG/PNG.Image.swift:576-668): -> the bytes of the file, written
+        on the device by one spng_compress_batch call.  before / after: the metadata's chunks as (type, payload) pairs, in front of
+        PLTE / behind tRNS (the reference's cHRM gAMA sRGB iCCP sBIT, and hIST pHYs tIME iTXt sPLT and application chunks).
+        chunk_bytes: payload bytes of every IDAT but the last -- the reference cuts at twice the capacity its output buffer got
+        (LZ77.DeflatorOut.swift:15-24, 121), an allocator fact: 65544 at the default hint on Linux, 8200 at hint 4096."""
+        from . import load
+        s = session or load()
+        return s.compress(bytes(storage), size, depth, channels, level=level, indexed=indexed, bgr=bgr, interlaced=interlaced, palette=palette,
+                          key=key, fill=fill, before=before, after=after, chunk_bytes=chunk_bytes)
+
     class Context:
         """PNG.Context (Sources/PNG/Decoding/PNG.Context.swift:56-147), image side reduced to the
         fields that cross the boundary: size, pixel depth/channels, interlacing, standard."""

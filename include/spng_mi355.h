@@ -59,7 +59,24 @@ enum {
     SPNG_E_TRUNCATED_CHUNK_BODY = 83,          /* truncatedChunkBody(expected: aux0) */
     SPNG_E_CHUNK_TYPE = 84,                    /* invalidChunkTypeCode(aux0) */
     SPNG_E_CHUNK_CHECKSUM = 85,                /* invalidChunkChecksum(declared: aux0, computed: aux1) */
+    /* PNG.ParsingError, Sources/PNG/Parsing/PNG.ParsingError.swift: the cases PNG.Text.init(parsing:unicode:) and
+     * PNG.ColorProfile.init(parsing:) throw -- the head status of a spng_chunk_entry, payload in its aux */
+    SPNG_E_TEXT_KEYWORD = 96,                  /* invalidTextEnglishKeyword(String?): aux 0 = nil (no NUL in the chunk), 1 = the keyword payload[0 .. k) */
+    SPNG_E_TEXT_CHUNK_LENGTH = 97,             /* invalidTextChunkLength(length, min: aux) */
+    SPNG_E_TEXT_LANGUAGE = 98,                 /* invalidTextLanguageTag(String?): aux 0 = nil (no NUL behind the tag), else 1 + the payload
+                                                  offset of the first subtag that is not 1 ... 8 letters (it ends at the next '-' or at l) */
+    SPNG_E_TEXT_LOCALIZED_KEYWORD = 99,        /* invalidTextLocalizedKeyword */
+    SPNG_E_TEXT_COMPRESSION_METHOD = 100,      /* invalidTextCompressionMethodCode(aux) */
+    SPNG_E_TEXT_COMPRESSION = 101,             /* invalidTextCompressionCode(aux) */
+    SPNG_E_TEXT_INCOMPLETE = 102,              /* incompleteTextCompressedDatastream (host side: spng_inflate_batch answered
+                                                  SPNG_NEED_MORE_INPUT for the chunk's body) */
+    SPNG_E_PROFILE_NAME = 104,                 /* invalidColorProfileName(String?): aux as SPNG_E_TEXT_KEYWORD */
+    SPNG_E_PROFILE_CHUNK_LENGTH = 105,         /* invalidColorProfileChunkLength(length, min: aux) */
+    SPNG_E_PROFILE_COMPRESSION_METHOD = 106,   /* invalidColorProfileCompressionMethodCode(aux) */
+    SPNG_E_PROFILE_INCOMPLETE = 107,           /* incompleteColorProfileCompressedDatastream (host side, as SPNG_E_TEXT_INCOMPLETE) */
     /* boundary-level conditions with no reference counterpart */
+    SPNG_E_TEXT_ENCODING = 112,       /* spng_text_batch, SPNG_TEXT_CHECK_UTF8: the input is not well-formed UTF-8 (the reference repairs
+                                         such text silently: String(decoding:as:)) */
     SPNG_E_OUTPUT_CAPACITY = 64,      /* destination buffer too small */
     SPNG_E_ARGUMENT = 65,             /* bad argument (null pointer, depth/channels combination, ...) */
     SPNG_E_DEVICE = 66,               /* HIP error / no gfx950 device; see spng_last_error_string */
@@ -289,6 +306,64 @@ int32_t spng_lex_resume_batch(spng_ctx *ctx, const spng_file_desc *files, void *
 /* The most recent spng_lex_resume_batch, summed over its files: bytes that went through the CRC, IDAT bytes copied, chunk headers
  * walked.  Waits for the context's stream; any pointer may be NULL. */
 int32_t spng_lex_resume_stats(spng_ctx *ctx, uint64_t *summed, uint64_t *copied, uint64_t *headers);
+/* ---- files: the chunk directory, and the heads of the text and profile chunks ---------------------------------- */
+/* One chunk of a file's directory.  For tEXt, zTXt, iTXt and iCCP the head is parsed as PNG.Text.init(parsing:unicode:)
+ * (Parsing/PNG.Text.swift:110-200, with name(parsing:), validate(name:), language(parsing:), validate(language:), :202-301) and
+ * PNG.ColorProfile.init(parsing:) (Parsing/PNG.ColorProfile.swift:51-85) parse it, up to the body:
+ *     tEXt / zTXt   keyword 0 [0] body              a second NUL directly behind the keyword means compressed, whatever the type says (:181)
+ *     iTXt          keyword 0 C M language 0 localized-keyword 0 body
+ *     iCCP          name 0 M body
+ * k, l, m: payload offsets of the NUL that ends the keyword (name), the language tag, the localised keyword (SPNG_NO_OFFSET: not
+ * there, or not reached because of an earlier error -- errors are found in the reference's order).  A good head: status SPNG_DONE,
+ * body_off = where the zlib stream (compressed = 1) or the plain text starts; the language tag is payload[k + 3 .. l) as written
+ * (the reference lower-cases it: the host's business).  A bad head: one of SPNG_E_TEXT_* / SPNG_E_PROFILE_* with its payload in aux,
+ * body_off = 0.  Every other chunk type: status SPNG_DONE, k = l = m = SPNG_NO_OFFSET, body_off = 0.  A head's status is that
+ * chunk's only: the file's spng_lexed does not know of it. */
+#define SPNG_NO_OFFSET 0xffffffffu
+typedef struct spng_chunk_entry {
+    uint32_t type;                              /* the four characters, big-endian */
+    uint32_t length;                            /* payload bytes */
+    uint64_t offset;                            /* of the payload in the file */
+    int32_t  status;
+    uint32_t aux;
+    uint32_t k, l, m;
+    uint32_t body_off;                          /* in the payload */
+    uint8_t  compressed;
+    uint8_t  pad[7];                            /* zero */
+} spng_chunk_entry;
+typedef struct spng_chunk_dir {
+    spng_chunk_entry *d_entries;                /* device memory for `cap` entries (NULL with a cap of 0) */
+    uint32_t          cap;
+    uint32_t          reserved;                 /* zero */
+} spng_chunk_dir;
+/* spng_lex_batch with a directory: infos byte for byte what spng_lex_batch reports for the same files (and the same IDAT bytes), and
+ * dirs[i].d_entries[0 .. min(infos[i].chunks, cap)) filled, an entry per chunk lexed in full -- checksum verified, in front of the
+ * first failure in file order -- in file order; entries behind that stay untouched: a caller that sees chunks > cap calls again with
+ * more room.  Heads are parsed by a wave per chunk, the separators found by ballots over 64-byte loads. */
+int32_t spng_lex_dir_batch(spng_ctx *ctx, const spng_file_desc *files, const spng_chunk_dir *dirs, uint32_t count,
+                           spng_lexed *d_infos, spng_lexed *h_infos);
+
+/* ---- text: the byte work between a text chunk's body and a String ------------------------------------------------ */
+enum { SPNG_TEXT_LATIN1_TO_UTF8 = 1,  /* String(uncompressed.map{ Character(Unicode.Scalar($0)) }).utf8 (PNG.Text.swift:198): a byte >= 0x80
+                                         becomes (0xc0 | b >> 6, 0x80 | b & 0x3f) */
+       SPNG_TEXT_CHECK_UTF8 = 2 };    /* is the input well-formed UTF-8 (Unicode 15, table 3-7)?  Nothing is written */
+typedef struct spng_text_desc {
+    const void *d_in;   uint64_t len;           /* device pointers of any alignment */
+    void       *d_out;  uint64_t out_cap;       /* SPNG_TEXT_CHECK_UTF8: unused */
+    uint8_t     op;
+    uint8_t     reserved[7];                    /* zero */
+} spng_text_desc;
+/* Results.  SPNG_TEXT_LATIN1_TO_UTF8: SPNG_DONE, consumed = len, written = len + the number of bytes >= 0x80; or
+ * SPNG_E_OUTPUT_CAPACITY with written = the bytes needed, nothing written.  SPNG_TEXT_CHECK_UTF8: SPNG_DONE, consumed = len,
+ * written = 0; or SPNG_E_TEXT_ENCODING with aux[0] = the offset of the first ill-formed sequence and aux[1] = the number of bytes
+ * that begin one -- sequences as a decoder that replaces maximal subparts finds them (Unicode 15, 3.9, U+FFFD substitution; what
+ * Python's bytes.decode("utf-8", "replace") and Swift's String(decoding:as:) put a U+FFFD for): an overlong form, a surrogate, a
+ * value above U+10FFFF, a stray or missing continuation byte, a sequence the end cuts off.  The input goes in tiles of 4096 bytes --
+ * a count per tile, a scan over the tiles, the write --, so one long text runs on many workgroups.  A len of 0 is valid (and
+ * well-formed).  SPNG_E_ARGUMENT (the call): an unknown op, a non-zero reserved byte, a null input with a len, a null output with an
+ * out_cap (a null output with an out_cap of 0 asks for the bytes needed), input and output that overlap. */
+int32_t spng_text_batch(spng_ctx *ctx, const spng_text_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results);
+
 /* One zlib stream to cut into IDAT chunks of chunk_bytes payload bytes (the last one shorter). */
 typedef struct spng_chunking_desc {
     const void *d_stream; uint64_t len;

@@ -31,6 +31,13 @@ E_EXTRANEOUS_IMAGE_DATA, E_EXTRANEOUS_COMPRESSED_DATA, E_INCOMPLETE_DATASTREAM =
 E_OUTPUT_CAPACITY, E_ARGUMENT, E_DEVICE, E_REFERENCE_UNDEFINED = 64, 65, 66, 67
 (E_TRUNCATED_SIGNATURE, E_SIGNATURE, E_TRUNCATED_CHUNK_HEADER, E_TRUNCATED_CHUNK_BODY, E_CHUNK_TYPE,
  E_CHUNK_CHECKSUM) = range(80, 86)
+(E_TEXT_KEYWORD, E_TEXT_CHUNK_LENGTH, E_TEXT_LANGUAGE, E_TEXT_LOCALIZED_KEYWORD, E_TEXT_COMPRESSION_METHOD, E_TEXT_COMPRESSION,
+ E_TEXT_INCOMPLETE) = range(96, 103)
+E_PROFILE_NAME, E_PROFILE_CHUNK_LENGTH, E_PROFILE_COMPRESSION_METHOD, E_PROFILE_INCOMPLETE = range(104, 108)
+E_TEXT_ENCODING = 112
+NO_OFFSET = 0xffffffff
+TEXT_LATIN1_TO_UTF8, TEXT_CHECK_UTF8 = 1, 2
+TEXT_TILE = 4096                                            # csrc/text.hip: bytes of a tile (the tests place their boundaries by it)
 FORMAT_ZLIB, FORMAT_IOS, FORMAT_GZIP = 0, 1, 2
 K_INFLATE, K_UNFILTER, K_SCATTER, K_FILTER, K_DEFLATE, K_ADLER, K_PINFLATE = 0, 1, 2, 3, 4, 5, 6
 K_UNPACK = 7
@@ -73,6 +80,7 @@ EXPORTS = [
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
     "spng_lex_state_bytes", "spng_lex_resume_batch", "spng_lex_resume_stats",
     "spng_file_bound", "spng_write_file_batch", "spng_compress_batch",
+    "spng_lex_dir_batch", "spng_text_batch",
 ]
 
 
@@ -115,6 +123,21 @@ class Lexed(ctypes.Structure):
                 ("ios", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2), ("idat_len", ctypes.c_uint64),
                 ("plte_off", ctypes.c_uint64), ("trns_off", ctypes.c_uint64), ("plte_len", ctypes.c_uint32),
                 ("trns_len", ctypes.c_uint32), ("consumed", ctypes.c_uint64)]
+
+
+class ChunkEntry(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_uint32), ("length", ctypes.c_uint32), ("offset", ctypes.c_uint64), ("status", ctypes.c_int32),
+                ("aux", ctypes.c_uint32), ("k", ctypes.c_uint32), ("l", ctypes.c_uint32), ("m", ctypes.c_uint32),
+                ("body_off", ctypes.c_uint32), ("compressed", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 7)]
+
+
+class ChunkDir(ctypes.Structure):
+    _fields_ = [("d_entries", ctypes.c_void_p), ("cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class TextDesc(ctypes.Structure):
+    _fields_ = [("d_in", ctypes.c_void_p), ("len", ctypes.c_uint64), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_uint64),
+                ("op", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 7)]
 
 
 class UnpackDesc(ctypes.Structure):
@@ -252,6 +275,10 @@ class LexingError(SpngError):            # PNG.LexingError
     pass
 
 
+class ParsingError(SpngError):           # PNG.ParsingError (the cases of PNG.Text and PNG.ColorProfile)
+    pass
+
+
 _NAMES = {
     16: "invalidCompressionMethod", 17: "invalidWindowSize", 18: "invalidCheckBits", 19: "unexpectedDictionary",
     24: "invalidSigil", 25: "invalidCompressionMethod", 26: "invalidFlagBits", 27: "_headerChecksumUnsupported",
@@ -263,6 +290,10 @@ _NAMES = {
     66: "deviceError", 67: "referenceUndefined",
     80: "truncatedSignature", 81: "invalidSignature", 82: "truncatedChunkHeader", 83: "truncatedChunkBody",
     84: "invalidChunkTypeCode", 85: "invalidChunkChecksum",
+    96: "invalidTextEnglishKeyword", 97: "invalidTextChunkLength", 98: "invalidTextLanguageTag", 99: "invalidTextLocalizedKeyword",
+    100: "invalidTextCompressionMethodCode", 101: "invalidTextCompressionCode", 102: "incompleteTextCompressedDatastream",
+    104: "invalidColorProfileName", 105: "invalidColorProfileChunkLength", 106: "invalidColorProfileCompressionMethodCode",
+    107: "incompleteColorProfileCompressedDatastream", 112: "textEncoding",
 }
 
 
@@ -279,6 +310,8 @@ def raise_for(status, aux=(0, 0)):
         raise DecodingError(status, aux)
     if 80 <= status < 96:
         raise LexingError(status, aux)
+    if 96 <= status < 112:
+        raise ParsingError(status, aux)
     raise SpngError(status, aux)
 
 
@@ -338,6 +371,8 @@ def load_library():
     lib.spng_lex_batch.argtypes = [vp, ctypes.POINTER(FileDesc), u32, vp, ctypes.POINTER(Lexed)]
     lib.spng_lex_state_bytes.restype = u64
     lib.spng_lex_resume_batch.argtypes = [vp, ctypes.POINTER(FileDesc), ctypes.POINTER(vp), u32, vp, ctypes.POINTER(Lexed)]
+    lib.spng_lex_dir_batch.argtypes = [vp, ctypes.POINTER(FileDesc), ctypes.POINTER(ChunkDir), u32, vp, ctypes.POINTER(Lexed)]
+    lib.spng_text_batch.argtypes = [vp, ctypes.POINTER(TextDesc), u32, vp, rp]
     lib.spng_lex_resume_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.spng_write_idat_batch.argtypes = [vp, ctypes.POINTER(ChunkingDesc), u32, vp, rp]
     lib.spng_crc32.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
@@ -731,6 +766,47 @@ class Session:
         infos = (Lexed * n)()
         _check(self.lib, self.lib.spng_lex_batch(self.ctx, descs, n, None, infos))
         return list(infos), [bytes(b[:r.idat_len].cpu().numpy()) for b, r in zip(d_idat, infos)]
+
+    def lex_dir_batch(self, files, caps=None, d_png=None, device_idat=False):
+        """lex_batch with a chunk directory (spng_lex_dir_batch).  files: list of PNG file bytes; caps: entries of room per file
+        (None: what a file of its length can hold at most); d_png: the files as device tensors, if they are there already.
+        -> (list[Lexed], list of IDAT payloads -- bytes, or with device_idat the device tensors they were written to --, list of
+        list[ChunkEntry]: the first min(chunks, cap) entries of each file)"""
+        n = len(files)
+        d_png = d_png or [self.to_device(f) for f in files]
+        d_idat = [self.empty(len(f)) for f in files]
+        caps = [len(f) // 12 for f in files] if caps is None else [int(c) for c in caps]
+        sz = ctypes.sizeof(ChunkEntry)
+        d_ent = [self.torch.full((max(c, 1) * sz,), 0xEE, dtype=self.torch.uint8, device=self.tdev) for c in caps]
+        descs, dirs = (FileDesc * max(n, 1))(), (ChunkDir * max(n, 1))()
+        for i, (f, a, b) in enumerate(zip(files, d_png, d_idat)):
+            descs[i] = FileDesc(self._ptr(a), len(f), self._ptr(b), len(f))
+            dirs[i] = ChunkDir(d_ent[i].data_ptr() if caps[i] else None, caps[i], 0)
+        infos = (Lexed * max(n, 1))()
+        _check(self.lib, self.lib.spng_lex_dir_batch(self.ctx, descs, dirs, n, None, infos))
+        entries = []
+        for r, c, e in zip(infos, caps, d_ent):
+            k = min(r.chunks, c)
+            raw = bytes(e[:k * sz].cpu().numpy())
+            entries.append(list((ChunkEntry * k).from_buffer_copy(raw)))
+        idats = d_idat if device_idat else [bytes(b[:r.idat_len].cpu().numpy()) for b, r in zip(d_idat, infos)]
+        return list(infos)[:n], idats, entries
+
+    def text_batch(self, texts, op, out_caps=None):
+        """spng_text_batch over device tensors (or bytes, which are uploaded).  op: TEXT_LATIN1_TO_UTF8 / TEXT_CHECK_UTF8, one or a list;
+        out_caps: capacities of the outputs (None: twice the input, which always fits).  -> (list of output tensors -- None for a
+        check --, list[Result])"""
+        n = len(texts)
+        ts = [self.to_device(t) if isinstance(t, (bytes, bytearray, memoryview)) else t for t in texts]
+        outs, descs = [], (TextDesc * max(n, 1))()
+        for i, t in enumerate(ts):
+            o = pick(op, i)
+            cap = 0 if o == TEXT_CHECK_UTF8 else 2 * t.numel() if out_caps is None else int(out_caps[i])
+            outs.append(None if o == TEXT_CHECK_UTF8 else self.empty(cap))
+            descs[i] = TextDesc(self._ptr(t), t.numel(), self._ptr(outs[-1]) if outs[-1] is not None else None, cap, o, (ctypes.c_uint8 * 7)())
+        res = (Result * max(n, 1))()
+        _check(self.lib, self.lib.spng_text_batch(self.ctx, descs, n, None, res))
+        return outs, list(res)[:n]
 
     def lex_states(self, count=1):
         """`count` states for lex_resume_batch: spng_lex_state_bytes() zero bytes of device memory each, one per file, kept by the

@@ -70,6 +70,18 @@ const char *spng_status_string(int32_t s)
     case SPNG_E_ARGUMENT: return "invalid argument";
     case SPNG_E_DEVICE: return "device error";
     case SPNG_E_REFERENCE_UNDEFINED: return "stream uses a distance code the reference leaves undefined";
+    case SPNG_E_TEXT_KEYWORD: return "invalid english keyword in text chunk";
+    case SPNG_E_TEXT_CHUNK_LENGTH: return "text chunk shorter than its head";
+    case SPNG_E_TEXT_LANGUAGE: return "invalid language tag in text chunk";
+    case SPNG_E_TEXT_LOCALIZED_KEYWORD: return "localized keyword of text chunk has no terminator";
+    case SPNG_E_TEXT_COMPRESSION_METHOD: return "invalid compression method code in text chunk";
+    case SPNG_E_TEXT_COMPRESSION: return "invalid compression code in text chunk";
+    case SPNG_E_TEXT_INCOMPLETE: return "compressed datastream of text chunk is incomplete";
+    case SPNG_E_PROFILE_NAME: return "invalid color profile name";
+    case SPNG_E_PROFILE_CHUNK_LENGTH: return "color profile chunk shorter than its head";
+    case SPNG_E_PROFILE_COMPRESSION_METHOD: return "invalid compression method code in color profile chunk";
+    case SPNG_E_PROFILE_INCOMPLETE: return "compressed datastream of color profile chunk is incomplete";
+    case SPNG_E_TEXT_ENCODING: return "text is not well-formed utf-8";
     case SPNG_E_GZIP_SIGIL: return "invalid gzip sigil";
     case SPNG_E_GZIP_METHOD: return "invalid gzip compression method";
     case SPNG_E_GZIP_FLAG_BITS: return "invalid gzip flag bits";

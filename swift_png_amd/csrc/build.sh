@@ -6,7 +6,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=${SPNG_OUT:-../libspng_mi355.so}
 OBJ=${SPNG_OBJ:-build}
-SRCS="api.hip host_decode.hip host_encode.hip host_colour.hip host_files.hip unfilter.hip inflate.hip pinflate2.hip encode.hip deflate.hip unpack.hip alpha.hip hsva.hip luminance.hip indexing.hip colour_tables.hip chunks.hip gzip.hip"
+SRCS="api.hip host_decode.hip host_encode.hip host_colour.hip host_files.hip unfilter.hip inflate.hip pinflate2.hip encode.hip deflate.hip unpack.hip alpha.hip hsva.hip luminance.hip indexing.hip colour_tables.hip chunks.hip text.hip gzip.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function ${SPNG_EXTRA_FLAGS:-}"
 HDRS="common.hpp geometry.hpp scanline.hpp host.hpp alpha.hpp indexing.hpp hsva.hpp luminance.hpp huffman.hpp crc32.hpp file_head.hpp ../../include/spng_mi355.h build.sh"
 mkdir -p "$OBJ"

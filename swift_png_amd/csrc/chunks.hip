@@ -193,6 +193,152 @@ __global__ void lex_finish_kernel(spng_lexed *__restrict__ out, const LexChunk *
     out[i] = r;
 }
 
+// ---- the chunk directory (spng_lex_dir_batch) -------------------------------------------------------------------------------
+// Behind the three kernels above, which it leaves as they are: `dir_list_kernel`, a wave per file, writes an entry per chunk lexed
+// in full (lex_finish_kernel's `chunks`) -- the listed ones from the list, a lane each; the ones the walking wave handled itself once
+// the list was full by walking their headers again from the last listed chunk on (every one of them has been checked against the
+// file's length by the walk).  `dir_head_kernel`, a wave per entry, parses the heads of tEXt / zTXt / iTXt / iCCP:
+//   PNG.Text.init(parsing:unicode:)     Sources/PNG/Parsing/PNG.Text.swift:110-200
+//   name(parsing:), validate(name:)     :202-251       language(parsing:), validate(language:)    :254-301
+//   PNG.ColorProfile.init(parsing:)     Sources/PNG/Parsing/PNG.ColorProfile.swift:51-85  (up to the inflator)
+// The separators are found 64 bytes at a time: a byte per lane, a ballot, the first set bit.
+static constexpr uint32_t T_tEXt = 0x74455874, T_zTXt = 0x7a545874, T_iTXt = 0x69545874, T_iCCP = 0x69434350;
+
+// the first NUL of payload[from, to), or SPNG_NO_OFFSET
+__device__ __forceinline__ uint32_t find_nul(const gbyte *payload, uint32_t from, uint32_t to, int lane)
+{
+    for (uint64_t base = from; base < to; base += 64) {
+        const uint64_t i = base + lane;
+        const unsigned long long hit = __ballot(i < to && payload[i] == 0);
+        if (hit) return (uint32_t)base + (uint32_t)__ffsll((long long)hit) - 1;
+    }
+    return SPNG_NO_OFFSET;
+}
+
+// validate(name:) over payload[0, k) (:226-251): 1 ... 80 scalars of 0x20 ... 0x7d or 0xa1 ... 0xff, no leading, trailing or doubled space
+__device__ __forceinline__ bool valid_keyword(const gbyte *payload, uint32_t k, int lane)
+{
+    if (k < 1 || k > 80) return false;
+    bool bad = false;
+    for (uint32_t i = lane; i < k; i += 64) {
+        const uint32_t c = payload[i], prev = payload[i ? i - 1 : 0];
+        bad = bad || !((c >= 0x20 && c <= 0x7d) || c >= 0xa1) || (prev == 0x20 && c == 0x20) || (i == k - 1 && c == 0x20);
+    }
+    return __ballot(bad) == 0;
+}
+
+// language(parsing:) over payload[from, l), l > from (:254-301): subtags between '-' of 1 ... 8 letters each.  -> the payload offset of
+// the first subtag that is none, or SPNG_NO_OFFSET.  The start of the subtag a position lies in never decreases along the tag, so the
+// first position that breaks a rule names the first bad subtag.
+__device__ __forceinline__ uint32_t bad_subtag(const gbyte *payload, uint32_t from, uint32_t l, int lane)
+{
+    uint32_t start = from;                                     // of the subtag in progress where the 64 bytes begin
+    for (uint64_t base = from; base <= l; base += 64) {
+        const uint64_t i = base + lane;
+        const uint32_t c = i < l ? payload[i] : 0x2d;          // (the NUL ends the last subtag as a '-' ends the others)
+        const bool in = i <= l, dash = in && c == 0x2d;
+        const unsigned long long dashes = __ballot(dash), below = dashes & ((1ull << lane) - 1);
+        const uint32_t mine = below ? (uint32_t)base + 64 - (uint32_t)__clzll((long long)below) : start;
+        const bool letter = (c | 0x20) >= 0x61 && (c | 0x20) <= 0x7a;
+        const bool fails = in && (dash ? (uint32_t)i == mine : !letter || (uint32_t)i - mine >= 8);
+        const unsigned long long failed = __ballot(fails);
+        if (failed) return (uint32_t)__shfl((int)mine, __ffsll((long long)failed) - 1);
+        if (dashes) start = (uint32_t)base + 64 - (uint32_t)__clzll((long long)dashes);
+    }
+    return SPNG_NO_OFFSET;
+}
+
+struct Head { int32_t status; uint32_t aux, k, l, m, body_off, compressed; };
+__device__ __forceinline__ Head parse_head(uint32_t name, const gbyte *payload, uint32_t length, int lane)
+{
+    Head h;
+    h.status = SPNG_DONE; h.aux = 0; h.k = h.l = h.m = SPNG_NO_OFFSET; h.body_off = 0; h.compressed = 0;
+    const bool profile = name == T_iCCP;
+    const uint32_t k = find_nul(payload, 0, length, lane);
+    if (k != SPNG_NO_OFFSET) h.k = k;
+    if (k == SPNG_NO_OFFSET || !valid_keyword(payload, k, lane)) {
+        h.status = profile ? SPNG_E_PROFILE_NAME : SPNG_E_TEXT_KEYWORD; h.aux = k != SPNG_NO_OFFSET;
+        return h;
+    }
+    if (profile) {
+        if ((uint64_t)k + 1 >= length) { h.status = SPNG_E_PROFILE_CHUNK_LENGTH; h.aux = k + 2; return h; }
+        if (payload[k + 1] != 0) { h.status = SPNG_E_PROFILE_COMPRESSION_METHOD; h.aux = payload[k + 1]; return h; }
+        h.compressed = 1; h.body_off = k + 2;
+        return h;
+    }
+    if (name != T_iTXt) {
+        // the one Latin-1 path of tEXt and zTXt: a second NUL means compressed (:181)
+        h.compressed = (uint64_t)k + 1 < length && payload[k + 1] == 0;
+        h.body_off = k + 1 + h.compressed;
+        return h;
+    }
+    if ((uint64_t)k + 2 >= length) { h.status = SPNG_E_TEXT_CHUNK_LENGTH; h.aux = k + 3; return h; }
+    const uint32_t l = find_nul(payload, k + 3, length, lane);
+    if (l == SPNG_NO_OFFSET) { h.status = SPNG_E_TEXT_LANGUAGE; return h; }
+    h.l = l;
+    if (l > k + 3) {
+        const uint32_t bad = bad_subtag(payload, k + 3, l, lane);
+        if (bad != SPNG_NO_OFFSET) { h.status = SPNG_E_TEXT_LANGUAGE; h.aux = 1 + bad; return h; }
+    }
+    const uint32_t m = find_nul(payload, l + 1, length, lane);
+    if (m == SPNG_NO_OFFSET) { h.status = SPNG_E_TEXT_LOCALIZED_KEYWORD; return h; }
+    h.m = m;
+    const uint32_t flag = payload[k + 1], method = payload[k + 2];
+    if (flag == 1 && method != 0) { h.status = SPNG_E_TEXT_COMPRESSION_METHOD; h.aux = method; return h; }
+    if (flag > 1) { h.status = SPNG_E_TEXT_COMPRESSION; h.aux = flag; return h; }
+    h.compressed = flag; h.body_off = m + 1;
+    return h;
+}
+
+__global__ __launch_bounds__(64) void dir_list_kernel(const spng_file_desc *__restrict__ files, const spng_chunk_dir *__restrict__ dirs,
+                                                      const spng_lexed *__restrict__ out, const LexChunk *__restrict__ table,
+                                                      const uint64_t *__restrict__ table_at, const LexWalk *__restrict__ walks)
+{
+    const int lane = threadIdx.x;
+    const uint32_t file = blockIdx.x;
+    const uint32_t chunks = UNI(out[file].chunks), cap = UNI(dirs[file].cap);
+    const uint32_t n = chunks < cap ? chunks : cap, listed = UNI(walks[file].listed);
+    spng_chunk_entry *entries = (spng_chunk_entry *)uni64((uint64_t)dirs[file].d_entries);
+    const LexChunk *list = table + uni64(table_at[file]);
+    spng_chunk_entry e;
+    memset(&e, 0, sizeof e);
+    e.status = SPNG_DONE; e.k = e.l = e.m = SPNG_NO_OFFSET;
+    const uint32_t from_list = n < listed ? n : listed;
+    for (uint32_t i = lane; i < from_list; i += 64) {
+        e.type = list[i].name; e.length = list[i].length; e.offset = list[i].off + 8;
+        entries[i] = e;
+    }
+    if (n <= listed) return;
+    // the list was full: the headers behind it once more, the serial way
+    const gbyte *p = (const gbyte *)uni64((uint64_t)files[file].d_png);
+    uint64_t off = listed ? uni64(list[listed - 1].off) + 12 + UNI(list[listed - 1].length) : 8;
+    for (uint32_t i = listed; i < n; ++i) {
+        e.length = be32(p + off); e.type = be32(p + off + 4); e.offset = off + 8;
+        if (lane == 0) entries[i] = e;
+        off += 12 + (uint64_t)e.length;
+    }
+}
+
+__global__ __launch_bounds__(64) void dir_head_kernel(const spng_file_desc *__restrict__ files, const spng_chunk_dir *__restrict__ dirs,
+                                                      const spng_lexed *__restrict__ out)
+{
+    const int lane = threadIdx.x;
+    const uint32_t file = blockIdx.y;
+    const uint32_t chunks = UNI(out[file].chunks), cap = UNI(dirs[file].cap);
+    const uint32_t n = chunks < cap ? chunks : cap;
+    spng_chunk_entry *entries = (spng_chunk_entry *)uni64((uint64_t)dirs[file].d_entries);
+    const gbyte *p = (const gbyte *)uni64((uint64_t)files[file].d_png);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint32_t name = UNI(entries[i].type), length = UNI(entries[i].length);
+        if (name != T_tEXt && name != T_zTXt && name != T_iTXt && name != T_iCCP) continue;
+        const Head h = parse_head(name, p + uni64(entries[i].offset), length, lane);
+        if (lane == 0) {
+            spng_chunk_entry &e = entries[i];
+            e.status = h.status; e.aux = h.aux; e.k = h.k; e.l = h.l; e.m = h.m; e.body_off = h.body_off; e.compressed = (uint8_t)h.compressed;
+        }
+    }
+}
+
 // ---- files that arrive in pieces (spng_lex_resume_batch) --------------------------------------------------------------------
 // The reference's OnlineDecoding tutorial (Snippets/PNG/OnlineDecoding.swift) retries signature() and chunk() on truncatedSignature /
 // truncatedChunkHeader / truncatedChunkBody until the bytes are there.  Here the loop's state lives on the device between the pushes:
@@ -662,6 +808,17 @@ hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed 
     if (e != hipSuccess) return e;
     lex_finish_kernel<<<(count + 63) / 64, 64, 0, stream>>>(d_out, (const LexChunk *)d_table, d_table_at, (const LexWalk *)d_walks, d_files, count);
     return hipGetLastError();
+}
+// behind launch_lex on the same stream.  most_entries: the most entries a file of the call can get
+hipError_t launch_lex_dir(const spng_file_desc *d_files, const spng_chunk_dir *d_dirs, uint32_t count, const spng_lexed *d_out, const void *d_table,
+                          const uint64_t *d_table_at, const void *d_walks, uint32_t most_entries, hipStream_t stream)
+{
+    if (!count || !most_entries) return hipSuccess;
+    dir_list_kernel<<<count, 64, 0, stream>>>(d_files, d_dirs, d_out, (const LexChunk *)d_table, d_table_at, (const LexWalk *)d_walks);
+    const uint32_t bx = lex_piece_blocks_x(count, most_entries);
+    return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+        dir_head_kernel<<<dim3(bx, ny), 64, 0, stream>>>(d_files + y0, d_dirs + y0, d_out + y0);
+    });
 }
 size_t lex_state_bytes() { return sizeof(LexState); }
 size_t lex_piece_bytes() { return sizeof(LexPiece); }

@@ -207,6 +207,18 @@ struct FileJob {
     uint64_t       head_len, len, stream_cap, out_cap, chunk_bytes;
 };
 
+// One text to transcode or check (text.hip)
+struct TextJob {
+    const uint8_t *in;
+    uint8_t       *out;
+    uint64_t       len, out_cap;
+    uint64_t       tiles;         // of TEXT_TILE bytes
+    uint32_t      *counts;        // call scratch, per tile: bytes >= 0x80 / ill-formed sequences that begin in it,
+    uint32_t      *firsts;        // ... the first of those in the tile (check only),
+    uint64_t      *offs;          // ... where its output starts (transcode only)
+    uint8_t        op, pad[7];    // spng_text_desc.op
+};
+
 struct InflateJob {
     const uint8_t *src;
     uint8_t       *dst;
@@ -470,6 +482,11 @@ size_t lex_chunk_bytes();
 size_t lex_walk_bytes();
 hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed *d_out, void *d_table, const uint64_t *d_table_at,
                       void *d_walks, uint32_t max_listed, hipStream_t stream);
+hipError_t launch_lex_dir(const spng_file_desc *d_files, const spng_chunk_dir *d_dirs, uint32_t count, const spng_lexed *d_out, const void *d_table,
+                          const uint64_t *d_table_at, const void *d_walks, uint32_t most_entries, hipStream_t stream);
+size_t text_tiles(uint64_t len);
+// blocks_x: workgroups along x of the per-tile kernels (0: no text of the call has a tile); writes: some text is transcoded
+hipError_t launch_text(const TextJob *d_jobs, uint32_t count, uint32_t blocks_x, bool writes, spng_result *d_results, hipStream_t stream);
 size_t lex_state_bytes();
 size_t lex_piece_bytes();
 size_t lex_rwalk_bytes();

@@ -52,9 +52,10 @@ static int32_t write_files(spng_ctx *c, const spng_png_desc *descs, uint32_t cou
     return read_back(c, h_results, dr, count * sizeof(spng_result));
 }
 
-// Both lexer entries.  d_states: a state per file (files that arrive in pieces: the call's counters go to c->h_lex_stats), or null:
-// whole files
-static int32_t lex_batch(spng_ctx *c, const spng_file_desc *files, void *const *d_states, uint32_t count, spng_lexed *d_infos, spng_lexed *h_infos)
+// The lexer entries.  d_states: a state per file (files that arrive in pieces: the call's counters go to c->h_lex_stats), or null:
+// whole files -- with `dirs`, a chunk directory per file behind the lexer's own kernels
+static int32_t lex_batch(spng_ctx *c, const spng_file_desc *files, void *const *d_states, uint32_t count, spng_lexed *d_infos, spng_lexed *h_infos,
+                         const spng_chunk_dir *dirs = nullptr)
 {
     if (!c || (!files && count) || (!d_infos && !h_infos && count)) return SPNG_E_ARGUMENT;
     if (!count) return SPNG_DONE;
@@ -72,9 +73,15 @@ static int32_t lex_batch(spng_ctx *c, const spng_file_desc *files, void *const *
         at[i + 1] = at[i] + k;
         max_listed = k > max_listed ? (uint32_t)k : max_listed;
     }
+    uint32_t most_entries = 0;                                 // (no chunk is shorter than 12 bytes)
+    for (uint32_t i = 0; dirs && i < count; ++i) {
+        if ((!dirs[i].d_entries && dirs[i].cap) || ((uintptr_t)dirs[i].d_entries & 7) || dirs[i].reserved) return SPNG_E_ARGUMENT;
+        most_entries = std::max(most_entries, (uint32_t)std::min<uint64_t>(dirs[i].cap, files[i].len / 12));
+    }
     const size_t walk_bytes = d_states ? lex_rwalk_bytes() : lex_walk_bytes();
     const size_t table_bytes = (size_t)at[count] * (d_states ? lex_piece_bytes() : lex_chunk_bytes());
-    if (int32_t st = c->reserve(count * (sizeof(spng_file_desc) + sizeof(spng_lexed) + 16 + walk_bytes) + table_bytes + 4096)) return st;
+    if (int32_t st = c->reserve(count * (sizeof(spng_file_desc) + sizeof(spng_lexed) + 16 + walk_bytes + (dirs ? sizeof(spng_chunk_dir) : 0)) + table_bytes + 4096))
+        return st;
     Arena a{c};
     const size_t fslot = a.take(count * sizeof(spng_file_desc));
     for (uint32_t i = 0; i < count; ++i) a.host<spng_file_desc>(fslot)[i] = files[i];
@@ -87,6 +94,8 @@ static int32_t lex_batch(spng_ctx *c, const spng_file_desc *files, void *const *
         cslot = a.take(32);                                    // the call's counters, zeroed by the upload
         memset(a.host<uint64_t>(cslot), 0, 32);
     }
+    const size_t dslot = dirs ? a.take(count * sizeof(spng_chunk_dir)) : 0;
+    if (dirs) memcpy(a.host<spng_chunk_dir>(dslot), dirs, count * sizeof(spng_chunk_dir));
     const size_t upload = a.off;
     const size_t oslot = a.take(count * sizeof(spng_lexed));
     const size_t wslot = a.take(count * walk_bytes);
@@ -101,6 +110,9 @@ static int32_t lex_batch(spng_ctx *c, const spng_file_desc *files, void *const *
         else
             HIP_TRY(launch_lex(a.dev<spng_file_desc>(fslot), count, dout, a.dev<uint8_t>(tslot), a.dev<uint64_t>(atslot), a.dev<uint8_t>(wslot),
                                max_listed, c->stream));
+        if (dirs)
+            HIP_TRY(launch_lex_dir(a.dev<spng_file_desc>(fslot), a.dev<spng_chunk_dir>(dslot), count, dout, a.dev<uint8_t>(tslot),
+                                   a.dev<uint64_t>(atslot), a.dev<uint8_t>(wslot), most_entries, c->stream));
     }
     if (d_states) HIP_TRY(hipMemcpyAsync(c->h_lex_stats, a.dev<uint64_t>(cslot), 24, hipMemcpyDeviceToHost, c->stream));
     return read_back(c, h_infos, dout, count * sizeof(spng_lexed));
@@ -111,6 +123,13 @@ extern "C" {
 int32_t spng_lex_batch(spng_ctx *c, const spng_file_desc *files, uint32_t count, spng_lexed *d_infos, spng_lexed *h_infos)
 {
     return lex_batch(c, files, nullptr, count, d_infos, h_infos);
+}
+
+int32_t spng_lex_dir_batch(spng_ctx *c, const spng_file_desc *files, const spng_chunk_dir *dirs, uint32_t count, spng_lexed *d_infos,
+                           spng_lexed *h_infos)
+{
+    if (!dirs && count) return SPNG_E_ARGUMENT;
+    return lex_batch(c, files, nullptr, count, d_infos, h_infos, dirs);
 }
 
 uint64_t spng_lex_state_bytes(void) { return lex_state_bytes(); }
@@ -201,6 +220,53 @@ int32_t spng_compress_batch(spng_ctx *c, const spng_image_desc *images, const sp
     if (int32_t st = spng_encode_batch(c, images, level, count, enc, nullptr)) return st;
     std::lock_guard<std::mutex> g(c->mu);
     return write_files(c, fd.data(), count, d_results, h_results);
+}
+
+int32_t spng_text_batch(spng_ctx *c, const spng_text_desc *descs, uint32_t count, spng_result *d_results, spng_result *h_results)
+{
+    if (!c || (!descs && count) || (!d_results && !h_results && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t tiles = 0, most = 0;
+    bool writes = false;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_text_desc &d = descs[i];
+        const bool transcode = d.op == SPNG_TEXT_LATIN1_TO_UTF8;
+        if ((!transcode && d.op != SPNG_TEXT_CHECK_UTF8) || (d.len && !d.d_in) || d.len > (~0ull >> 2)) return SPNG_E_ARGUMENT;
+        for (uint8_t r : d.reserved) if (r) return SPNG_E_ARGUMENT;
+        if (transcode && d.len) {
+            const uintptr_t in = (uintptr_t)d.d_in, out = (uintptr_t)d.d_out;
+            if ((!out && d.out_cap) || (in < out + d.out_cap && out < in + d.len)) return SPNG_E_ARGUMENT;   // (no room at all: the bytes needed come back)
+        }
+        writes = writes || transcode;
+        tiles += text_tiles(d.len);
+        most = std::max<uint64_t>(most, text_tiles(d.len));
+    }
+    if (int32_t st = c->reserve(count * (sizeof(TextJob) + sizeof(spng_result)) + 16 * tiles + 4096)) return st;
+    Arena a{c};
+    const size_t jslot = a.take(count * sizeof(TextJob));
+    const size_t upload = a.off;
+    const size_t rslot = a.take(count * sizeof(spng_result));
+    const size_t oslot = a.take(8 * tiles), cslot = a.take(4 * tiles), fslot = a.take(4 * tiles);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const spng_text_desc &d = descs[i];
+        TextJob j{};
+        j.in = (const uint8_t *)d.d_in; j.out = (uint8_t *)d.d_out; j.len = d.len; j.out_cap = d.out_cap; j.op = d.op;
+        j.tiles = text_tiles(d.len);
+        j.offs = a.dev<uint64_t>(oslot) + at; j.counts = a.dev<uint32_t>(cslot) + at; j.firsts = a.dev<uint32_t>(fslot) + at;
+        at += j.tiles;
+        a.host<TextJob>(jslot)[i] = j;
+    }
+    if (int32_t st = c->upload(0, upload)) return st;
+    spng_result *dr = d_results ? d_results : a.dev<spng_result>(rslot);
+    {
+        Timed t(c, SPNG_K_LEX);
+        HIP_TRY(launch_text(a.dev<TextJob>(jslot), count, most ? lex_piece_blocks_x(count, (uint32_t)std::min<uint64_t>(most, 1u << 20)) : 0, writes, dr,
+                            c->stream));
+    }
+    return read_back(c, h_results, dr, count * sizeof(spng_result));
 }
 
 int32_t spng_crc32(spng_ctx *c, const void *data, uint64_t n, uint32_t *out)

@@ -8,12 +8,171 @@ inflated bytes so far, and the point (a block boundary) from which the next push
 """
 from __future__ import annotations
 
+import struct
+
 from . import (DONE, FORMAT_GZIP, FORMAT_IOS, FORMAT_ZLIB, NEED_MORE_INPUT, DecodingError, SpngError,
                E_EXTRANEOUS_COMPRESSED_DATA, E_INCOMPLETE_DATASTREAM, E_OUTPUT_CAPACITY, IMAGE_OVERDRAW,
                HSVA_FROM_RGBA8, HSVA_TO_RGBA8, HSVA_TO_VA8, LUMINANCE_V8, LUMINANCE_VA8, PREMULTIPLY, PREMULTIPLY_AS_U8, STRAIGHTEN, STRAIGHTEN_AS_U8, TARGET_RGBA,
                TARGET_VA)
 
 _DELAY_FORMATS = {1: (8, 1), 2: (8, 2), 3: (8, 3), 4: (8, 4), 6: (16, 3), 8: (16, 4)}
+
+
+class ChunkOrderError(Exception):
+    """The cases of PNG.DecodingError about which chunks a file holds and in which order: the host's business"""
+
+
+class RequiredChunk(ChunkOrderError):
+    """PNG.DecodingError.required(chunk:before:)"""
+
+    def __init__(self, chunk, before):
+        self.chunk, self.before = chunk, before
+        super().__init__(f"required({chunk}, before: {before})")
+
+
+class DuplicateChunk(ChunkOrderError):
+    """PNG.DecodingError.duplicate(chunk:)"""
+
+    def __init__(self, chunk):
+        self.chunk = chunk
+        super().__init__(f"duplicate({chunk})")
+
+
+class UnexpectedChunk(ChunkOrderError):
+    """PNG.DecodingError.unexpected(chunk:after:)"""
+
+    def __init__(self, chunk, after):
+        self.chunk, self.after = chunk, after
+        super().__init__(f"unexpected({chunk}, after: {after})")
+
+
+def _name(type_code: int) -> str:
+    return struct.pack(">I", type_code).decode("latin-1")
+
+
+_BEFORE_PLTE = ("cHRM", "gAMA", "sRGB", "iCCP", "sBIT")
+# the fields of PNG.Metadata by chunk type: (attribute, typed)
+_UNIQUE = {"cHRM": "chromaticity", "gAMA": "gamma", "sRGB": "colorRendering", "iCCP": "colorProfile", "sBIT": "significantBits",
+           "hIST": "histogram", "pHYs": "physicalDimensions", "tIME": "time"}
+
+
+class Text:
+    """PNG.Text (Sources/PNG/Parsing/PNG.Text.swift:6-99): compressed, keyword (english, localized), language, content"""
+
+    def __init__(self, compressed, keyword, language, content):
+        self.compressed, self.keyword, self.language, self.content = bool(compressed), tuple(keyword), list(language), content
+
+    def __eq__(self, other):
+        return isinstance(other, Text) and vars(self) == vars(other)
+
+    def __repr__(self):
+        return f"Text(compressed={self.compressed}, keyword={self.keyword}, language={self.language}, content=<{len(self.content)} characters>)"
+
+    def head(self) -> bytes:
+        """`serialized` up to the content (:317-332)"""
+        english, localized = self.keyword
+        return (english.encode("latin-1") + b"\0" + bytes([1 if self.compressed else 0, 0]) +
+                b"-".join(t.encode("latin-1") for t in self.language) + b"\0" +
+                (localized.encode("utf-8") if localized != english else b"") + b"\0")
+
+
+class ColorProfile:
+    """PNG.ColorProfile (Sources/PNG/Parsing/PNG.ColorProfile.swift:5-44): name, profile"""
+
+    def __init__(self, name, profile):
+        self.name, self.profile = name, bytes(profile)
+
+    def __eq__(self, other):
+        return isinstance(other, ColorProfile) and vars(self) == vars(other)
+
+
+class Metadata:
+    """PNG.Metadata (Sources/PNG/Decoding/PNG.Metadata.swift:5-95).  Typed: time -- (year, month, day, hour, minute, second),
+    PNG.TimeModified --, gamma -- the numerator over 100000, PNG.Gamma --, physicalDimensions -- (x, y, unit byte),
+    PNG.PhysicalDimensions --, colorProfile -- ColorProfile --, text -- [Text].  Carried as their payload bytes, uninterpreted:
+    chromaticity, colorRendering, significantBits, histogram, suggestedPalettes (a list of payloads) and application (a list of
+    (type, payload))."""
+
+    def __init__(self, time=None, chromaticity=None, colorProfile=None, colorRendering=None, gamma=None, histogram=None,
+                 physicalDimensions=None, significantBits=None, suggestedPalettes=(), text=(), application=()):
+        self.time, self.chromaticity, self.colorProfile, self.colorRendering = time, chromaticity, colorProfile, colorRendering
+        self.gamma, self.histogram, self.physicalDimensions, self.significantBits = gamma, histogram, physicalDimensions, significantBits
+        self.suggestedPalettes, self.text, self.application = list(suggestedPalettes), list(text), list(application)
+
+    def push(self, chunk, palette_seen=False, parsed=None):
+        """push(ancillary:pixel:palette:background:transparency:) (PNG.Metadata.swift:151-245) for every chunk but bKGD and tRNS,
+        which are the format's: chunk = (type, payload); parsed: the Text or ColorProfile of a text or profile chunk, which the
+        device has taken apart (PNG.decompress).  Raises UnexpectedChunk for cHRM gAMA sRGB iCCP sBIT behind PLTE (:159-164),
+        RequiredChunk for hIST without PLTE (:190-194), DuplicateChunk for a second one of the unique chunks (:98-108)."""
+        kind, payload = chunk
+        if kind in ("CgBI", "IHDR", "PLTE", "IDAT", "IEND", "bKGD", "tRNS"):
+            raise ValueError(f"Metadata.push cannot be used with chunk type '{kind}'")       # (:166-170: fatalError)
+        if kind in _BEFORE_PLTE and palette_seen:
+            raise UnexpectedChunk(kind, "PLTE")
+        if kind == "hIST" and not palette_seen:
+            raise RequiredChunk("PLTE", "hIST")
+        if kind in _UNIQUE:
+            if getattr(self, _UNIQUE[kind]) is not None:
+                raise DuplicateChunk(kind)
+            if kind == "gAMA":                                   # PNG.Gamma.init(parsing:): one big-endian UInt32
+                value = struct.unpack(">I", payload)[0]
+            elif kind == "pHYs":                                 # PNG.PhysicalDimensions.init(parsing:): x, y, unit
+                value = struct.unpack(">IIB", payload)
+            elif kind == "tIME":                                 # PNG.TimeModified.init(parsing:)
+                value = struct.unpack(">HBBBBB", payload)
+            elif kind == "iCCP":
+                value = parsed
+            else:
+                value = bytes(payload)
+            setattr(self, _UNIQUE[kind], value)
+        elif kind == "sPLT":
+            self.suggestedPalettes.append(bytes(payload))
+        elif kind in ("iTXt", "tEXt", "zTXt"):
+            self.text.append(parsed)
+        else:
+            self.application.append((kind, bytes(payload)))
+
+    def chunks(self, deflated):
+        """-> (before, after): the chunks PNG.Image.compress writes in front of PLTE and behind tRNS, in its order
+        (PNG.Image.swift:596-656).  deflated: the streams of colorProfile and of the compressed texts, in that order"""
+        deflated = list(deflated)
+        before, after = [], []
+        if self.chromaticity is not None:
+            before.append(("cHRM", self.chromaticity))
+        if self.gamma is not None:
+            before.append(("gAMA", struct.pack(">I", self.gamma)))
+        if self.colorRendering is not None:
+            before.append(("sRGB", self.colorRendering))
+        if self.colorProfile is not None:                        # PNG.ColorProfile.serialized (PNG.ColorProfile.swift:87-103)
+            before.append(("iCCP", self.colorProfile.name.encode("latin-1") + b"\0\0" + deflated.pop(0)))
+        if self.significantBits is not None:
+            before.append(("sBIT", self.significantBits))
+        if self.histogram is not None:
+            after.append(("hIST", self.histogram))
+        if self.physicalDimensions is not None:
+            after.append(("pHYs", struct.pack(">IIB", *self.physicalDimensions)))
+        if self.time is not None:
+            after.append(("tIME", struct.pack(">HBBBBB", *self.time)))
+        for t in self.text:                                      # every text as iTXt (PNG.Text.serialized, PNG.Text.swift:309-349)
+            after.append(("iTXt", t.head() + (deflated.pop(0) if t.compressed else t.content.encode("utf-8"))))
+        after += [("sPLT", p) for p in self.suggestedPalettes] + list(self.application)
+        as_bytes = lambda cs: [(k.encode("latin-1") if isinstance(k, str) else bytes(k), bytes(p)) for k, p in cs]  # noqa: E731
+        return as_bytes(before), as_bytes(after)
+
+    def to_deflate(self):
+        """what `chunks` wants deflated at level 13, exponent 15: the profile, the contents of the compressed texts"""
+        return ([self.colorProfile.profile] if self.colorProfile is not None else []) + [t.content.encode("utf-8") for t in self.text if t.compressed]
+
+
+class Image:
+    """What PNG.decompress returns: size, the pieces of the format as PNG.compress takes them, storage, metadata"""
+
+    def __init__(self, size, depth, channels, indexed, bgr, interlaced, palette, key, fill, storage, metadata):
+        self.size, self.depth, self.channels, self.indexed, self.bgr, self.interlaced = size, depth, channels, indexed, bgr, interlaced
+        self.palette, self.key, self.fill, self.storage, self.metadata = palette, key, fill, storage, metadata
+
+    def format(self) -> dict:
+        return dict(indexed=self.indexed, bgr=self.bgr, interlaced=self.interlaced, palette=self.palette, key=self.key, fill=self.fill)
 
 
 class LZ77:
@@ -400,16 +559,200 @@ class PNG:
             self._cursor += len(data)
             return data
 
+    Metadata, Text, ColorProfile, Image = Metadata, Text, ColorProfile, Image
+
+    @staticmethod
+    def _walk(entries, names, info, metadata, work, payload):
+        """the loops of PNG.Image.decompress behind IHDR (PNG.Image.swift:323-399) over a file's directory: which chunks may stand
+        where.  Text and profile chunks go to `work`, their places to the metadata; PLTE, bKGD, tRNS to metadata._critical"""
+        from . import ParsingError
+        plte = bkgd = trns = None
+        seen_idat = done_idat = False
+        metadata._critical = (None, None, None)
+        for e, kind in zip(entries, names):
+            if kind == "IDAT":
+                if done_idat:
+                    raise UnexpectedChunk("IDAT", "IDAT")        # (PNG.Context.swift:133-135)
+                if not seen_idat and info.color == 3 and plte is None:
+                    raise RequiredChunk("PLTE", "IDAT")          # :363-365
+                seen_idat = True
+                continue
+            done_idat = seen_idat
+            if kind == "IEND":
+                if not seen_idat:
+                    raise RequiredChunk("IDAT", "IEND")          # :368-369
+                break
+            if seen_idat:                                        # PNG.Context.push(ancillary:) (PNG.Context.swift:120-146)
+                if kind in ("CgBI", "IHDR", "PLTE", "bKGD", "tRNS", "hIST", "cHRM", "gAMA", "sRGB", "iCCP", "sBIT", "pHYs", "sPLT"):
+                    raise UnexpectedChunk(kind, "IDAT")
+            elif kind == "IHDR":
+                raise DuplicateChunk("IHDR")                     # :336-337
+            elif kind == "PLTE":                                 # :339-355
+                if plte is not None:
+                    raise DuplicateChunk("PLTE")
+                if bkgd is not None:
+                    raise UnexpectedChunk("PLTE", "bKGD")
+                if trns is not None:
+                    raise UnexpectedChunk("PLTE", "tRNS")
+                plte = payload(e)
+                metadata._critical = (plte, bkgd, trns)
+                continue
+            elif kind in ("bKGD", "tRNS"):                       # PNG.Metadata.swift:173-182
+                if (bkgd if kind == "bKGD" else trns) is not None:
+                    raise DuplicateChunk(kind)
+                if kind == "bKGD":
+                    bkgd = payload(e)
+                else:
+                    trns = payload(e)
+                metadata._critical = (plte, bkgd, trns)
+                continue
+            if kind in ("iTXt", "tEXt", "zTXt", "iCCP"):
+                if kind == "iCCP" and (plte is not None or metadata.colorProfile is not None):
+                    metadata.push((kind, b""), palette_seen=plte is not None)        # (raises: the order and the multiplicity come first)
+                if e.status != DONE:
+                    raise ParsingError(e.status, (e.aux, 0))
+                work.append((e, kind))
+                metadata.push((kind, b""), palette_seen=plte is not None, parsed=len(work) - 1)
+            else:
+                metadata.push((kind, payload(e)), palette_seen=plte is not None)
+
+    @staticmethod
+    def decompress(data, session=None) -> Image:
+        """PNG.Image.decompress(stream:) (Sources/PNG/PNG.Image.swift:298-400) for a whole file: lexed on the device with its chunk
+        directory (spng_lex_dir_batch), the image decoded there from the IDAT bytes the lexer gathered (spng_decode_batch), the heads of
+        the text and profile chunks parsed there; their compressed bodies inflated in one spng_inflate_batch call straight from the
+        file's bytes in device memory, Latin-1 contents transcoded and iTXt contents checked in one spng_text_batch call.  The host
+        sees the infos, the directory, the small chunks and the finished contents; it applies the rules about which chunks may
+        stand where (RequiredChunk, DuplicateChunk, UnexpectedChunk) and reads PLTE / tRNS / bKGD.  An iTXt content that is not
+        well-formed UTF-8 is repaired on the host with errors="replace"."""
+        from . import (E_OUTPUT_CAPACITY, E_PROFILE_INCOMPLETE, E_TEXT_ENCODING, E_TEXT_INCOMPLETE, FORMAT_IOS, FORMAT_ZLIB,
+                       NEED_MORE_INPUT, TEXT_CHECK_UTF8, TEXT_LATIN1_TO_UTF8, ParsingError, load, raise_for, storage_size, inflated_size)
+        s = session or load()
+        data = bytes(data)
+        d_png = s.to_device(data)
+        (info,), (d_idat,), (entries,) = s.lex_dir_batch([data], d_png=[d_png], device_idat=True)
+        # (the chunks in front of a lexing failure have been lexed in full: what is wrong with them comes first, as in the reference's loop)
+        names = [_name(e.type) for e in entries]
+        payload = lambda e: data[e.offset:e.offset + e.length]  # noqa: E731
+        # :303-321: CgBI?, IHDR
+        at = 1 if names[:1] == ["CgBI"] else 0
+        if len(names) <= at:
+            raise_for(info.status, (info.aux[0], info.aux[1]))
+        if names[at] != "IHDR":
+            raise RequiredChunk("IHDR", names[at])
+        ios = at == 1
+        metadata = Metadata()
+        work = []                                                # (entry, kind): the text and profile chunks, in file order
+        pending = None                                           # the first thing wrong with the chunks: raised once the bodies in front of it have been looked at
+        try:
+            PNG._walk(entries[at + 1:], names[at + 1:], info, metadata, work, payload)
+        except (ChunkOrderError, ParsingError) as err:
+            pending = err
+        plte, bkgd, trns = metadata._critical
+        if pending is None:
+            raise_for(info.status, (info.aux[0], info.aux[1]))
+        # the bodies: compressed ones inflated from the file's bytes in device memory, all at once
+        bodies = [d_png[e.offset + e.body_off:e.offset + e.length] for e, _ in work]
+        packed = [k for k, (e, _) in enumerate(work) if e.compressed]
+        caps = [max(1 << 16, 8 * bodies[k].numel()) for k in packed]
+        todo = list(range(len(packed)))
+        while todo:
+            outs, results = s.inflate_batch([bodies[packed[j]] for j in todo], [caps[j] for j in todo])
+            again = []
+            for j, out, r in zip(todo, outs, results):
+                if r.status == E_OUTPUT_CAPACITY:                # (the reference's output buffer is unbounded)
+                    caps[j] *= 4
+                    again.append(j)
+                    continue
+                if r.status == NEED_MORE_INPUT:                  # PNG.Text.swift:161-165, 184-188; PNG.ColorProfile.swift:78-82
+                    raise ParsingError(E_PROFILE_INCOMPLETE if work[packed[j]][1] == "iCCP" else E_TEXT_INCOMPLETE)
+                raise_for(r.status, (r.aux[0], r.aux[1]))
+                bodies[packed[j]] = out[:r.written]
+            todo = again
+        if pending is not None:
+            raise pending
+        # the image: the IDAT bytes are where the lexer put them
+        if (info.color, info.depth) not in ((0, 1), (0, 2), (0, 4), (0, 8), (0, 16), (2, 8), (2, 16), (3, 1), (3, 2), (3, 4), (3, 8), (4, 8),
+                                            (4, 16), (6, 8), (6, 16)) or not info.width or not info.height:
+            raise ValueError("no PNG.Header: the pixel format or the size of IHDR")     # (PNG.Header.init(parsing:standard:) throws)
+        channels = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[info.color]
+        size = (info.width, info.height)
+        d_rows = s.empty(inflated_size(size[0], size[1], info.depth, channels, bool(info.interlace)))
+        nbytes = storage_size(size[0], size[1], info.depth, channels)
+        d_storage = s.empty(nbytes)
+        desc = s.image_desc(d_idat[:info.idat_len], d_rows, d_storage, size[0], size[1], info.depth, channels, bool(info.interlace),
+                            FORMAT_IOS if ios else FORMAT_ZLIB)
+        (res,) = s.decode_batch([desc])
+        raise_for(res.status, (res.aux[0], res.aux[1]))
+        if res.status == NEED_MORE_INPUT:
+            raise DecodingError(E_INCOMPLETE_DATASTREAM)         # (PNG.Context.swift:137-142)
+        storage = bytes(d_storage[:nbytes].cpu().numpy())
+        # the contents: Latin-1 ones transcoded, iTXt ones checked
+        texts = [k for k, (_, kind) in enumerate(work) if kind != "iCCP"]
+        ops = [TEXT_CHECK_UTF8 if work[k][1] == "iTXt" else TEXT_LATIN1_TO_UTF8 for k in texts]
+        outs, results = s.text_batch([bodies[k] for k in texts], ops) if texts else ([], [])
+        parsed = []
+        for k, (e, kind) in enumerate(work):
+            raw = payload(e)
+            if kind == "iCCP":
+                parsed.append(ColorProfile(raw[:e.k].decode("latin-1"), bodies[k].cpu().numpy().tobytes()))
+                continue
+            out, r = outs[texts.index(k)], results[texts.index(k)]
+            english = raw[:e.k].decode("latin-1")
+            if kind == "iTXt":
+                if r.status not in (DONE, E_TEXT_ENCODING):
+                    raise_for(r.status, (r.aux[0], r.aux[1]))
+                content = bodies[k].cpu().numpy().tobytes().decode("utf-8", "replace" if r.status == E_TEXT_ENCODING else "strict")
+                tag = raw[e.k + 3:e.l]
+                language = [t.decode("latin-1").lower() for t in tag.split(b"-")] if tag else []      # PNG.Text.swift:265-286
+                localized = raw[e.l + 1:e.m].decode("utf-8", "replace")
+                parsed.append(Text(e.compressed, (english, "" if localized == english else localized), language, content))
+            else:
+                raise_for(r.status, (r.aux[0], r.aux[1]))
+                parsed.append(Text(e.compressed, (english, ""), ["en"], out[:r.written].cpu().numpy().tobytes().decode("utf-8")))
+        metadata.text = [parsed[k] for k in metadata.text]
+        if metadata.colorProfile is not None:
+            metadata.colorProfile = parsed[metadata.colorProfile]
+        # PNG.Format.recognize (Formats/PNG.Format.swift:396-560): what PLTE / tRNS / bKGD mean for this pixel format
+        indexed = info.color == 3
+        palette = key = fill = None
+
+        def fields(raw):
+            v = struct.unpack(">" + "H" * (len(raw) // 2), raw)
+            return v[0] if len(v) == 1 else (v[::-1] if ios else v)
+
+        if plte is not None:
+            alphas = trns if indexed and trns is not None else b""
+            palette = [(plte[3 * k], plte[3 * k + 1], plte[3 * k + 2], alphas[k] if k < len(alphas) else 255) for k in range(len(plte) // 3)]
+        if trns is not None and not indexed:
+            key = fields(trns)
+        if bkgd is not None:
+            fill = bkgd[0] if indexed else fields(bkgd)
+        return Image(size, info.depth, channels, indexed, ios, bool(info.interlace), palette, key, fill, storage, metadata)
+
     @staticmethod
     def compress(storage, size, depth, channels, indexed=False, bgr=False, interlaced=False, palette=None, key=None, fill=None,
-                 before=(), after=(), level=9, chunk_bytes=65544, session=None) -> bytes:
+                 before=(), after=(), level=9, chunk_bytes=65544, session=None, metadata=None) -> bytes:
         """PNG.Image.compress(stream:level:hint:) from storage (Sources/PNG/PNG.Image.swift:576-668): -> the bytes of the file, written
         on the device by one spng_compress_batch call.  before / after: the metadata's chunks as (type, payload) pairs, in front of
         PLTE / behind tRNS (the reference's cHRM gAMA sRGB iCCP sBIT, and hIST pHYs tIME iTXt sPLT and application chunks).
         chunk_bytes: payload bytes of every IDAT but the last -- the reference cuts at twice the capacity its output buffer got
         (LZ77.DeflatorOut.swift:15-24, 121), an allocator fact: 65544 at the default hint on Linux, 8200 at hint 4096."""
-        from . import load
+        from . import load, raise_for
         s = session or load()
+        if metadata is not None:
+            # metadata: a PNG.Metadata, written in the order of PNG.Image.swift:596-656 in front of `before` / `after`; the profile and
+            # the contents of the compressed texts are deflated on the device in one call (LZ77.Deflator(level: 13, exponent: 15),
+            # PNG.Text.swift:336, PNG.ColorProfile.swift:97)
+            plain = metadata.to_deflate()
+            streams = []
+            if plain:
+                outs, results = s.deflate_batch([s.to_device(p) for p in plain], 13)
+                for out, r in zip(outs, results):
+                    raise_for(r.status, (r.aux[0], r.aux[1]))
+                    streams.append(out[:r.written].cpu().numpy().tobytes())
+            m_before, m_after = metadata.chunks(streams)
+            before, after = m_before + list(before), m_after + list(after)
         return s.compress(bytes(storage), size, depth, channels, level=level, indexed=indexed, bgr=bgr, interlaced=interlaced, palette=palette,
                           key=key, fill=fill, before=before, after=after, chunk_bytes=chunk_bytes)
 

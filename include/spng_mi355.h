@@ -104,7 +104,11 @@ typedef struct spng_result {
     uint64_t aux[2];                  /* error payload, see the status table */
 } spng_result;
 
-/* One zlib/raw-DEFLATE stream to inflate.  All pointers are device pointers. */
+/* One zlib/raw-DEFLATE stream to inflate.  All pointers are device pointers.
+ * d_src and d_dst may have any alignment.  The kernels read no byte behind d_src[src_len - 1] and write no byte behind
+ * d_dst[dst_cap - 1] or in front of d_dst; a capacity that is too small answers SPNG_E_OUTPUT_CAPACITY (inflate: written = the bytes
+ * in front of the token that did not fit, all of them valid; deflate: see spng_deflate_batch).  Bytes in [written, dst_cap) are
+ * unspecified after a call.  (tests/test_gpu_bounds.py, tests/test_emu_bounds.py) */
 typedef struct spng_stream_desc {
     const void *d_src;  uint64_t src_len;     /* whole stream = concatenated IDAT payloads */
     void       *d_dst;  uint64_t dst_cap;     /* inflated bytes */
@@ -760,7 +764,10 @@ int32_t spng_filter(spng_ctx *ctx, const void *storage,
  * and LZ77.Format.ios ignores it (LZ77.DeflatorBuffers.swift:52-55).  SPNG_FORMAT_GZIP: Gzip.Deflator (header, CRC-32 and
  * byte count of the input appended on the device).  Levels >= 8: the call waits for a small probe kernel (how
  * repetitive is each input: compressible streams get helper waves) before it enqueues the compression, so it is
- * asynchronous only from there on. */
+ * asynchronous only from there on.
+ * A capacity below the stream's length L (every format, the gzip trailer included): SPNG_E_OUTPUT_CAPACITY with written = L, the
+ * bytes the whole stream needs -- allocate that much and call again --, consumed = src_len, and d_dst[0 .. dst_cap) = the stream's
+ * first dst_cap bytes; nothing is stored behind dst_cap.  dst_cap may be 0 (d_dst must still be a pointer). */
 uint64_t spng_deflate_bound(uint64_t n);
 int32_t spng_deflate_batch(spng_ctx *ctx, const spng_stream_desc *descs, const int32_t *levels, uint32_t count,
                            spng_result *d_results, spng_result *h_results);
@@ -777,7 +784,12 @@ int32_t spng_deflate_window(spng_ctx *ctx, const void *src, uint64_t n, int32_t 
  * bytes so far determine: levels 0-7 every term whose positions see their whole 258-byte look-ahead, levels 8 and up every whole
  * block (2047, 4095, ... vertices); the rest waits for the next push.  Results: SPNG_NEED_MORE_INPUT with written = stream bytes
  * so far, consumed = input bytes parsed, aux = the host-side part of the state to hand to the next call as h_state[2 i], [2 i + 1]
- * (levels >= 8: it sizes the call's launches; NULL / {0, 0} at the first push); SPNG_DONE with the final counts when last. */
+ * (levels >= 8: it sizes the call's launches; NULL / {0, 0} at the first push); SPNG_DONE with the final counts when last.
+ * A capacity the stream outgrows: the push that overflows and every later one answer SPNG_E_OUTPUT_CAPACITY (written = the stream
+ * bytes so far, beyond dst_cap; consumed and aux as for SPNG_NEED_MORE_INPUT: the pushes go on), the last one with written = the
+ * bytes the whole stream needs and consumed = src_len; d_dst[0 .. dst_cap) = the stream's first dst_cap bytes.
+ * Limit: the checksum sums of levels 0-7 (D1State.adlerS / adlerI, csrc/common.hpp) are 32-bit and grow by up to 65 520 per search
+ * chunk and push: a stream of more than 65 536 chunks or pushes could wrap them. */
 uint64_t spng_deflate_state_bytes(void);
 int32_t spng_deflate_resume_batch(spng_ctx *ctx, const spng_stream_desc *descs, const int32_t *levels, void *const *d_states,
                                   const uint8_t *last, const uint64_t *h_state, uint32_t count,

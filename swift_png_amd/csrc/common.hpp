@@ -342,7 +342,9 @@ struct D1State {
     uint32_t terms[2048];
     // the two-kernel form (round 5: dfl3_search_kernel + dfl3_parse_kernel): the positions of the round the parse is at, the
     // search's own cursor (it runs a round ahead) and how far the input has been searched -- rounds partition the positions, so the
-    // Adler sums the search workgroups add up (unreduced, adlerS / adlerI) count every byte once whatever the pushes were
+    // Adler sums the search workgroups add up (unreduced, adlerS / adlerI) count every byte once whatever the pushes were.
+    // LIMIT: the two sums are 32-bit and grow by up to 65 520 per search chunk and push (deflate.hip: atomicAdd(adlerS, S % 65521)): a
+    // stream of more than 65 536 chunks or pushes could wrap them (include/spng_mi355.h, spng_deflate_resume_batch, says so too).
     uint64_t rb, re, srb, sre, spos;
     uint32_t done, pad3;
 };

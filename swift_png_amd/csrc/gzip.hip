@@ -161,12 +161,20 @@ __global__ void gzip_deflate_post_kernel(const DeflateJob *__restrict__ jobs, sp
     if (i >= count || jobs[i].format != SPNG_FORMAT_GZIP) return;
     const DeflateJob &j = jobs[i];
     spng_result &r = results[j.image];
+    // A body that did not fit (`written` is what it needs, beyond dst_cap) counts the trailer too and stores nothing of it: the
+    // capacity error reports what the whole member needs.  (A push that is not the last answers SPNG_E_OUTPUT_CAPACITY as well once
+    // the stream has overflowed: it has no trailer yet.)
+    if (r.status == SPNG_E_OUTPUT_CAPACITY && !j.more) { r.written += 8; return; }
     if (r.status != SPNG_DONE) return;
     const uint32_t crc = fold_pieces(parts + (uint64_t)i * GZ_PIECES, j.src_len), size = (uint32_t)j.src_len;
-    if (r.written + 8 > j.dst_cap) { r.status = SPNG_E_OUTPUT_CAPACITY; r.written += 8; return; }
-    gbyte *q = (gbyte *)j.dst + r.written;
-    for (int k = 0; k < 4; ++k) { q[k] = (uint8_t)(crc >> (8 * k)); q[4 + k] = (uint8_t)(size >> (8 * k)); }
+    // the bytes of the trailer that lie in front of dst_cap are stored: the first dst_cap bytes are the stream's own
+    gbyte *dst = (gbyte *)j.dst;
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint64_t at = r.written + k;
+        if (at < j.dst_cap) dst[at] = (uint8_t)((k < 4 ? crc : size) >> (8 * (k & 3)));
+    }
     r.written += 8;
+    if (r.written > j.dst_cap) r.status = SPNG_E_OUTPUT_CAPACITY;
 }
 
 // ---- resumable streams (spng_inflate_resume_batch) ------------------------------------------------------

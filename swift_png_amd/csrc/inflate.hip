@@ -85,8 +85,7 @@ static constexpr int LBITS = 10, DBITS = 8, MBITS = 7;
 // Tokens the walker decodes itself may be degenerate (run 0, checks the reference leaves to the
 // output side) and use the wide forms:
 //   back-reference   1 << 31 | run << 16 | distance
-//   capacity check   3 << 30 | bytes        ("the next `bytes` bytes must fit the output": stored
-//                                             blocks check their whole length up front)
+//   block start      3 << 30                ("a block begins at this output position")
 static constexpr uint32_t T_MATCH = 0x80000000u, T_CHECK = 0xc0000000u, T_REF = 0x80u;
 
 struct Ctrl {
@@ -403,7 +402,7 @@ __device__ __attribute__((always_inline)) void resolver(Lds &s, gbyte *dst, uint
         if (over) m = (uint32_t)__ffsll((long long)over) - 1;  // >= 1: a single token is <= 258 bytes
         const uint32_t offs = incl - len;
         const uint64_t at = o.pos + offs;
-        const uint32_t need = is_match ? run : is_check ? dist : 1u;
+        const uint32_t need = is_match ? run : is_check ? 0u : 1u;   // (a stored byte is a literal: it fits or the stream stops in front of it)
         const bool bad_ref = is_match && (uint64_t)dist > at;
         const unsigned long long bad = __ballot((uint32_t)lane < m && (bad_ref || at + need > o.cap));
         if (bad) {
@@ -769,8 +768,8 @@ __device__ __attribute__((always_inline)) void decoder(Lds &s, const gbyte *src,
             const uint32_t l = TAKE(16);
             const uint32_t m = TAKE(16);
             if (l != (~m & 0xffffu)) FAIL(SPNG_E_BLOCK_COUNT_PARITY, l, m);
-            // readBlock(upTo:) (:384-399): copies as many of the LEN bytes as the input holds, after
-            // making sure all of them fit the output
+            // readBlock(upTo:) (:384-399): copies as many of the LEN bytes as the input holds, byte by byte: a capacity that ends
+            // inside the block leaves the bytes in front of it written (the resolver checks every literal)
             uint64_t from = boundary / 8 + 4;
             uint32_t l_left = l;
             if (inside) {                                      // (earlier calls copied r_done of the LEN bytes)
@@ -779,7 +778,6 @@ __device__ __attribute__((always_inline)) void decoder(Lds &s, const gbyte *src,
                 from += dn; l_left -= dn; inside = false;
             }
             const uint32_t have = n - from < l_left ? (uint32_t)(n - from) : l_left;
-            if (have) PUSH(1ull, T_CHECK | have);               // (a check of 0 bytes is a block start)
             for (uint32_t done_ = 0; done_ < have; done_ += 64) {
                 const uint32_t piece = have - done_ < 64 ? have - done_ : 64;
                 const uint32_t b = (uint32_t)lane < piece ? src[from + done_ + lane] : 0u;

@@ -7,8 +7,14 @@
 //   emu_deflate2 <input file> <expected stream file> <level> <format 0 zlib | 1 raw (ios)> [chunks per stream] [cut ...]
 //   cut ...: the input arrives in pieces (spng_deflate_resume_batch): a call per cut with `more` set, the state kept, then the rest
 //   EMU_EXPONENT=8...15: the window exponent (default 15, what PNG uses; the raw format always takes 15, DeflatorBuffers.swift:52-55)
-//   exit code 0: SPNG_DONE and identical bytes; 1: anything else (printed)
+//   EMU_DST_CAP=n: the output capacity (default: the expected stream's length + 4096).  Below that length the run succeeds exactly when
+//   the status is SPNG_E_OUTPUT_CAPACITY, written is the expected stream's length and the first n bytes are the expected stream's; with
+//   `cut ...` every push from the one that overflowed on must answer SPNG_E_OUTPUT_CAPACITY
+//   The input has exactly its bytes and the output exactly its capacity, both between guard bytes (tools/emu/guard.hpp; under the
+//   address sanitizer: exact heap buffers): exit code 6 when a guard byte changed (printed: which), whatever else happened
+//   exit code 0: SPNG_DONE and identical bytes (or the capacity answer above); 1: anything else (printed)
 #include EMU_DEFLATE_SRC
+#include "guard.hpp"
 
 #include <fstream>
 #include <iostream>
@@ -21,18 +27,54 @@ static std::vector<uint8_t> slurp(const char *path)
     return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
 }
 
+static int run(int argc, char **argv, const emu::Guarded &src, const std::vector<uint8_t> &want, emu::Guarded &dst);
+
 int main(int argc, char **argv)
 {
     if (argc < 5) { fprintf(stderr, "usage\n"); return 2; }
-    std::vector<uint8_t> src = slurp(argv[1]), want = slurp(argv[2]);
+    const emu::Guarded src(slurp(argv[1]));
+    const std::vector<uint8_t> want = slurp(argv[2]);
+    emu::Guarded dst(getenv("EMU_DST_CAP") ? strtoull(getenv("EMU_DST_CAP"), nullptr, 10) : want.size() + 4096);
+    const int code = run(argc, argv, src, want, dst);
+    if (!src.intact("source") || !dst.intact("destination")) return emu::EXIT_GUARD;
+    return code;
+}
+
+// the end of a run: the whole stream, or -- a capacity below its length -- the capacity answer
+static int verdict(const spng_result &res, const std::vector<uint8_t> &want, const emu::Guarded &dst, uint64_t n, uint32_t rounds, const char *form)
+{
+    const uint64_t cap = dst.size(), head = cap < want.size() ? cap : want.size();
+    const int32_t expect = cap < want.size() ? SPNG_E_OUTPUT_CAPACITY : SPNG_DONE;
+    if (res.status != expect) { printf("status %d where %d is expected (capacity %llu, stream %zu)\n", res.status, expect, (unsigned long long)cap, want.size()); return 1; }
+    if (res.written != want.size() || res.consumed != n || memcmp(dst.data(), want.data(), head)) {
+        size_t k = 0;
+        while (k < head && dst.data()[k] == want[k]) ++k;
+        printf("stream differs: %llu bytes against %zu expected, consumed %llu of %llu, first difference at %zu of the first %llu\n", (unsigned long long)res.written,
+               want.size(), (unsigned long long)res.consumed, (unsigned long long)n, k, (unsigned long long)head);
+        return 1;
+    }
+    printf("ok%s: %llu -> %llu bytes in %u rounds%s\n", expect ? " (capacity)" : "", (unsigned long long)n, (unsigned long long)res.written, rounds, form);
+    return 0;
+}
+
+// a push that is not the last: more input wanted -- or, from the push that overflowed on, the capacity error
+static bool push_answer(const spng_result &res, bool &overflowed, size_t call)
+{
+    if (res.status == SPNG_E_OUTPUT_CAPACITY) overflowed = true;
+    if (res.status == (overflowed ? SPNG_E_OUTPUT_CAPACITY : SPNG_NEED_MORE_INPUT)) return true;
+    printf("call %zu (more): status %d%s\n", call, res.status, overflowed ? " after the stream had overflowed" : "");
+    return false;
+}
+
+static int run(int argc, char **argv, const emu::Guarded &src, const std::vector<uint8_t> &want, emu::Guarded &dst)
+{
     const int level = atoi(argv[3]), format = atoi(argv[4]);
     const uint32_t cps = argc > 5 ? (uint32_t)atoi(argv[5]) : 3;
     const uint64_t n = src.size();
     const int asked = getenv("EMU_EXPONENT") ? atoi(getenv("EMU_EXPONENT")) : 15;
     if (asked < 8 || asked > 15) { fprintf(stderr, "EMU_EXPONENT: 8 ... 15\n"); return 2; }
     const uint32_t exponent = format == 1 ? 15u : (uint32_t)asked;
-    std::vector<uint8_t> dst(want.size() + 4096, 0xEE);
-    src.resize(n + 64);                                          // (the kernels read keys a few bytes past positions they search)
+    bool overflowed = false;
 
     if (level < 8) {
         // levels 0-7 in rounds: dfl3_begin -> (dfl3_search_fast + dfl3_advance, dfl3_parse) per round, the two sets of answers
@@ -90,18 +132,11 @@ int main(int argc, char **argv)
                     emu::launch(grid, 64, [&] { dfl4_place_kernel(&st, maxb); });
                 } else emu::launch(1, 128, [&] { dfl3_parse_kernel(&st, &res, par); });
             }
-            if (st.more && res.status != SPNG_NEED_MORE_INPUT) { printf("call %zu (more): status %d\n", call, res.status); return 1; }
+            if (st.more && !push_answer(res, overflowed, call)) return 1;
             if (st.more) { if (res.aux[1] != st.state->spos) { printf("call %zu: aux[1] %llu != spos %llu\n", call, (unsigned long long)res.aux[1], (unsigned long long)st.state->spos); return 1; } spos = res.aux[1]; }
         }
-        if (res.status != SPNG_DONE || !st.state->done) { printf("status %d done %u after %u rounds\n", res.status, st.state->done, rounds); return 1; }
-        if (res.written != want.size() || memcmp(dst.data(), want.data(), want.size())) {
-            size_t k = 0;
-            while (k < want.size() && k < res.written && dst[k] == want[k]) ++k;
-            printf("stream differs: %llu bytes against %zu expected, first difference at %zu\n", (unsigned long long)res.written, want.size(), k);
-            return 1;
-        }
-        printf("ok: %llu -> %llu bytes in %u rounds (search + parse kernels%s)\n", (unsigned long long)n, (unsigned long long)res.written, rounds, blocks ? ", blocks side by side" : "");
-        return 0;
+        if (!st.state->done) { printf("status %d done %u after %u rounds\n", res.status, st.state->done, rounds); return 1; }
+        return verdict(res, want, dst, n, rounds, blocks ? " (search + parse kernels, blocks side by side)" : " (search + parse kernels)");
     }
     const uint64_t V = deflate2_vertices(n), B = V / 64 + 2;
     std::vector<uint16_t> vinfo[2] = {std::vector<uint16_t>(V, 0xDEAD), std::vector<uint16_t>(V, 0xBEEF)};
@@ -148,16 +183,9 @@ int main(int argc, char **argv)
             if (getenv("EMU_VERBOSE")) fprintf(stderr, "call %zu round %u: pos %llu limit %u total %llu fail %u done %u status %d\n", call, r, (unsigned long long)state.pos,
                                                state.limit, (unsigned long long)state.total, state.fail, state.done, res.status);
         }
-        if (st.more && res.status != SPNG_NEED_MORE_INPUT) { printf("call %zu (more): status %d\n", call, res.status); return 1; }
+        if (st.more && !push_answer(res, overflowed, call)) return 1;
     }
-    if (getenv("EMU_DUMP")) { std::ofstream o(getenv("EMU_DUMP"), std::ios::binary); o.write((const char *)dst.data(), (std::streamsize)res.written); }
-    if (res.status != SPNG_DONE || !state.done || state.fail) { printf("status %d done %u fail %u after %u rounds\n", res.status, state.done, state.fail, rounds); return 1; }
-    if (res.written != want.size() || memcmp(dst.data(), want.data(), want.size())) {
-        size_t k = 0;
-        while (k < want.size() && k < res.written && dst[k] == want[k]) ++k;
-        printf("stream differs: %llu bytes against %zu expected, first difference at %zu\n", (unsigned long long)res.written, want.size(), k);
-        return 1;
-    }
-    printf("ok: %llu -> %llu bytes in %u rounds\n", (unsigned long long)n, (unsigned long long)res.written, rounds);
-    return 0;
+    if (getenv("EMU_DUMP")) { std::ofstream o(getenv("EMU_DUMP"), std::ios::binary); o.write((const char *)dst.data(), (std::streamsize)(res.written < dst.size() ? res.written : dst.size())); }
+    if (!state.done || state.fail) { printf("status %d done %u fail %u after %u rounds\n", res.status, state.done, state.fail, rounds); return 1; }
+    return verdict(res, want, dst, n, rounds, "");
 }

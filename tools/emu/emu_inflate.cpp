@@ -6,7 +6,10 @@
 //   emu_inflate <stream file> <format 0 zlib | 1 ios | 2 gzip-less raw> <capacity> <output file> [block_bit block_out token_bit token_out <bytes so far file>]
 //   (the five: a call of spng_inflate_resume_batch that goes on where an earlier one stopped -- its four words of state and the output so far)
 //   prints: status written consumed aux0 aux1
+//   The stream has exactly its bytes and the output exactly <capacity>, both between guard bytes (tools/emu/guard.hpp; under the address
+//   sanitizer: exact heap buffers).  exit code 0: the kernel ran;  6: it changed a guard byte (printed: which)
 #include EMU_INFLATE_SRC
+#include "guard.hpp"
 
 #include <fstream>
 #include <iostream>
@@ -23,12 +26,11 @@ static std::vector<uint8_t> slurp(const char *path)
 int main(int argc, char **argv)
 {
     if (argc < 5) { fprintf(stderr, "usage\n"); return 2; }
-    std::vector<uint8_t> src = slurp(argv[1]);
+    const emu::Guarded src(slurp(argv[1]));
     const int format = atoi(argv[2]);
     const uint64_t cap = strtoull(argv[3], nullptr, 10);
     const uint64_t n = src.size();
-    src.resize(n + 64);
-    std::vector<uint8_t> dst(cap + 64, 0xEE);
+    emu::Guarded dst(cap);
     uint64_t state[4] = {0, 0, 0, 0};
     InflateJob job;
     memset(&job, 0, sizeof job);
@@ -47,5 +49,6 @@ int main(int argc, char **argv)
            (unsigned long long)res.aux[0], (unsigned long long)res.aux[1]);
     std::ofstream o(argv[4], std::ios::binary);
     o.write((const char *)dst.data(), (std::streamsize)(res.written < cap ? res.written : cap));
+    if (!src.intact("source") || !dst.intact("destination")) return emu::EXIT_GUARD;
     return 0;
 }

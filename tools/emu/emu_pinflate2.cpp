@@ -9,10 +9,15 @@
 //   state is {start_bit, out_pos, b, w} (b = 0: it stands at the block header), the first w bytes of the output are there, the
 //   segments count from the resume point; prints "handover bit=<b> bytes=<n> header=<bit> header_bytes=<n>" when the chain was
 //   handed to the serial kernel at a token (PStream.ok == 3)
+//   EMU_DST_CAP=n: the output capacity (default: the expected output's length).  Below that length the pipeline must leave the stream
+//   to the serial kernel: exit code 3 or 4
+//   The stream has exactly its bytes and the output exactly its capacity, both between guard bytes (tools/emu/guard.hpp; under the
+//   address sanitizer: exact heap buffers): exit code 6 when a guard byte changed (printed: which), whatever else happened
 //   exit code 0: the pipeline produced SPNG_DONE and identical bytes;  3: the pipeline left the whole stream to the serial
 //   kernel;  4: it decoded a prefix (printed: the block boundary and byte count the serial kernel would start from) and that
 //   prefix is right;  5: it reported an error of its own (printed);  1: wrong bytes / wrong result
 #include "../../swift_png_amd/csrc/pinflate2.hip"
+#include "guard.hpp"
 
 #include <fstream>
 #include <iostream>
@@ -34,13 +39,24 @@ static void cov_print()
     if (getenv("EMU_CUT_BYTES")) fprintf(stderr, "COVCUT %ld %ld %ld\n", spng::g_cov[6], spng::g_cov[7], spng::g_cov[8]);
 }
 #endif
+static int run(int argc, char **argv, const emu::Guarded &src, const std::vector<uint8_t> &want, emu::Guarded &dst);
+
 int main(int argc, char **argv)
 {
     if (argc < 5) { fprintf(stderr, "usage\n"); return 2; }
 #ifdef SPNG_EMU_COV
     atexit(cov_print);
 #endif
-    std::vector<uint8_t> src = slurp(argv[1]), want = slurp(argv[2]);
+    const emu::Guarded src(slurp(argv[1]));
+    const std::vector<uint8_t> want = slurp(argv[2]);
+    emu::Guarded dst(getenv("EMU_DST_CAP") ? strtoull(getenv("EMU_DST_CAP"), nullptr, 10) : want.size());
+    const int code = run(argc, argv, src, want, dst);
+    if (!src.intact("source") || !dst.intact("destination")) return emu::EXIT_GUARD;
+    return code;
+}
+
+static int run(int argc, char **argv, const emu::Guarded &src, const std::vector<uint8_t> &want, emu::Guarded &dst)
+{
     const int format = atoi(argv[3]);
     uint64_t seg_bytes = strtoull(argv[4], nullptr, 10);
     seg_bytes = (seg_bytes + 255) & ~(uint64_t)255;
@@ -48,11 +64,10 @@ int main(int argc, char **argv)
     const bool verbose = getenv("EMU_VERBOSE") != nullptr;
     const uint32_t ptcap = getenv("EMU_PTCAP") ? (uint32_t)atoi(getenv("EMU_PTCAP")) : pages;   // page-table entries per segment
 
-    std::vector<uint8_t> dst(want.size() + 64, 0xEE);
-    src.resize(src.size());
+    const uint64_t cap = dst.size();
     PStream st;
     memset(&st, 0, sizeof st);
-    st.src = src.data(); st.dst = dst.data(); st.src_len = src.size(); st.dst_cap = want.size();
+    st.src = src.data(); st.dst = dst.data(); st.src_len = src.size(); st.dst_cap = cap;
     st.format = format; st.image = 0;
     uint64_t state[4] = {0, 0, 0, 0};                          // (four words: the pipeline moves the first pair and clears the second)
     st.state = state;                                          // (host_decode.hip: every stream has a state slot, {0, 0} unless resumed)
@@ -69,6 +84,7 @@ int main(int argc, char **argv)
                 if (state[2]) { st.tok_bit = state[2]; st.out_pos = state[3]; }
             }
         }
+        if (st.out_pos > cap) { fprintf(stderr, "EMU_DST_CAP below the resumed position\n"); return 2; }
         memcpy(dst.data(), want.data(), st.out_pos);
     }
     uint64_t k = (src.size() - st.seg_origin + seg_bytes - 1) / seg_bytes;
@@ -208,7 +224,7 @@ int main(int argc, char **argv)
     }
     if (!done && (state[0] || state[1])) {
         printf("partial: the serial kernel starts at bit %llu with %llu bytes in front of it\n", (unsigned long long)state[0], (unsigned long long)state[1]);
-        if (state[1] > want.size() || memcmp(dst.data(), want.data(), state[1]) != 0) { printf("MISMATCH in the prefix\n"); return 1; }
+        if (state[1] > want.size() || state[1] > cap || memcmp(dst.data(), want.data(), state[1]) != 0) { printf("MISMATCH in the prefix\n"); return 1; }
         return 4;
     }
     if (done && res.status != SPNG_DONE) {
@@ -218,18 +234,16 @@ int main(int argc, char **argv)
     }
     if (!done) {
         size_t i = 0;
-        while (i < want.size() && dst[i] == want[i]) ++i;
+        while (i < want.size() && i < cap && dst.data()[i] == want[i]) ++i;
         printf("declined (ok=%d); output agrees with the expected bytes up to %zu of %zu\n", st.ok, i, want.size());
         return 3;
     }
-    if (res.status != SPNG_DONE || res.reserved != 1 || res.written != want.size()) {
+    if (res.status != SPNG_DONE || res.reserved != 1 || res.written != want.size() || res.written > cap) {
         printf("bad result: status %d written %llu (want %zu)\n", res.status, (unsigned long long)res.written, want.size());
         return 1;
     }
     for (size_t i = 0; i < want.size(); ++i)
-        if (dst[i] != want[i]) { printf("MISMATCH at byte %zu: %02x != %02x\n", i, dst[i], want[i]); return 1; }
-    for (size_t i = want.size(); i < dst.size(); ++i)
-        if (dst[i] != 0xEE) { printf("wrote past the end at %zu\n", i); return 1; }
+        if (dst.data()[i] != want[i]) { printf("MISMATCH at byte %zu: %02x != %02x\n", i, dst.data()[i], want[i]); return 1; }
     printf("ok: %zu -> %zu bytes, %llu segments, %u pages, consumed %llu\n", src.size(), want.size(), (unsigned long long)k, next,
            (unsigned long long)res.consumed);
     return 0;

@@ -208,7 +208,8 @@ __global__ __launch_bounds__(64) void resume_adler_kernel(const InflateJob *__re
     uint32_t S = 0, I = 0, g = (uint32_t)((from + (uint64_t)lane) % 65521);      // position mod 65521, kept incrementally
     for (uint64_t k = lane; k < m; k += 64) {
         const uint32_t b = p[from + k];
-        S += b;                                                // < 2^32: a piece is far below 2^24 bytes
+        S += b;                                                // < 2^32 while a lane sees at most (2^32 - 1) / 255 bytes: pieces of up to 2^30 bytes; a
+                                                               // stream of 2^32 bytes has pieces of 2^24 (tests/checksum_cases.py: RESUME_PIECE_LIMIT)
         I = (I + g * b) % 65521;
         g += 64; g = g >= 65521 ? g - 65521 : g;
     }

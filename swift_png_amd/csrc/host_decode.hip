@@ -499,9 +499,10 @@ static int32_t trace_inflate_plan(spng_ctx *c, const InflatePlan &p, Arena &a)
     }
     for (uint32_t i = 0; i < n && i < 4; ++i) {
         const PStream &st = hs[i];
-        fprintf(stderr, "[pinflate] stream %u: len %llu segs %u seg_bytes %llu ok %d pass %u ntok %llu end_bit %llu\n", i,
+        // (parts: how many the chain was cut into, of the slots plan_parts gave the stream -- 0 of 0: one workgroup)
+        fprintf(stderr, "[pinflate] stream %u: len %llu segs %u seg_bytes %llu ok %d pass %u ntok %llu end_bit %llu parts %u of %u\n", i,
                 (unsigned long long)st.src_len, st.seg_count, (unsigned long long)st.seg_bytes, st.ok, st.pass,
-                (unsigned long long)st.ntok, (unsigned long long)st.end_bit);
+                (unsigned long long)st.ntok, (unsigned long long)st.end_bit, st.parts, st.parts_max);
         for (uint32_t k = 0; k < st.seg_count && k < 12; ++k) {
             const PSeg &sg = hg[st.seg_first + k];
             fprintf(stderr, "   seg %u: start %lld end %lld status %d used %u ntok %llu tok_base %llu next %u", k,

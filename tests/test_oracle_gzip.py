@@ -82,3 +82,58 @@ def test_header_rules():
     assert gw.inflate(full[:11], raw_inflate)[0] == gw.NEED_MORE_INPUT            # XLEN incomplete
     assert gw.inflate(full[:15], raw_inflate)[0] == gw.NEED_MORE_INPUT            # FEXTRA bytes incomplete
     assert gw.inflate(full[:20], raw_inflate)[0] == gw.NEED_MORE_INPUT            # FNAME unterminated
+
+
+# ---- the header table of tests/checksum_cases.py ---------------------------------------------------------------------------------------
+
+def test_header_table_well_formed_rows_are_read_by_python_gzip():
+    """every row that is a whole member: Python's gzip module finds the same payload (it inflates the same bytes), its header parser
+    stops at the offset read_header gives, and the restatement inflates the member to its end"""
+    import checksum_cases as cc
+    rows = [(name, z) for name, z, whole in cc.header_rows() if whole]
+    assert len(rows) >= 16 + 5
+    for name, z in rows:
+        st, aux, off = gw.read_header(z)
+        assert (st, aux) == (gw.DONE, 0), name
+        assert gzip.decompress(z) == cc.H_DATA, name
+        assert zlib.decompress(z[off:], -15) == cc.H_DATA, name                   # the payload begins exactly there
+        if hasattr(gzip, "_read_gzip_header"):
+            fp = io.BytesIO(z)
+            gzip._read_gzip_header(fp)
+            assert fp.tell() == off, name
+        assert gw.inflate(z, raw_inflate)[:3] == (0, cc.H_DATA, len(z)), name
+
+
+def test_header_table_other_rows_follow_the_reference():
+    """The rows Python's gzip module cannot judge (it accepts FHCRC, other reserved bits ...): what the reference's parser answers, read
+    from its source.  Gzip.StreamHeader.read (Sources/LZ77/Gzip/Gzip.StreamHeader.swift) checks, in this order: ten bytes there (:21-25,
+    else nil = more input), the sigil (:27-32), the method, thrown with its code (:34-38), the reserved flag bits, thrown with the flag
+    byte (:40-44), FHCRC (:57-60), and with FEXTRA the two bytes of XLEN (:62-69, else nil).  The member's InflatorBuffers
+    (Sources/LZ77/Inflator/LZ77.InflatorBuffers.swift) then skips XLEN bytes once they are all there (:193-198) and one zero-terminated
+    string per set bit of FNAME and FCOMMENT -- it only COUNTS them (:157-166, :177-191), so which of the two comes first is not
+    something a parser of this format can tell."""
+    import checksum_cases as cc
+    m, h = cc.member(cc.ALL_FIELDS)
+    seen = set()
+    for name, z, whole in cc.header_rows():
+        if whole:
+            continue
+        got = gw.read_header(z)
+        if name.startswith("prefix-") or name == "header-ends-the-source":
+            cut = len(z)
+            want = (gw.DONE, 0, h) if cut >= h else (gw.NEED_MORE_INPUT, 0, 0)
+        elif name.startswith("xlen-65535-cut-"):
+            full = cc.member(cc.FEXTRA | cc.FNAME, extra=bytes(65535))[1]
+            want = (gw.DONE, 0, full) if len(z) >= full else (gw.NEED_MORE_INPUT, 0, 0)
+        elif name.startswith("reserved-") or name == "flags-before-fhcrc":
+            want = (gw.E_GZIP_FLAG_BITS, z[3], 0)
+        elif name.startswith("fhcrc"):
+            want = (gw.E_GZIP_HEADER_CHECKSUM, 0, 0)
+        elif name.startswith("method-"):
+            want = (gw.E_GZIP_METHOD, z[2], 0)
+        else:
+            assert name.startswith("sigil-"), name
+            want = (gw.E_GZIP_SIGIL, 0, 0)
+        assert got == want, (name, got, want)
+        seen.add(want[0])
+    assert seen == {gw.DONE, gw.NEED_MORE_INPUT, gw.E_GZIP_SIGIL, gw.E_GZIP_METHOD, gw.E_GZIP_FLAG_BITS, gw.E_GZIP_HEADER_CHECKSUM}

@@ -74,6 +74,45 @@ enum {
     SPNG_E_PROFILE_CHUNK_LENGTH = 105,         /* invalidColorProfileChunkLength(length, min: aux) */
     SPNG_E_PROFILE_COMPRESSION_METHOD = 106,   /* invalidColorProfileCompressionMethodCode(aux) */
     SPNG_E_PROFILE_INCOMPLETE = 107,           /* incompleteColorProfileCompressedDatastream (host side, as SPNG_E_TEXT_INCOMPLETE) */
+    /* the other 33 cases of PNG.ParsingError, in the order of its enum: the status of a record of spng_parse_dir_batch,
+     * payload in its aux[0], aux[1] */
+    SPNG_E_PARSE_HEADER_CHUNK_LENGTH = 128,            /* invalidHeaderChunkLength(aux0) */
+    SPNG_E_PARSE_HEADER_PIXEL_FORMAT_CODE = 129,       /* invalidHeaderPixelFormatCode((depth aux0, colour type aux1)) */
+    SPNG_E_PARSE_HEADER_PIXEL_FORMAT = 130,            /* invalidHeaderPixelFormat(_, standard: .ios): a CgBI file that is not rgb8 / rgba8;
+                                                          depth aux0, colour type aux1 */
+    SPNG_E_PARSE_HEADER_COMPRESSION_METHOD = 131,      /* invalidHeaderCompressionMethodCode(aux0) */
+    SPNG_E_PARSE_HEADER_FILTER = 132,                  /* invalidHeaderFilterCode(aux0) */
+    SPNG_E_PARSE_HEADER_INTERLACING = 133,             /* invalidHeaderInterlacingCode(aux0) */
+    SPNG_E_PARSE_HEADER_SIZE = 134,                    /* invalidHeaderSize((x: aux0, y: aux1)) */
+    SPNG_E_PARSE_UNEXPECTED_PALETTE = 135,             /* unexpectedPalette(pixel:): depth aux0, colour type aux1 */
+    SPNG_E_PARSE_PALETTE_CHUNK_LENGTH = 136,           /* invalidPaletteChunkLength(aux0) */
+    SPNG_E_PARSE_PALETTE_COUNT = 137,                  /* invalidPaletteCount(aux0, max: aux1 = 1 << min(depth, 8)) */
+    SPNG_E_PARSE_UNEXPECTED_TRANSPARENCY = 138,        /* unexpectedTransparency(pixel:), va / rgba only: depth aux0, colour type aux1 */
+    SPNG_E_PARSE_TRANSPARENCY_CHUNK_LENGTH = 139,      /* invalidTransparencyChunkLength(aux0, expected: aux1) */
+    SPNG_E_PARSE_TRANSPARENCY_SAMPLE = 140,            /* invalidTransparencySample(aux0 = v or max(r, g, b), max: aux1) */
+    SPNG_E_PARSE_TRANSPARENCY_COUNT = 141,             /* invalidTransparencyCount(aux0, max: aux1 = palette entries) */
+    SPNG_E_PARSE_BACKGROUND_CHUNK_LENGTH = 142,        /* invalidBackgroundChunkLength(aux0, expected: aux1) */
+    SPNG_E_PARSE_BACKGROUND_SAMPLE = 143,              /* invalidBackgroundSample(aux0, max: aux1) */
+    SPNG_E_PARSE_BACKGROUND_INDEX = 144,               /* invalidBackgroundIndex(aux0, max: aux1 = palette entries - 1) */
+    SPNG_E_PARSE_HISTOGRAM_CHUNK_LENGTH = 145,         /* invalidHistogramChunkLength(aux0, expected: aux1 = 2 x palette entries) */
+    SPNG_E_PARSE_GAMMA_CHUNK_LENGTH = 146,             /* invalidGammaChunkLength(aux0) */
+    SPNG_E_PARSE_CHROMATICITY_CHUNK_LENGTH = 147,      /* invalidChromaticityChunkLength(aux0) */
+    SPNG_E_PARSE_RENDERING_CHUNK_LENGTH = 148,         /* invalidColorRenderingChunkLength(aux0) */
+    SPNG_E_PARSE_RENDERING_CODE = 149,                 /* invalidColorRenderingCode(aux0) */
+    SPNG_E_PARSE_SIGNIFICANT_BITS_CHUNK_LENGTH = 150,  /* invalidSignificantBitsChunkLength(aux0, expected: aux1) */
+    SPNG_E_PARSE_SIGNIFICANT_BITS_PRECISION = 151,     /* invalidSignificantBitsPrecision(aux0 = the first one in payload order outside
+                                                          1 ... max, max: aux1) */
+    SPNG_E_PARSE_PHYSICAL_CHUNK_LENGTH = 152,          /* invalidPhysicalDimensionsChunkLength(aux0) */
+    SPNG_E_PARSE_PHYSICAL_UNIT = 153,                  /* invalidPhysicalDimensionsDensityUnitCode(aux0) */
+    SPNG_E_PARSE_SUGGESTED_PALETTE_CHUNK_LENGTH = 154, /* invalidSuggestedPaletteChunkLength(aux0, min: aux1 = k + 2) */
+    SPNG_E_PARSE_SUGGESTED_PALETTE_NAME = 155,         /* invalidSuggestedPaletteName(String?): aux0 as SPNG_E_TEXT_KEYWORD */
+    SPNG_E_PARSE_SUGGESTED_PALETTE_DATA_LENGTH = 156,  /* invalidSuggestedPaletteDataLength(aux0, stride: aux1) */
+    SPNG_E_PARSE_SUGGESTED_PALETTE_DEPTH = 157,        /* invalidSuggestedPaletteDepthCode(aux0) */
+    SPNG_E_PARSE_SUGGESTED_PALETTE_FREQUENCY = 158,    /* invalidSuggestedPaletteFrequency; aux0 = the index of the first entry whose
+                                                          frequency exceeds its predecessor's (the reference carries no payload) */
+    SPNG_E_PARSE_TIME_CHUNK_LENGTH = 159,              /* invalidTimeModifiedChunkLength(aux0) */
+    SPNG_E_PARSE_TIME = 160,                           /* invalidTimeModifiedTime: aux0 = year | month << 16 | day << 24,
+                                                          aux1 = hour | minute << 8 | second << 16 */
     /* boundary-level conditions with no reference counterpart */
     SPNG_E_TEXT_ENCODING = 112,       /* spng_text_batch, SPNG_TEXT_CHECK_UTF8: the input is not well-formed UTF-8 (the reference repairs
                                          such text silently: String(decoding:as:)) */
@@ -346,6 +385,56 @@ typedef struct spng_chunk_dir {
  * more room.  Heads are parsed by a wave per chunk, the separators found by ballots over 64-byte loads. */
 int32_t spng_lex_dir_batch(spng_ctx *ctx, const spng_file_desc *files, const spng_chunk_dir *dirs, uint32_t count,
                            spng_lexed *d_infos, spng_lexed *h_infos);
+
+/* ---- files: the typed chunks -- every parser of Sources/PNG/Parsing but PNG.Text's and PNG.ColorProfile's ------------------ */
+/* A record per chunk, parallel to the directory, and a record per file.  Each record is the answer of the reference's parser for that
+ * chunk on its own (checks in the reference's order: the first that fails decides), given the file's header and palette:
+ *     IHDR  PNG.Header.init(parsing:standard:)             Parsing/PNG.Header.swift:73-129
+ *     PLTE  PNG.Palette.init(parsing:pixel:)               Parsing/PNG.Palette.swift:54-81
+ *     tRNS  PNG.Transparency.init(parsing:pixel:palette:)  Parsing/PNG.Transparency.swift:126-180
+ *     bKGD  PNG.Background.init(parsing:pixel:palette:)    Parsing/PNG.Background.swift:119-176
+ *     hIST  PNG.Histogram.init(parsing:palette:)           Parsing/PNG.Histogram.swift:49-61
+ *     gAMA cHRM sRGB pHYs tIME                             PNG.Gamma / Chromaticity / ColorRendering / PhysicalDimensions / TimeModified
+ *     sBIT  PNG.SignificantBits.init(parsing:pixel:)       Parsing/PNG.SignificantBits.swift:60-110
+ *     sPLT  PNG.SuggestedPalette.init(parsing:)            Parsing/PNG.SuggestedPalette.swift:54-156
+ * The header is entry 0, or entry 1 behind a CgBI chunk (which makes the file PNG.Standard.ios).  A chunk's palette is the FIRST PLTE
+ * among the entries if it stands in front of the chunk and parsed (PNG.Image.swift:298-400, PNG.Metadata.swift:151-246).  Which chunk
+ * may stand where -- duplicate, unexpected, required -- stays the host's rule; chunks behind a bad one are parsed all the same.
+ * v[] by chunk type: IHDR width, height, depth, colour type, interlace; tRNS / bKGD of a format that is not indexed 1 or 3 samples;
+ * bKGD of an indexed one the index; gAMA the value; cHRM the eight values in payload order; sRGB the code; sBIT up to 4 precisions;
+ * pHYs x, y, unit; tIME year, month, day, hour, minute, second; sPLT the depth.  PLTE, hIST, the alphas of an indexed tRNS and the
+ * entries of an sPLT stay in the payload: `count` says how many there are.  Words without a meaning are zero, and so is all of v
+ * beside a status that is not SPNG_DONE. */
+enum { SPNG_SCOPE_NONE = 0,                     /* no parser here: IDAT, IEND, CgBI, tEXt / zTXt / iTXt / iCCP (their heads are the
+                                                   directory's), private chunks */
+       SPNG_SCOPE_PARSED = 1,                   /* the parser ran: status and values are its answer */
+       SPNG_SCOPE_NO_HEADER = 2,                /* the file's IHDR is not where it must be, or did not parse: no parser behind it ran */
+       SPNG_SCOPE_NO_PALETTE = 3 };             /* hIST, or bKGD / tRNS of an indexed image, with no PLTE that parsed in front of it (the
+                                                   reference throws DecodingError.required(PLTE, before:): the host's rule) */
+typedef struct spng_chunk_value {               /* 64 bytes */
+    int32_t  status;                            /* SPNG_DONE or one of SPNG_E_PARSE_* */
+    uint32_t scope;
+    uint64_t aux[2];
+    uint32_t count;                             /* PLTE: entries; indexed tRNS: alphas; hIST: entries; sPLT: entries */
+    uint32_t k;                                 /* sPLT: payload offset of the NUL behind the name, else SPNG_NO_OFFSET */
+    uint32_t v[8];
+} spng_chunk_value;
+typedef struct spng_parsed {                    /* per file */
+    int32_t  status;                            /* of the first record in file order whose status is not SPNG_DONE (SPNG_DONE: none) */
+    uint32_t index;                             /* ... and its index (SPNG_NO_OFFSET: none) */
+    uint64_t aux[2];
+    uint32_t ihdr_index, plte_index;            /* SPNG_NO_OFFSET: none among the entries */
+    uint32_t palette_count;                     /* of that PLTE if it parsed, else 0 */
+    uint8_t  depth, color, ios, interlaced;     /* of the header if it parsed, else 0 (ios: entry 0 is CgBI) */
+} spng_parsed;
+/* files, dirs, d_infos: exactly what spng_lex_dir_batch consumed and produced, still on the device; the entries a file has are
+ * min(d_infos[i].chunks, dirs[i].cap).  d_values[i]: device memory for dirs[i].cap records, 8-byte aligned (NULL with a cap of 0);
+ * records behind the entries stay untouched.  d_parsed / h_parsed: a record per file; with d_parsed alone the call is asynchronous on the context's
+ * stream, and nothing waits between it and a spng_lex_dir_batch in front of it.  A wave per chunk; an sPLT's frequencies are
+ * compared 64 entries per step.  SPNG_E_ARGUMENT (the call): a null array with a non-zero count, a null d_values[i] or a null
+ * d_entries with a non-zero cap. */
+int32_t spng_parse_dir_batch(spng_ctx *ctx, const spng_file_desc *files, const spng_chunk_dir *dirs, const spng_lexed *d_infos,
+                             spng_chunk_value *const *d_values, uint32_t count, spng_parsed *d_parsed, spng_parsed *h_parsed);
 
 /* ---- text: the byte work between a text chunk's body and a String ------------------------------------------------ */
 enum { SPNG_TEXT_LATIN1_TO_UTF8 = 1,  /* String(uncompressed.map{ Character(Unicode.Scalar($0)) }).utf8 (PNG.Text.swift:198): a byte >= 0x80

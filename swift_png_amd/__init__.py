@@ -35,6 +35,16 @@ E_OUTPUT_CAPACITY, E_ARGUMENT, E_DEVICE, E_REFERENCE_UNDEFINED = 64, 65, 66, 67
  E_TEXT_INCOMPLETE) = range(96, 103)
 E_PROFILE_NAME, E_PROFILE_CHUNK_LENGTH, E_PROFILE_COMPRESSION_METHOD, E_PROFILE_INCOMPLETE = range(104, 108)
 E_TEXT_ENCODING = 112
+# the other 33 cases of PNG.ParsingError, in the order of its enum: the status of a ChunkValue (spng_parse_dir_batch)
+(E_PARSE_HEADER_CHUNK_LENGTH, E_PARSE_HEADER_PIXEL_FORMAT_CODE, E_PARSE_HEADER_PIXEL_FORMAT, E_PARSE_HEADER_COMPRESSION_METHOD,
+ E_PARSE_HEADER_FILTER, E_PARSE_HEADER_INTERLACING, E_PARSE_HEADER_SIZE, E_PARSE_UNEXPECTED_PALETTE, E_PARSE_PALETTE_CHUNK_LENGTH,
+ E_PARSE_PALETTE_COUNT, E_PARSE_UNEXPECTED_TRANSPARENCY, E_PARSE_TRANSPARENCY_CHUNK_LENGTH, E_PARSE_TRANSPARENCY_SAMPLE,
+ E_PARSE_TRANSPARENCY_COUNT, E_PARSE_BACKGROUND_CHUNK_LENGTH, E_PARSE_BACKGROUND_SAMPLE, E_PARSE_BACKGROUND_INDEX,
+ E_PARSE_HISTOGRAM_CHUNK_LENGTH, E_PARSE_GAMMA_CHUNK_LENGTH, E_PARSE_CHROMATICITY_CHUNK_LENGTH, E_PARSE_RENDERING_CHUNK_LENGTH,
+ E_PARSE_RENDERING_CODE, E_PARSE_SIGNIFICANT_BITS_CHUNK_LENGTH, E_PARSE_SIGNIFICANT_BITS_PRECISION, E_PARSE_PHYSICAL_CHUNK_LENGTH,
+ E_PARSE_PHYSICAL_UNIT, E_PARSE_SUGGESTED_PALETTE_CHUNK_LENGTH, E_PARSE_SUGGESTED_PALETTE_NAME, E_PARSE_SUGGESTED_PALETTE_DATA_LENGTH,
+ E_PARSE_SUGGESTED_PALETTE_DEPTH, E_PARSE_SUGGESTED_PALETTE_FREQUENCY, E_PARSE_TIME_CHUNK_LENGTH, E_PARSE_TIME) = range(128, 161)
+SCOPE_NONE, SCOPE_PARSED, SCOPE_NO_HEADER, SCOPE_NO_PALETTE = 0, 1, 2, 3
 NO_OFFSET = 0xffffffff
 TEXT_LATIN1_TO_UTF8, TEXT_CHECK_UTF8 = 1, 2
 TEXT_TILE = 4096                                            # csrc/text.hip: bytes of a tile (the tests place their boundaries by it)
@@ -80,7 +90,7 @@ EXPORTS = [
     "spng_shard", "spng_decode_batch_multi", "spng_copy_ceiling", "spng_trim", "spng_lds_exchange_ordered", "spng_deflate_state_bytes", "spng_deflate_resume_batch",
     "spng_lex_state_bytes", "spng_lex_resume_batch", "spng_lex_resume_stats",
     "spng_file_bound", "spng_write_file_batch", "spng_compress_batch",
-    "spng_lex_dir_batch", "spng_text_batch",
+    "spng_lex_dir_batch", "spng_text_batch", "spng_parse_dir_batch",
 ]
 
 
@@ -133,6 +143,17 @@ class ChunkEntry(ctypes.Structure):
 
 class ChunkDir(ctypes.Structure):
     _fields_ = [("d_entries", ctypes.c_void_p), ("cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ChunkValue(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("scope", ctypes.c_uint32), ("aux", ctypes.c_uint64 * 2), ("count", ctypes.c_uint32),
+                ("k", ctypes.c_uint32), ("v", ctypes.c_uint32 * 8)]
+
+
+class Parsed(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("index", ctypes.c_uint32), ("aux", ctypes.c_uint64 * 2), ("ihdr_index", ctypes.c_uint32),
+                ("plte_index", ctypes.c_uint32), ("palette_count", ctypes.c_uint32), ("depth", ctypes.c_uint8), ("color", ctypes.c_uint8),
+                ("ios", ctypes.c_uint8), ("interlaced", ctypes.c_uint8)]
 
 
 class TextDesc(ctypes.Structure):
@@ -275,7 +296,7 @@ class LexingError(SpngError):            # PNG.LexingError
     pass
 
 
-class ParsingError(SpngError):           # PNG.ParsingError (the cases of PNG.Text and PNG.ColorProfile)
+class ParsingError(SpngError):           # PNG.ParsingError
     pass
 
 
@@ -294,6 +315,16 @@ _NAMES = {
     100: "invalidTextCompressionMethodCode", 101: "invalidTextCompressionCode", 102: "incompleteTextCompressedDatastream",
     104: "invalidColorProfileName", 105: "invalidColorProfileChunkLength", 106: "invalidColorProfileCompressionMethodCode",
     107: "incompleteColorProfileCompressedDatastream", 112: "textEncoding",
+    128: "invalidHeaderChunkLength", 129: "invalidHeaderPixelFormatCode", 130: "invalidHeaderPixelFormat",
+    131: "invalidHeaderCompressionMethodCode", 132: "invalidHeaderFilterCode", 133: "invalidHeaderInterlacingCode", 134: "invalidHeaderSize",
+    135: "unexpectedPalette", 136: "invalidPaletteChunkLength", 137: "invalidPaletteCount", 138: "unexpectedTransparency",
+    139: "invalidTransparencyChunkLength", 140: "invalidTransparencySample", 141: "invalidTransparencyCount",
+    142: "invalidBackgroundChunkLength", 143: "invalidBackgroundSample", 144: "invalidBackgroundIndex", 145: "invalidHistogramChunkLength",
+    146: "invalidGammaChunkLength", 147: "invalidChromaticityChunkLength", 148: "invalidColorRenderingChunkLength",
+    149: "invalidColorRenderingCode", 150: "invalidSignificantBitsChunkLength", 151: "invalidSignificantBitsPrecision",
+    152: "invalidPhysicalDimensionsChunkLength", 153: "invalidPhysicalDimensionsDensityUnitCode", 154: "invalidSuggestedPaletteChunkLength",
+    155: "invalidSuggestedPaletteName", 156: "invalidSuggestedPaletteDataLength", 157: "invalidSuggestedPaletteDepthCode",
+    158: "invalidSuggestedPaletteFrequency", 159: "invalidTimeModifiedChunkLength", 160: "invalidTimeModifiedTime",
 }
 
 
@@ -310,7 +341,7 @@ def raise_for(status, aux=(0, 0)):
         raise DecodingError(status, aux)
     if 80 <= status < 96:
         raise LexingError(status, aux)
-    if 96 <= status < 112:
+    if 96 <= status < 112 or 128 <= status <= 160:
         raise ParsingError(status, aux)
     raise SpngError(status, aux)
 
@@ -373,6 +404,8 @@ def load_library():
     lib.spng_lex_resume_batch.argtypes = [vp, ctypes.POINTER(FileDesc), ctypes.POINTER(vp), u32, vp, ctypes.POINTER(Lexed)]
     lib.spng_lex_dir_batch.argtypes = [vp, ctypes.POINTER(FileDesc), ctypes.POINTER(ChunkDir), u32, vp, ctypes.POINTER(Lexed)]
     lib.spng_text_batch.argtypes = [vp, ctypes.POINTER(TextDesc), u32, vp, rp]
+    lib.spng_parse_dir_batch.argtypes = [vp, ctypes.POINTER(FileDesc), ctypes.POINTER(ChunkDir), vp, ctypes.POINTER(vp), u32, vp,
+                                         ctypes.POINTER(Parsed)]
     lib.spng_lex_resume_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.spng_write_idat_batch.argtypes = [vp, ctypes.POINTER(ChunkingDesc), u32, vp, rp]
     lib.spng_crc32.argtypes = [vp, vp, u64, ctypes.POINTER(u32)]
@@ -791,6 +824,50 @@ class Session:
             entries.append(list((ChunkEntry * k).from_buffer_copy(raw)))
         idats = d_idat if device_idat else [bytes(b[:r.idat_len].cpu().numpy()) for b, r in zip(d_idat, infos)]
         return list(infos)[:n], idats, entries
+
+    def lex_parse_batch(self, files, caps=None, d_png=None):
+        """lex_dir_batch with the typed chunks: spng_lex_dir_batch with its infos left on the device, and parse_dir_batch directly
+        behind it -- nothing waits in between.  -> (list[Lexed], list of list[ChunkEntry], list of list[ChunkValue], list[Parsed],
+        d_png, d_idat: the device tensors of the files and of their IDAT payloads)"""
+        t = self.torch
+        n = len(files)
+        d_png = d_png or [self.to_device(f) for f in files]
+        d_idat = [self.empty(len(f)) for f in files]
+        caps = [len(f) // 12 for f in files] if caps is None else [int(c) for c in caps]
+        esz = ctypes.sizeof(ChunkEntry)
+        d_ent = [t.full((max(c, 1) * esz,), 0xEE, dtype=t.uint8, device=self.tdev) for c in caps]
+        d_infos = t.zeros(max(n, 1) * ctypes.sizeof(Lexed), dtype=t.uint8, device=self.tdev)
+        descs, dirs = (FileDesc * max(n, 1))(), (ChunkDir * max(n, 1))()
+        for i, (f, a, b) in enumerate(zip(files, d_png, d_idat)):
+            descs[i] = FileDesc(self._ptr(a), len(f), self._ptr(b), len(f))
+            dirs[i] = ChunkDir(d_ent[i].data_ptr() if caps[i] else None, caps[i], 0)
+        _check(self.lib, self.lib.spng_lex_dir_batch(self.ctx, descs, dirs, n, d_infos.data_ptr(), None))
+        values, parsed = self.parse_dir_batch(files, d_png, dirs, d_infos)
+        infos = list((Lexed * max(n, 1)).from_buffer_copy(d_infos.cpu().numpy().tobytes()))[:n]
+        entries = [list((ChunkEntry * len(v)).from_buffer_copy(e[:len(v) * esz].cpu().numpy().tobytes())) for e, v in zip(d_ent, values)]
+        return infos, entries, values, parsed, d_png, d_idat
+
+    def parse_dir_batch(self, files, d_png, dirs, d_infos):
+        """spng_parse_dir_batch behind a spng_lex_dir_batch whose results are still on the device.  files: list of PNG file bytes (their
+        lengths are what counts); d_png: the files as device tensors; dirs: the (ChunkDir * n) array the directory was made with;
+        d_infos: the device tensor its infos went to.  -> (list of list[ChunkValue] -- the first min(chunks, cap) records of each
+        file --, list[Parsed])"""
+        t = self.torch
+        n = len(files)
+        vsz = ctypes.sizeof(ChunkValue)
+        d_val = [t.full((max(dirs[i].cap, 1) * vsz,), 0xEE, dtype=t.uint8, device=self.tdev) for i in range(n)]
+        descs, vals = (FileDesc * max(n, 1))(), (ctypes.c_void_p * max(n, 1))()
+        for i, (f, a) in enumerate(zip(files, d_png)):
+            descs[i] = FileDesc(self._ptr(a), len(f), None, 0)
+            vals[i] = d_val[i].data_ptr() if dirs[i].cap else None
+        parsed = (Parsed * max(n, 1))()
+        _check(self.lib, self.lib.spng_parse_dir_batch(self.ctx, descs, dirs, self._ptr(d_infos), vals, n, None, parsed))
+        infos = (Lexed * max(n, 1)).from_buffer_copy(d_infos.cpu().numpy().tobytes())
+        out = []
+        for i in range(n):
+            k = min(infos[i].chunks, dirs[i].cap)
+            out.append(list((ChunkValue * k).from_buffer_copy(d_val[i][:k * vsz].cpu().numpy().tobytes())))
+        return out, list(parsed)[:n]
 
     def text_batch(self, texts, op, out_caps=None):
         """spng_text_batch over device tensors (or bytes, which are uploaded).  op: TEXT_LATIN1_TO_UTF8 / TEXT_CHECK_UTF8, one or a list;

@@ -82,6 +82,25 @@ const char *spng_status_string(int32_t s)
     case SPNG_E_PROFILE_COMPRESSION_METHOD: return "invalid compression method code in color profile chunk";
     case SPNG_E_PROFILE_INCOMPLETE: return "compressed datastream of color profile chunk is incomplete";
     case SPNG_E_TEXT_ENCODING: return "text is not well-formed utf-8";
+    // PNG.ParsingError.message without its scope (PNG.ParsingError.swift:397-473): the status names the chunk
+    case SPNG_E_PARSE_HEADER_CHUNK_LENGTH: case SPNG_E_PARSE_PALETTE_CHUNK_LENGTH: case SPNG_E_PARSE_TRANSPARENCY_CHUNK_LENGTH:
+    case SPNG_E_PARSE_BACKGROUND_CHUNK_LENGTH: case SPNG_E_PARSE_HISTOGRAM_CHUNK_LENGTH: case SPNG_E_PARSE_GAMMA_CHUNK_LENGTH:
+    case SPNG_E_PARSE_CHROMATICITY_CHUNK_LENGTH: case SPNG_E_PARSE_RENDERING_CHUNK_LENGTH: case SPNG_E_PARSE_SIGNIFICANT_BITS_CHUNK_LENGTH:
+    case SPNG_E_PARSE_PHYSICAL_CHUNK_LENGTH: case SPNG_E_PARSE_SUGGESTED_PALETTE_CHUNK_LENGTH: case SPNG_E_PARSE_SUGGESTED_PALETTE_DATA_LENGTH:
+    case SPNG_E_PARSE_TIME_CHUNK_LENGTH: return "invalid chunk length";
+    case SPNG_E_PARSE_HEADER_PIXEL_FORMAT_CODE: case SPNG_E_PARSE_HEADER_COMPRESSION_METHOD: case SPNG_E_PARSE_HEADER_FILTER:
+    case SPNG_E_PARSE_HEADER_INTERLACING: case SPNG_E_PARSE_RENDERING_CODE: case SPNG_E_PARSE_PHYSICAL_UNIT:
+    case SPNG_E_PARSE_SUGGESTED_PALETTE_DEPTH: return "invalid flag code";
+    case SPNG_E_PARSE_HEADER_PIXEL_FORMAT: return "invalid pixel format";
+    case SPNG_E_PARSE_HEADER_SIZE: return "invalid image size";
+    case SPNG_E_PARSE_UNEXPECTED_PALETTE: case SPNG_E_PARSE_UNEXPECTED_TRANSPARENCY: return "unexpected chunk";
+    case SPNG_E_PARSE_PALETTE_COUNT: case SPNG_E_PARSE_TRANSPARENCY_COUNT: return "invalid count";
+    case SPNG_E_PARSE_TRANSPARENCY_SAMPLE: case SPNG_E_PARSE_BACKGROUND_SAMPLE: return "invalid sample";
+    case SPNG_E_PARSE_BACKGROUND_INDEX: return "invalid index";
+    case SPNG_E_PARSE_SIGNIFICANT_BITS_PRECISION: return "invalid precision";
+    case SPNG_E_PARSE_SUGGESTED_PALETTE_NAME: return "invalid name";
+    case SPNG_E_PARSE_SUGGESTED_PALETTE_FREQUENCY: return "invalid frequency";
+    case SPNG_E_PARSE_TIME: return "invalid time";
     case SPNG_E_GZIP_SIGIL: return "invalid gzip sigil";
     case SPNG_E_GZIP_METHOD: return "invalid gzip compression method";
     case SPNG_E_GZIP_FLAG_BITS: return "invalid gzip flag bits";

@@ -339,6 +339,258 @@ __global__ __launch_bounds__(64) void dir_head_kernel(const spng_file_desc *__re
     }
 }
 
+// ---- the typed chunks (spng_parse_dir_batch) --------------------------------------------------------------------------------
+// Behind the directory, over what it left on the device: a record per entry with the answer of the reference's parser for that chunk,
+//   PNG.Header.init(parsing:standard:)         Sources/PNG/Parsing/PNG.Header.swift:73-129
+//   PNG.Palette.init(parsing:pixel:)           PNG.Palette.swift:54-81          PNG.Histogram.init(parsing:palette:)    PNG.Histogram.swift:49-61
+//   PNG.Transparency.init(parsing:...)         PNG.Transparency.swift:126-180   PNG.Background.init(parsing:...)        PNG.Background.swift:119-176
+//   PNG.SignificantBits.init(parsing:pixel:)   PNG.SignificantBits.swift:60-110 PNG.SuggestedPalette.init(parsing:)     PNG.SuggestedPalette.swift:54-156
+//   PNG.Gamma, Chromaticity, ColorRendering, PhysicalDimensions, TimeModified .init(parsing:)
+// its checks in its order.  `parse_scope_kernel`, a wave per file: the header -- entry 0, or entry 1 behind CgBI -- and the first PLTE
+// among the entries (64 types per step, a ballot, the first set bit), parsed against the header: what every other parser of the file
+// is handed (PNG.Image.swift:298-400, PNG.Metadata.swift:151-246).  `parse_value_kernel`, a wave per entry on dir_head_kernel's grid:
+// a wave-uniform branch per chunk type; the first 64 bytes of the payload a byte per lane, fields read across the lanes; the
+// frequencies of an sPLT 64 entries per step, each lane's against its left neighbour's.  `parse_first_kernel`, a wave per file: the
+// first record in file order that holds an error -- read from the records once they are all there, so no order in which the waves
+// finish can change it.
+static constexpr uint32_t T_CgBI = 0x43674249, T_IHDR = 0x49484452, T_PLTE = 0x504c5445, T_tRNS = 0x74524e53, T_bKGD = 0x624b4744,
+                          T_hIST = 0x68495354, T_gAMA = 0x67414d41, T_cHRM = 0x6348524d, T_sRGB = 0x73524742, T_sBIT = 0x73424954,
+                          T_pHYs = 0x70485973, T_tIME = 0x74494d45, T_sPLT = 0x73504c54;
+
+// what a file's parsers are handed: the pixel format (depth 0: no header), the standard, the entries of the palette in front of the chunk
+struct ParseScope { uint32_t depth, color, ios; bool palette; uint32_t palette_count; };
+
+__device__ __forceinline__ bool parsed_type(uint32_t name)
+{
+    return name == T_IHDR || name == T_PLTE || name == T_tRNS || name == T_bKGD || name == T_hIST || name == T_gAMA || name == T_cHRM ||
+           name == T_sRGB || name == T_sBIT || name == T_pHYs || name == T_tIME || name == T_sPLT;
+}
+// PNG.Format.Pixel.recognize(code:) (Formats/PNG.Format.swift)
+__device__ __forceinline__ bool pixel_format(uint32_t depth, uint32_t color)
+{
+    switch (color) {
+    case 0: return depth == 1 || depth == 2 || depth == 4 || depth == 8 || depth == 16;
+    case 3: return depth == 1 || depth == 2 || depth == 4 || depth == 8;
+    case 2: case 4: case 6: return depth == 8 || depth == 16;
+    default: return false;
+    }
+}
+// byte j of the payload's first 64, which the lanes hold a byte each; big-endian fields from there
+__device__ __forceinline__ uint32_t at8(uint32_t b, int j) { return (uint32_t)__shfl((int)b, j); }
+__device__ __forceinline__ uint32_t at16(uint32_t b, int j) { return at8(b, j) << 8 | at8(b, j + 1); }
+__device__ __forceinline__ uint32_t at32(uint32_t b, int j) { return at16(b, j) << 16 | at16(b, j + 2); }
+
+__device__ __forceinline__ spng_chunk_value parse_fail(spng_chunk_value r, int32_t status, uint64_t aux0, uint64_t aux1 = 0)
+{
+    r.status = status; r.aux[0] = aux0; r.aux[1] = aux1;
+    return r;
+}
+
+// descendingFrequency (PNG.SuggestedPalette.swift:125-156) over `entries` of `stride` bytes: -> the index of the first entry whose
+// frequency -- its last two bytes -- exceeds its predecessor's (the first one's: UInt16.max), or SPNG_NO_OFFSET
+__device__ __forceinline__ uint32_t first_ascent(const gbyte *data, uint32_t entries, uint32_t stride, int lane)
+{
+    uint32_t carry = 0xffff;                                   // the frequency in front of the step
+    for (uint64_t base = 0; base < entries; base += 64) {
+        const uint64_t i = base + lane;
+        const bool in = i < entries;
+        const uint32_t cur = in ? (uint32_t)data[i * stride + stride - 2] << 8 | data[i * stride + stride - 1] : 0;
+        uint32_t prev = (uint32_t)__shfl_up((int)cur, 1);
+        if (lane == 0) prev = carry;
+        const unsigned long long up = __ballot(in && cur > prev);
+        if (up) return (uint32_t)base + (uint32_t)__ffsll((long long)up) - 1;
+        carry = (uint32_t)__shfl((int)cur, 63);
+    }
+    return SPNG_NO_OFFSET;
+}
+
+// one chunk.  Every argument but `lane` is the same in all lanes, and so is every branch
+__device__ __forceinline__ spng_chunk_value parse_value(uint32_t name, const gbyte *payload, uint32_t length, const ParseScope s, int lane)
+{
+    spng_chunk_value r;
+    memset(&r, 0, sizeof r);
+    r.status = SPNG_DONE; r.scope = SPNG_SCOPE_NONE; r.k = SPNG_NO_OFFSET;
+    if (!parsed_type(name)) return r;
+    if (!s.depth) { r.scope = SPNG_SCOPE_NO_HEADER; return r; }
+    const bool indexed = s.color == 3, has_color = (s.color & 2) != 0, has_alpha = (s.color & 4) != 0;
+    if ((name == T_hIST || ((name == T_tRNS || name == T_bKGD) && indexed)) && !s.palette) { r.scope = SPNG_SCOPE_NO_PALETTE; return r; }
+    r.scope = SPNG_SCOPE_PARSED;
+    const uint32_t b = (uint32_t)lane < length ? payload[lane] : 0;
+    const uint32_t sample_max = 0xffffu >> (16 - s.depth);
+    if (name == T_IHDR) {
+        if (length != 13) return parse_fail(r, SPNG_E_PARSE_HEADER_CHUNK_LENGTH, length);
+        const uint32_t depth = at8(b, 8), color = at8(b, 9), compression = at8(b, 10), filter = at8(b, 11), interlace = at8(b, 12);
+        if (!pixel_format(depth, color)) return parse_fail(r, SPNG_E_PARSE_HEADER_PIXEL_FORMAT_CODE, depth, color);
+        if (s.ios && !(depth == 8 && (color == 2 || color == 6))) return parse_fail(r, SPNG_E_PARSE_HEADER_PIXEL_FORMAT, depth, color);
+        if (compression) return parse_fail(r, SPNG_E_PARSE_HEADER_COMPRESSION_METHOD, compression);
+        if (filter) return parse_fail(r, SPNG_E_PARSE_HEADER_FILTER, filter);
+        if (interlace > 1) return parse_fail(r, SPNG_E_PARSE_HEADER_INTERLACING, interlace);
+        const uint32_t x = at32(b, 0), y = at32(b, 4);
+        if (!x || !y) return parse_fail(r, SPNG_E_PARSE_HEADER_SIZE, x, y);
+        r.v[0] = x; r.v[1] = y; r.v[2] = depth; r.v[3] = color; r.v[4] = interlace;
+    } else if (name == T_PLTE) {
+        if (!has_color) return parse_fail(r, SPNG_E_PARSE_UNEXPECTED_PALETTE, s.depth, s.color);
+        if (length % 3) return parse_fail(r, SPNG_E_PARSE_PALETTE_CHUNK_LENGTH, length);
+        const uint32_t count = length / 3, most = 1u << (s.depth < 8 ? s.depth : 8);
+        if (count < 1 || count > most) return parse_fail(r, SPNG_E_PARSE_PALETTE_COUNT, count, most);
+        r.count = count;
+    } else if (name == T_tRNS || name == T_bKGD) {
+        const bool fill = name == T_bKGD;
+        if (has_alpha && !fill) return parse_fail(r, SPNG_E_PARSE_UNEXPECTED_TRANSPARENCY, s.depth, s.color);
+        if (indexed && !fill) {
+            if (length > s.palette_count) return parse_fail(r, SPNG_E_PARSE_TRANSPARENCY_COUNT, length, s.palette_count);
+            r.count = length;
+        } else if (indexed) {
+            if (length != 1) return parse_fail(r, SPNG_E_PARSE_BACKGROUND_CHUNK_LENGTH, length, 1);
+            const uint32_t index = at8(b, 0);
+            if (index >= s.palette_count) return parse_fail(r, SPNG_E_PARSE_BACKGROUND_INDEX, index, s.palette_count - 1);
+            r.v[0] = index;
+        } else {
+            const uint32_t samples = has_color ? 3 : 1;
+            if (length != 2 * samples)
+                return parse_fail(r, fill ? SPNG_E_PARSE_BACKGROUND_CHUNK_LENGTH : SPNG_E_PARSE_TRANSPARENCY_CHUNK_LENGTH, length, 2 * samples);
+            const uint32_t c0 = at16(b, 0), c1 = at16(b, 2), c2 = at16(b, 4);      // (behind a grey sample: zeros)
+            const uint32_t top = c0 > c1 ? (c0 > c2 ? c0 : c2) : (c1 > c2 ? c1 : c2);
+            if (top > sample_max) return parse_fail(r, fill ? SPNG_E_PARSE_BACKGROUND_SAMPLE : SPNG_E_PARSE_TRANSPARENCY_SAMPLE, top, sample_max);
+            r.v[0] = c0; r.v[1] = c1; r.v[2] = c2;
+        }
+    } else if (name == T_hIST) {
+        if (length != 2 * s.palette_count) return parse_fail(r, SPNG_E_PARSE_HISTOGRAM_CHUNK_LENGTH, length, 2 * s.palette_count);
+        r.count = length / 2;
+    } else if (name == T_gAMA) {
+        if (length != 4) return parse_fail(r, SPNG_E_PARSE_GAMMA_CHUNK_LENGTH, length);
+        r.v[0] = at32(b, 0);
+    } else if (name == T_cHRM) {
+        if (length != 32) return parse_fail(r, SPNG_E_PARSE_CHROMATICITY_CHUNK_LENGTH, length);
+        for (int j = 0; j < 8; ++j) r.v[j] = at32(b, 4 * j);
+    } else if (name == T_sRGB) {
+        if (length != 1) return parse_fail(r, SPNG_E_PARSE_RENDERING_CHUNK_LENGTH, length);
+        const uint32_t code = at8(b, 0);
+        if (code > 3) return parse_fail(r, SPNG_E_PARSE_RENDERING_CODE, code);
+        r.v[0] = code;
+    } else if (name == T_sBIT) {
+        const uint32_t arity = (has_color ? 3 : 1) + (has_alpha ? 1 : 0), most = indexed ? 8 : s.depth;
+        if (length != arity) return parse_fail(r, SPNG_E_PARSE_SIGNIFICANT_BITS_CHUNK_LENGTH, length, arity);
+        const unsigned long long bad = __ballot((uint32_t)lane < arity && (b < 1 || b > most));
+        if (bad) return parse_fail(r, SPNG_E_PARSE_SIGNIFICANT_BITS_PRECISION, at8(b, __ffsll((long long)bad) - 1), most);
+        for (int j = 0; j < 4; ++j) r.v[j] = at8(b, j);
+    } else if (name == T_pHYs) {
+        if (length != 9) return parse_fail(r, SPNG_E_PARSE_PHYSICAL_CHUNK_LENGTH, length);
+        const uint32_t unit = at8(b, 8);
+        if (unit > 1) return parse_fail(r, SPNG_E_PARSE_PHYSICAL_UNIT, unit);
+        r.v[0] = at32(b, 0); r.v[1] = at32(b, 4); r.v[2] = unit;
+    } else if (name == T_tIME) {
+        if (length != 7) return parse_fail(r, SPNG_E_PARSE_TIME_CHUNK_LENGTH, length);
+        // month, day, hour, minute, second in lanes 2 ... 6: each against its own range
+        const uint32_t lo = lane == 2 || lane == 3 ? 1 : 0, hi = lane == 2 ? 12 : lane == 3 ? 31 : lane == 4 ? 23 : lane == 5 ? 59 : 60;
+        const unsigned long long bad = __ballot(lane >= 2 && lane <= 6 && (b < lo || b > hi));
+        const uint32_t year = at16(b, 0), month = at8(b, 2), day = at8(b, 3), hour = at8(b, 4), minute = at8(b, 5), second = at8(b, 6);
+        if (bad) return parse_fail(r, SPNG_E_PARSE_TIME, year | month << 16 | day << 24, hour | minute << 8 | second << 16);
+        r.v[0] = year; r.v[1] = month; r.v[2] = day; r.v[3] = hour; r.v[4] = minute; r.v[5] = second;
+    } else {                                                   // sPLT
+        const uint32_t k = find_nul(payload, 0, length, lane);
+        if (k != SPNG_NO_OFFSET) r.k = k;
+        if (k == SPNG_NO_OFFSET || !valid_keyword(payload, k, lane)) return parse_fail(r, SPNG_E_PARSE_SUGGESTED_PALETTE_NAME, k != SPNG_NO_OFFSET);
+        if ((uint64_t)k + 1 >= length) return parse_fail(r, SPNG_E_PARSE_SUGGESTED_PALETTE_CHUNK_LENGTH, length, (uint64_t)k + 2);
+        const uint32_t bytes = length - k - 2, code = payload[k + 1];
+        if (code != 8 && code != 16) return parse_fail(r, SPNG_E_PARSE_SUGGESTED_PALETTE_DEPTH, code);
+        const uint32_t stride = code == 8 ? 6 : 10;
+        if (bytes % stride) return parse_fail(r, SPNG_E_PARSE_SUGGESTED_PALETTE_DATA_LENGTH, bytes, stride);
+        const uint32_t up = first_ascent(payload + k + 2, bytes / stride, stride, lane);
+        if (up != SPNG_NO_OFFSET) return parse_fail(r, SPNG_E_PARSE_SUGGESTED_PALETTE_FREQUENCY, up);
+        r.count = bytes / stride; r.v[0] = code;
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(64) void parse_scope_kernel(const spng_file_desc *__restrict__ files, const spng_chunk_dir *__restrict__ dirs,
+                                                         const spng_lexed *__restrict__ out, spng_chunk_value *const *__restrict__ values,
+                                                         spng_parsed *__restrict__ parsed)
+{
+    const int lane = threadIdx.x;
+    const uint32_t file = blockIdx.x;
+    const uint32_t chunks = UNI(out[file].chunks), cap = UNI(dirs[file].cap);
+    const uint32_t n = chunks < cap ? chunks : cap;
+    const spng_chunk_entry *entries = (const spng_chunk_entry *)uni64((uint64_t)dirs[file].d_entries);
+    spng_chunk_value *vals = (spng_chunk_value *)uni64((uint64_t)values[file]);
+    const gbyte *p = (const gbyte *)uni64((uint64_t)files[file].d_png);
+    spng_parsed r;
+    memset(&r, 0, sizeof r);
+    r.status = SPNG_DONE; r.index = r.ihdr_index = r.plte_index = SPNG_NO_OFFSET;
+    ParseScope s;
+    s.depth = s.color = s.ios = s.palette_count = 0; s.palette = false;
+    // PNG.Image.swift:303-321: CgBI?, IHDR
+    s.ios = n && UNI(entries[0].type) == T_CgBI;
+    const uint32_t at = s.ios;
+    if (at < n && UNI(entries[at].type) == T_IHDR) {
+        ParseScope first = s;
+        first.depth = 8;                                       // (the header's own parser asks for no header)
+        const spng_chunk_value h = parse_value(T_IHDR, p + uni64(entries[at].offset), UNI(entries[at].length), first, lane);
+        if (lane == 0) vals[at] = h;
+        r.ihdr_index = at;
+        if (h.status == SPNG_DONE) { s.depth = h.v[2]; s.color = h.v[3]; r.interlaced = (uint8_t)h.v[4]; }
+    }
+    // the first PLTE
+    uint32_t plte = SPNG_NO_OFFSET;
+    for (uint64_t base = 0; base < n && plte == SPNG_NO_OFFSET; base += 64) {
+        const uint64_t i = base + lane;
+        const unsigned long long hit = __ballot(i < n && entries[i].type == T_PLTE);
+        if (hit) plte = (uint32_t)base + (uint32_t)__ffsll((long long)hit) - 1;
+    }
+    if (plte != SPNG_NO_OFFSET) {
+        const spng_chunk_value v = parse_value(T_PLTE, p + uni64(entries[plte].offset), UNI(entries[plte].length), s, lane);
+        if (lane == 0) vals[plte] = v;
+        r.plte_index = plte;
+        if (v.scope == SPNG_SCOPE_PARSED && v.status == SPNG_DONE) r.palette_count = v.count;
+    }
+    r.depth = (uint8_t)s.depth; r.color = (uint8_t)s.color; r.ios = (uint8_t)s.ios;
+    if (lane == 0) parsed[file] = r;
+}
+
+__global__ __launch_bounds__(64) void parse_value_kernel(const spng_file_desc *__restrict__ files, const spng_chunk_dir *__restrict__ dirs,
+                                                         const spng_lexed *__restrict__ out, spng_chunk_value *const *__restrict__ values,
+                                                         const spng_parsed *__restrict__ parsed)
+{
+    const int lane = threadIdx.x;
+    const uint32_t file = blockIdx.y;
+    const uint32_t chunks = UNI(out[file].chunks), cap = UNI(dirs[file].cap);
+    const uint32_t n = chunks < cap ? chunks : cap;
+    if (blockIdx.x >= n) return;
+    const spng_chunk_entry *entries = (const spng_chunk_entry *)uni64((uint64_t)dirs[file].d_entries);
+    spng_chunk_value *vals = (spng_chunk_value *)uni64((uint64_t)values[file]);
+    const gbyte *p = (const gbyte *)uni64((uint64_t)files[file].d_png);
+    const uint32_t ihdr = UNI(parsed[file].ihdr_index), plte = UNI(parsed[file].plte_index), palette_count = UNI(parsed[file].palette_count);
+    ParseScope s;
+    s.depth = UNI(parsed[file].depth); s.color = UNI(parsed[file].color); s.ios = UNI(parsed[file].ios);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        if (i == ihdr || i == plte) continue;                  // (parse_scope_kernel's)
+        s.palette = plte < i && palette_count != 0; s.palette_count = s.palette ? palette_count : 0;
+        const spng_chunk_value r = parse_value(UNI(entries[i].type), p + uni64(entries[i].offset), UNI(entries[i].length), s, lane);
+        if (lane == 0) vals[i] = r;
+    }
+}
+
+__global__ __launch_bounds__(64) void parse_first_kernel(const spng_chunk_dir *__restrict__ dirs, const spng_lexed *__restrict__ out,
+                                                         spng_chunk_value *const *__restrict__ values, spng_parsed *__restrict__ parsed)
+{
+    const int lane = threadIdx.x;
+    const uint32_t file = blockIdx.x;
+    const uint32_t chunks = UNI(out[file].chunks), cap = UNI(dirs[file].cap);
+    const uint32_t n = chunks < cap ? chunks : cap;
+    const spng_chunk_value *vals = (const spng_chunk_value *)uni64((uint64_t)values[file]);
+    for (uint64_t base = 0; base < n; base += 64) {
+        const uint64_t i = base + lane;
+        const unsigned long long bad = __ballot(i < n && vals[i].status != SPNG_DONE);
+        if (!bad) continue;
+        const uint32_t first = (uint32_t)base + (uint32_t)__ffsll((long long)bad) - 1;
+        if (lane == 0) {
+            spng_parsed &r = parsed[file];
+            r.status = vals[first].status; r.index = first; r.aux[0] = vals[first].aux[0]; r.aux[1] = vals[first].aux[1];
+        }
+        return;
+    }
+}
+
 // ---- files that arrive in pieces (spng_lex_resume_batch) --------------------------------------------------------------------
 // The reference's OnlineDecoding tutorial (Snippets/PNG/OnlineDecoding.swift) retries signature() and chunk() on truncatedSignature /
 // truncatedChunkHeader / truncatedChunkBody until the bytes are there.  Here the loop's state lives on the device between the pushes:
@@ -819,6 +1071,21 @@ hipError_t launch_lex_dir(const spng_file_desc *d_files, const spng_chunk_dir *d
     return launch_rows(count, [&](uint32_t y0, uint32_t ny) {
         dir_head_kernel<<<dim3(bx, ny), 64, 0, stream>>>(d_files + y0, d_dirs + y0, d_out + y0);
     });
+}
+hipError_t launch_parse_dir(const spng_file_desc *d_files, const spng_chunk_dir *d_dirs, uint32_t count, const spng_lexed *d_infos,
+                            spng_chunk_value *const *d_values, uint32_t most_entries, spng_parsed *d_parsed, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    parse_scope_kernel<<<count, 64, 0, stream>>>(d_files, d_dirs, d_infos, d_values, d_parsed);
+    if (most_entries) {
+        const uint32_t bx = lex_piece_blocks_x(count, most_entries);
+        const hipError_t e = launch_rows(count, [&](uint32_t y0, uint32_t ny) {
+            parse_value_kernel<<<dim3(bx, ny), 64, 0, stream>>>(d_files + y0, d_dirs + y0, d_infos + y0, d_values + y0, d_parsed + y0);
+        });
+        if (e != hipSuccess) return e;
+    }
+    parse_first_kernel<<<count, 64, 0, stream>>>(d_dirs, d_infos, d_values, d_parsed);
+    return hipGetLastError();
 }
 size_t lex_state_bytes() { return sizeof(LexState); }
 size_t lex_piece_bytes() { return sizeof(LexPiece); }

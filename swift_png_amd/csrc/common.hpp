@@ -486,6 +486,9 @@ hipError_t launch_lex(const spng_file_desc *d_files, uint32_t count, spng_lexed 
                       void *d_walks, uint32_t max_listed, hipStream_t stream);
 hipError_t launch_lex_dir(const spng_file_desc *d_files, const spng_chunk_dir *d_dirs, uint32_t count, const spng_lexed *d_out, const void *d_table,
                           const uint64_t *d_table_at, const void *d_walks, uint32_t most_entries, hipStream_t stream);
+// behind launch_lex_dir on the same stream, over its files, directories and infos; most_entries as there
+hipError_t launch_parse_dir(const spng_file_desc *d_files, const spng_chunk_dir *d_dirs, uint32_t count, const spng_lexed *d_infos,
+                            spng_chunk_value *const *d_values, uint32_t most_entries, spng_parsed *d_parsed, hipStream_t stream);
 size_t text_tiles(uint64_t len);
 // blocks_x: workgroups along x of the per-tile kernels (0: no text of the call has a tile); writes: some text is transcoded
 hipError_t launch_text(const TextJob *d_jobs, uint32_t count, uint32_t blocks_x, bool writes, spng_result *d_results, hipStream_t stream);

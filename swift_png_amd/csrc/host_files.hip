@@ -132,6 +132,41 @@ int32_t spng_lex_dir_batch(spng_ctx *c, const spng_file_desc *files, const spng_
     return lex_batch(c, files, nullptr, count, d_infos, h_infos, dirs);
 }
 
+int32_t spng_parse_dir_batch(spng_ctx *c, const spng_file_desc *files, const spng_chunk_dir *dirs, const spng_lexed *d_infos,
+                             spng_chunk_value *const *d_values, uint32_t count, spng_parsed *d_parsed, spng_parsed *h_parsed)
+{
+    if (!c || ((!files || !dirs || !d_infos || !d_values) && count) || (!d_parsed && !h_parsed && count)) return SPNG_E_ARGUMENT;
+    if (!count) return SPNG_DONE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->mu);
+    uint32_t most_entries = 0;                                 // (as the directory's: no chunk is shorter than 12 bytes)
+    for (uint32_t i = 0; i < count; ++i) {
+        if ((!files[i].d_png && files[i].len) || (dirs[i].cap && (!dirs[i].d_entries || !d_values[i])) || ((uintptr_t)d_values[i] & 7) ||
+            dirs[i].reserved)
+            return SPNG_E_ARGUMENT;
+        most_entries = std::max(most_entries, (uint32_t)std::min<uint64_t>(dirs[i].cap, files[i].len / 12));
+    }
+    // the tables go up behind whatever the stream still holds -- the directory's kernels, as a rule --: nothing here waits for them
+    if (int32_t st = c->reserve(count * (sizeof(spng_file_desc) + sizeof(spng_chunk_dir) + sizeof(void *) + sizeof(spng_parsed)) + 4096)) return st;
+    Arena a{c};
+    const size_t fslot = a.take(count * sizeof(spng_file_desc));
+    memcpy(a.host<spng_file_desc>(fslot), files, count * sizeof(spng_file_desc));
+    const size_t dslot = a.take(count * sizeof(spng_chunk_dir));
+    memcpy(a.host<spng_chunk_dir>(dslot), dirs, count * sizeof(spng_chunk_dir));
+    const size_t vslot = a.take(count * sizeof(void *));
+    memcpy(a.host<void *>(vslot), d_values, count * sizeof(void *));
+    const size_t upload = a.off;
+    const size_t pslot = a.take(count * sizeof(spng_parsed));
+    if (int32_t st = c->upload(0, upload)) return st;
+    spng_parsed *dp = d_parsed ? d_parsed : a.dev<spng_parsed>(pslot);
+    {
+        Timed t(c, SPNG_K_LEX);
+        HIP_TRY(launch_parse_dir(a.dev<spng_file_desc>(fslot), a.dev<spng_chunk_dir>(dslot), count, d_infos, a.dev<spng_chunk_value *>(vslot),
+                                 most_entries, dp, c->stream));
+    }
+    return read_back(c, h_parsed, dp, count * sizeof(spng_parsed));
+}
+
 uint64_t spng_lex_state_bytes(void) { return lex_state_bytes(); }
 
 int32_t spng_lex_resume_batch(spng_ctx *c, const spng_file_desc *files, void *const *d_states, uint32_t count, spng_lexed *d_infos,

@@ -89,9 +89,12 @@ class ColorProfile:
 class Metadata:
     """PNG.Metadata (Sources/PNG/Decoding/PNG.Metadata.swift:5-95).  Typed: time -- (year, month, day, hour, minute, second),
     PNG.TimeModified --, gamma -- the numerator over 100000, PNG.Gamma --, physicalDimensions -- (x, y, unit byte),
-    PNG.PhysicalDimensions --, colorProfile -- ColorProfile --, text -- [Text].  Carried as their payload bytes, uninterpreted:
-    chromaticity, colorRendering, significantBits, histogram, suggestedPalettes (a list of payloads) and application (a list of
-    (type, payload))."""
+    PNG.PhysicalDimensions --, colorProfile -- ColorProfile --, text -- [Text].  From PNG.decompress(typed=True), out of the records of
+    spng_parse_dir_batch: chromaticity -- the eight values in payload order, PNG.Chromaticity --, colorRendering -- the code,
+    PNG.ColorRendering --, significantBits -- the precisions, PNG.SignificantBits --, histogram -- the frequencies, PNG.Histogram --,
+    suggestedPalettes -- (name, depth, [(r, g, b, a, frequency)]), PNG.SuggestedPalette.  From the default, untyped decompress these
+    five are carried as their payload bytes, uninterpreted (a field that holds bytes is written back as it is).  application: a list
+    of (type, payload)."""
 
     def __init__(self, time=None, chromaticity=None, colorProfile=None, colorRendering=None, gamma=None, histogram=None,
                  physicalDimensions=None, significantBits=None, suggestedPalettes=(), text=(), application=()):
@@ -99,11 +102,14 @@ class Metadata:
         self.gamma, self.histogram, self.physicalDimensions, self.significantBits = gamma, histogram, physicalDimensions, significantBits
         self.suggestedPalettes, self.text, self.application = list(suggestedPalettes), list(text), list(application)
 
-    def push(self, chunk, palette_seen=False, parsed=None):
+    def push(self, chunk, palette_seen=False, parsed=None, value=None):
         """push(ancillary:pixel:palette:background:transparency:) (PNG.Metadata.swift:151-245) for every chunk but bKGD and tRNS,
         which are the format's: chunk = (type, payload); parsed: the Text or ColorProfile of a text or profile chunk, which the
         device has taken apart (PNG.decompress).  Raises UnexpectedChunk for cHRM gAMA sRGB iCCP sBIT behind PLTE (:159-164),
-        RequiredChunk for hIST without PLTE (:190-194), DuplicateChunk for a second one of the unique chunks (:98-108)."""
+        RequiredChunk for hIST without PLTE (:190-194), DuplicateChunk for a second one of the unique chunks (:98-108).  value: the
+        chunk's record of spng_parse_dir_batch; with one, its status is raised behind those rules -- unique(assign:) looks for the
+        duplicate before it parses (:99-108) -- and the field is typed from it."""
+        from . import ParsingError
         kind, payload = chunk
         if kind in ("CgBI", "IHDR", "PLTE", "IDAT", "IEND", "bKGD", "tRNS"):
             raise ValueError(f"Metadata.push cannot be used with chunk type '{kind}'")       # (:166-170: fatalError)
@@ -114,7 +120,16 @@ class Metadata:
         if kind in _UNIQUE:
             if getattr(self, _UNIQUE[kind]) is not None:
                 raise DuplicateChunk(kind)
-            if kind == "gAMA":                                   # PNG.Gamma.init(parsing:): one big-endian UInt32
+            if value is not None and value.status != DONE:
+                raise ParsingError(value.status, tuple(value.aux))
+            if value is not None and kind != "iCCP":             # the record's words, as many as the field has
+                v, count = tuple(value.v), value.count
+                if kind == "hIST":
+                    value = list(struct.unpack(">" + "H" * count, payload))
+                else:
+                    width = {"gAMA": 1, "sRGB": 1, "pHYs": 3, "tIME": 6, "cHRM": 8, "sBIT": len(payload)}[kind]
+                    value = v[0] if width == 1 and kind != "sBIT" else v[:width]
+            elif kind == "gAMA":                                  # PNG.Gamma.init(parsing:): one big-endian UInt32
                 value = struct.unpack(">I", payload)[0]
             elif kind == "pHYs":                                 # PNG.PhysicalDimensions.init(parsing:): x, y, unit
                 value = struct.unpack(">IIB", payload)
@@ -126,7 +141,14 @@ class Metadata:
                 value = bytes(payload)
             setattr(self, _UNIQUE[kind], value)
         elif kind == "sPLT":
-            self.suggestedPalettes.append(bytes(payload))
+            if value is not None and value.status != DONE:
+                raise ParsingError(value.status, tuple(value.aux))
+            if value is not None:                                # PNG.SuggestedPalette.swift:79-112
+                fmt = ">BBBBH" if value.v[0] == 8 else ">HHHHH"
+                entries = [struct.unpack_from(fmt, payload, value.k + 2 + i * struct.calcsize(fmt)) for i in range(value.count)]
+                self.suggestedPalettes.append((payload[:value.k].decode("latin-1"), value.v[0], entries))
+            else:
+                self.suggestedPalettes.append(bytes(payload))
         elif kind in ("iTXt", "tEXt", "zTXt"):
             self.text.append(parsed)
         else:
@@ -137,25 +159,30 @@ class Metadata:
         (PNG.Image.swift:596-656).  deflated: the streams of colorProfile and of the compressed texts, in that order"""
         deflated = list(deflated)
         before, after = [], []
+        raw = lambda v, pack: bytes(v) if isinstance(v, (bytes, bytearray)) else pack(v)  # noqa: E731  (an untyped field: as it came)
+
+        def palette(p):                                          # PNG.SuggestedPalette.serialized
+            name, depth, entries = p
+            return name.encode("latin-1") + b"\0" + bytes([depth]) + b"".join(struct.pack(">BBBBH" if depth == 8 else ">HHHHH", *e) for e in entries)
         if self.chromaticity is not None:
-            before.append(("cHRM", self.chromaticity))
+            before.append(("cHRM", raw(self.chromaticity, lambda v: struct.pack(">8I", *v))))
         if self.gamma is not None:
             before.append(("gAMA", struct.pack(">I", self.gamma)))
         if self.colorRendering is not None:
-            before.append(("sRGB", self.colorRendering))
+            before.append(("sRGB", raw(self.colorRendering, lambda v: bytes([v]))))
         if self.colorProfile is not None:                        # PNG.ColorProfile.serialized (PNG.ColorProfile.swift:87-103)
             before.append(("iCCP", self.colorProfile.name.encode("latin-1") + b"\0\0" + deflated.pop(0)))
         if self.significantBits is not None:
-            before.append(("sBIT", self.significantBits))
+            before.append(("sBIT", raw(self.significantBits, bytes)))
         if self.histogram is not None:
-            after.append(("hIST", self.histogram))
+            after.append(("hIST", raw(self.histogram, lambda v: struct.pack(">" + "H" * len(v), *v))))
         if self.physicalDimensions is not None:
             after.append(("pHYs", struct.pack(">IIB", *self.physicalDimensions)))
         if self.time is not None:
             after.append(("tIME", struct.pack(">HBBBBB", *self.time)))
         for t in self.text:                                      # every text as iTXt (PNG.Text.serialized, PNG.Text.swift:309-349)
             after.append(("iTXt", t.head() + (deflated.pop(0) if t.compressed else t.content.encode("utf-8"))))
-        after += [("sPLT", p) for p in self.suggestedPalettes] + list(self.application)
+        after += [("sPLT", raw(p, palette)) for p in self.suggestedPalettes] + list(self.application)
         as_bytes = lambda cs: [(k.encode("latin-1") if isinstance(k, str) else bytes(k), bytes(p)) for k, p in cs]  # noqa: E731
         return as_bytes(before), as_bytes(after)
 
@@ -562,14 +589,27 @@ class PNG:
     Metadata, Text, ColorProfile, Image = Metadata, Text, ColorProfile, Image
 
     @staticmethod
-    def _walk(entries, names, info, metadata, work, payload):
+    def _walk(entries, names, info, metadata, work, payload, values=None):
         """the loops of PNG.Image.decompress behind IHDR (PNG.Image.swift:323-399) over a file's directory: which chunks may stand
-        where.  Text and profile chunks go to `work`, their places to the metadata; PLTE, bKGD, tRNS to metadata._critical"""
-        from . import ParsingError
+        where.  Text and profile chunks go to `work`, their places to the metadata; PLTE, bKGD, tRNS to metadata._critical.  values: the
+        records of spng_parse_dir_batch beside the entries (typed): a chunk's order rules come first, then its record's status; the
+        records of PLTE, bKGD, tRNS go to metadata._records"""
+        from . import SCOPE_NO_PALETTE, ParsingError
         plte = bkgd = trns = None
         seen_idat = done_idat = False
         metadata._critical = (None, None, None)
-        for e, kind in zip(entries, names):
+        metadata._records = {}
+
+        def parsed(kind, v):
+            if v is None:
+                return
+            if v.scope == SCOPE_NO_PALETTE:                      # PNG.Transparency.swift:165-169, PNG.Background.swift:158-162
+                raise RequiredChunk("PLTE", kind)
+            if v.status != DONE:
+                raise ParsingError(v.status, tuple(v.aux))
+            metadata._records[kind] = v
+        for i, (e, kind) in enumerate(zip(entries, names)):
+            value = values[i] if values is not None else None
             if kind == "IDAT":
                 if done_idat:
                     raise UnexpectedChunk("IDAT", "IDAT")        # (PNG.Context.swift:133-135)
@@ -594,12 +634,14 @@ class PNG:
                     raise UnexpectedChunk("PLTE", "bKGD")
                 if trns is not None:
                     raise UnexpectedChunk("PLTE", "tRNS")
+                parsed(kind, value)                              # PNG.Image.swift:355
                 plte = payload(e)
                 metadata._critical = (plte, bkgd, trns)
                 continue
             elif kind in ("bKGD", "tRNS"):                       # PNG.Metadata.swift:173-182
                 if (bkgd if kind == "bKGD" else trns) is not None:
                     raise DuplicateChunk(kind)
+                parsed(kind, value)
                 if kind == "bKGD":
                     bkgd = payload(e)
                 else:
@@ -614,23 +656,31 @@ class PNG:
                 work.append((e, kind))
                 metadata.push((kind, b""), palette_seen=plte is not None, parsed=len(work) - 1)
             else:
-                metadata.push((kind, payload(e)), palette_seen=plte is not None)
+                metadata.push((kind, payload(e)), palette_seen=plte is not None, value=value)
 
     @staticmethod
-    def decompress(data, session=None) -> Image:
+    def decompress(data, typed=False, session=None) -> Image:
         """PNG.Image.decompress(stream:) (Sources/PNG/PNG.Image.swift:298-400) for a whole file: lexed on the device with its chunk
         directory (spng_lex_dir_batch), the image decoded there from the IDAT bytes the lexer gathered (spng_decode_batch), the heads of
         the text and profile chunks parsed there; their compressed bodies inflated in one spng_inflate_batch call straight from the
         file's bytes in device memory, Latin-1 contents transcoded and iTXt contents checked in one spng_text_batch call.  The host
         sees the infos, the directory, the small chunks and the finished contents; it applies the rules about which chunks may
         stand where (RequiredChunk, DuplicateChunk, UnexpectedChunk) and reads PLTE / tRNS / bKGD.  An iTXt content that is not
-        well-formed UTF-8 is repaired on the host with errors="replace"."""
+        well-formed UTF-8 is repaired on the host with errors="replace".
+        typed: every other chunk is parsed on the device as well (spng_parse_dir_batch, enqueued behind the directory with no wait in
+        between): the header's ParsingError is raised first (:317), every chunk's behind the rules about its place, PLTE / tRNS /
+        bKGD are validated and read from their records, and the metadata's fields are typed (Metadata).  The default answers what
+        it always has: a malformed typed chunk travels as it is."""
         from . import (E_OUTPUT_CAPACITY, E_PROFILE_INCOMPLETE, E_TEXT_ENCODING, E_TEXT_INCOMPLETE, FORMAT_IOS, FORMAT_ZLIB,
                        NEED_MORE_INPUT, TEXT_CHECK_UTF8, TEXT_LATIN1_TO_UTF8, ParsingError, load, raise_for, storage_size, inflated_size)
         s = session or load()
         data = bytes(data)
         d_png = s.to_device(data)
-        (info,), (d_idat,), (entries,) = s.lex_dir_batch([data], d_png=[d_png], device_idat=True)
+        values = None
+        if typed:
+            (info,), (entries,), (values,), _, _, (d_idat,) = s.lex_parse_batch([data], d_png=[d_png])
+        else:
+            (info,), (d_idat,), (entries,) = s.lex_dir_batch([data], d_png=[d_png], device_idat=True)
         # (the chunks in front of a lexing failure have been lexed in full: what is wrong with them comes first, as in the reference's loop)
         names = [_name(e.type) for e in entries]
         payload = lambda e: data[e.offset:e.offset + e.length]  # noqa: E731
@@ -641,11 +691,13 @@ class PNG:
         if names[at] != "IHDR":
             raise RequiredChunk("IHDR", names[at])
         ios = at == 1
+        if typed and values[at].status != DONE:                  # :317: PNG.Header.init(parsing:standard:) throws
+            raise ParsingError(values[at].status, tuple(values[at].aux))
         metadata = Metadata()
         work = []                                                # (entry, kind): the text and profile chunks, in file order
         pending = None                                           # the first thing wrong with the chunks: raised once the bodies in front of it have been looked at
         try:
-            PNG._walk(entries[at + 1:], names[at + 1:], info, metadata, work, payload)
+            PNG._walk(entries[at + 1:], names[at + 1:], info, metadata, work, payload, values[at + 1:] if typed else None)
         except (ChunkOrderError, ParsingError) as err:
             pending = err
         plte, bkgd, trns = metadata._critical
@@ -721,12 +773,22 @@ class PNG:
             v = struct.unpack(">" + "H" * (len(raw) // 2), raw)
             return v[0] if len(v) == 1 else (v[::-1] if ios else v)
 
-        if plte is not None:
+        if typed:                                                # the records: counts and samples as the parsers left them
+            rec = metadata._records
+            if "PLTE" in rec:
+                alphas = trns[:rec["tRNS"].count] if indexed and "tRNS" in rec else b""
+                palette = [(plte[3 * k], plte[3 * k + 1], plte[3 * k + 2], alphas[k] if k < len(alphas) else 255) for k in range(rec["PLTE"].count)]
+            samples = lambda v: v.v[0] if info.color in (0, 4) else (tuple(v.v[:3])[::-1] if ios else tuple(v.v[:3]))  # noqa: E731
+            if "tRNS" in rec and not indexed:
+                key = samples(rec["tRNS"])
+            if "bKGD" in rec:
+                fill = rec["bKGD"].v[0] if indexed else samples(rec["bKGD"])
+        elif plte is not None:
             alphas = trns if indexed and trns is not None else b""
             palette = [(plte[3 * k], plte[3 * k + 1], plte[3 * k + 2], alphas[k] if k < len(alphas) else 255) for k in range(len(plte) // 3)]
-        if trns is not None and not indexed:
+        if not typed and trns is not None and not indexed:
             key = fields(trns)
-        if bkgd is not None:
+        if not typed and bkgd is not None:
             fill = bkgd[0] if indexed else fields(bkgd)
         return Image(size, info.depth, channels, indexed, ios, bool(info.interlace), palette, key, fill, storage, metadata)
 
